@@ -15,7 +15,21 @@ deep-supervision L1 loss, backward, gradient all-reduce (mean), Adam step.  Inpu
 generated on the device before the timed region.  Weak scaling: every rank processes --batch
 segments.
 
-Rank 0 prints ONE JSON line (contract in the task brief) with these extra objects:
+Rank 0 prints ONE JSON line: the headline (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall time of the --steps timed steps / steps) and the run's configuration.  A plain
+run does nothing else: it sets up, warms up, times the steps, writes the outputs of the last
+step if --dump-outputs DIR is given, and prints the line.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last step computed, as float32
+.npy files (see dump_outputs): out (the six decoder layers' predictions), loss, geometry (the
+step's [initial, refined] point errors), grads (the flat gradient buffer after the exchange) and
+state (every floating state_dict entry after the Adam step, concatenated in state_dict order).
+An array of more than DUMP_MAX_ELEMS elements is replaced by a fixed seeded sample of that many.
+Inputs, initial weights and dropout seeds are all seeded, so two builds run with the same
+arguments can be compared file by file.  That holds for eager steps (the default), which are
+bit-identical from run to run; --graph replays are not (their losses differ between processes).
+
+--full adds everything else the benchmark measures, as extra objects of the same line:
   roofline      the dominant kernel of the timed region, timed live with HIP events on its
                 launch stream (library profiler), against the peak of the MFMA products it
                 issues; roofline.step = whole-step algorithmic FLOPs over the step time
@@ -25,6 +39,9 @@ Rank 0 prints ONE JSON line (contract in the task brief) with these extra object
   cpu_baseline  the oracle (CPU restatement of the reference, kind "port") timed on the host
                 cores on a bounded sample of the same workload (rank 0, N=1 only): full
                 fwd+bwd (= value), encoder-only fwd+bwd, eval forward
+  workloads     the other BASELINE.json configurations (extra_workloads), at B=4096, N=1024 only
+The live per-launch HIP events behind roofline are recorded with --full, or with --kernels K,
+which prints the K longest GEMM launches without the rest of --full.
 """
 import argparse
 import json
@@ -78,10 +95,17 @@ def parse():
     ap.add_argument("--graph", action="store_true",
                     help="capture forward+loss+backward in a HIP graph (small, launch-bound batches)")
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam instead of the fused flat-buffer Adam")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the exact-fp32 parity step after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline, parity, workloads, "
+                         "cpu_baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline object")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the exact-fp32 parity step after the timed region")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="skip the `workloads` object (the other BASELINE.json configs, run after the timed region)")
+                    help="with --full: skip the `workloads` object (the other BASELINE.json configs, run after the "
+                         "timed region)")
     ap.add_argument("--kernels", type=int, default=0, help="print the K longest GEMM launches (live HIP-event times) to stderr")
     ap.add_argument("--cpu-batch", type=int, default=16,
                     help="segments in the CPU sample (16: the host's best throughput; 64 measured 2.5x slower per segment)")
@@ -241,6 +265,45 @@ def pmc_traffic(dname, batch, points, mode):
         return None, fn
     r = max(cands, key=lambda r: r["fetch_bytes_largest_launch"])      # the fusion-layer launch
     return r["fetch_bytes_largest_launch"] + (r["write_bytes_largest_launch"] or 0.0), fn
+
+
+DUMP_MAX_ELEMS = 1 << 22        # per array (16 MB in float32): at most three arrays reach it, < 64 MB in all
+DUMP_SAMPLE_SEED = 20240217
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> tensor.  Writes DIR/<name>.npy in float32 (float64 stays float64).  An array of
+    more than DUMP_MAX_ELEMS elements is flattened and replaced by the elements at DUMP_MAX_ELEMS
+    indices drawn without replacement by a generator seeded with DUMP_SAMPLE_SEED, in ascending
+    order: the same positions in every run with the same shapes."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        total += a.nbytes
+    log(f"dumped {len(arrays)} arrays ({total / 2**20:.1f} MiB) to {dirname}")
+
+
+def step_outputs(step, model, loss):
+    """What one TrainStep call hands its caller, for dump_outputs: the loss it returns, the predictions
+    and step metrics it keeps (keep_out must have been set before the step), the flat gradient buffer,
+    and the model state the optimiser step left behind."""
+    import torch
+    arrays = {"out": step.last_out, "loss": loss}
+    if step.geometry is not None:
+        arrays["geometry"] = step.geometry
+    arrays["grads"] = step.grads.flat
+    state = [v.reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()]
+    arrays["state"] = torch.cat(state)
+    return arrays
 
 
 class StubNet:
@@ -622,12 +685,14 @@ def run(args):
         return 0.0 if args.stub else torch.cuda.max_memory_allocated(dev) / 2**30
 
     parity_init = None
-    if lib is not None and mode in (2, 4) and not args.no_parity and not args.graph:
+    if lib is not None and args.full and mode in (2, 4) and not args.no_parity and not args.graph:
         # reduced precision: per-tensor gradient parity at the INITIAL weights (see grade_parity)
         try:
             parity_init = parity_check(step, model, (ctx, noisy, target), lib, mode, dev)
         except torch.cuda.OutOfMemoryError:
             parity_init = None
+    dump = args.dump_outputs is not None and rank == 0
+    step.keep_out = dump               # predictions are kept only to be dumped (a captured graph keeps them too)
     for i in range(args.warmup):
         loss = step(ctx, noisy, target)
         if rank == 0:
@@ -639,26 +704,30 @@ def run(args):
     # step and decoder chunk pair); if it still fills up only whole steps are counted
     cap = 0
     marks = []
-    if lib is not None:
+    prof = lib is not None and (args.full or args.kernels > 0)
+    if prof:
         chunks = max(1, -(-B // max(1, args.decoder_chunk)))
         cap = min(262144, (args.steps + 1) * (400 + 300 * chunks))
         lib.prh_profile_enable(cap)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step(ctx, noisy, target)
-        if lib is not None:
+        if prof:
             marks.append(lib.prh_profile_count())
     sync()
     dt = time.perf_counter() - t0
     if rank == 0:
         log(f"timed {args.steps} steps in {dt:.3f} s")
+    if dump:
+        dump_outputs(args.dump_outputs, step_outputs(step, model, loss))
+        step.keep_out, step.last_out = False, None
     if launched:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
     roofline = None
-    if lib is not None:
+    if prof:
         if args.graph:
             # the library's per-launch events are not recorded inside a replayed graph: one eager
             # step after the timed region supplies the per-kernel figures of the roofline object
@@ -688,7 +757,7 @@ def run(args):
         if rank == 0 and args.kernels > 0:
             for k, (c, t, f, _) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:args.kernels]:
                 print(f"[bench] {k:44s} x{c:4d} {t / c:8.3f} ms  {f / (t / c * 1e-3) / 1e12:7.1f} TF", file=sys.stderr)
-        if agg:
+        if agg and args.full:
             # dominant = the kernel (name incl. its GEMM shape) with the most time in the timed region
             dname, (cnt, tot_ms, flops, bytes_) = max(agg.items(), key=lambda kv: kv[1][1])
             avg_ms = tot_ms / cnt
@@ -730,7 +799,7 @@ def run(args):
                                           "segment (SURVEY 8d) / step time, against the peak of this GEMM mode"}}
 
     parity = None
-    if lib is not None and not args.no_parity and not args.graph:
+    if lib is not None and args.full and not args.no_parity and not args.graph:
         try:
             vhat = None
             if mode in (2, 4) and getattr(step.opt, "exp_avg_sq", None) is not None and step.opt.steps > 0:
@@ -747,7 +816,7 @@ def run(args):
         parity_failed = bool(f.item() > 0)
 
     workloads = None
-    if (rank == 0 and world == 1 and lib is not None and not args.no_workloads and not args.graph
+    if (rank == 0 and world == 1 and lib is not None and args.full and not args.no_workloads and not args.graph
             and B == 4096 and N == 1024):
         # free the headline run's buffers first: config 3 alone needs ~140 GB
         final_loss = float(loss)
@@ -788,7 +857,7 @@ def run(args):
             line["parity"] = parity
         if workloads is not None:
             line["workloads"] = workloads
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, args.cpu_batch)
         emit(line)
     if launched:
@@ -851,11 +920,18 @@ def run_encoder(args):
         log(f"warmup {i} done, mem {torch.cuda.max_memory_allocated(dev) / 2**30:.1f} GiB")
     lib.prh_profile_enable(min(262144, (args.steps + 1) * 200))
     torch.cuda.synchronize(dev)
+    dump = args.dump_outputs is not None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        if dump and i == args.steps - 1:
+            last = step()              # only the last step's returns are held: fused is B x N x 1024
+        else:
+            step()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
+    if dump:
+        dump_outputs(args.dump_outputs, {"global_feat": last[0], "fused": last[1]})
+        del last
     agg = {}
     name = C.create_string_buffer(64)
     ms, fl, by = C.c_float(), C.c_double(), C.c_double()

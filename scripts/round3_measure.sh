@@ -9,11 +9,11 @@ mkdir -p $O
 case "$1" in
 A)
   timeout -k 10 900 python -m pytest tests -m gpu -q > $O/tests.log 2>&1; echo "tests rc=$?"; tail -3 $O/tests.log
-  python bench.py --steps 20 --warmup 5 > $O/bench_split16.json 2> $O/bench_split16.err; echo "default rc=$?"
-  python bench.py --steps 20 --warmup 5 --gemm bf16 --no-cpu-baseline --no-workloads > $O/bench_bf16.json 2> $O/bench_bf16.err; echo "bf16 rc=$?"
-  python bench.py --batch 32 --points 2048 --steps 50 --warmup 10 --no-cpu-baseline > $O/b32.json 2>/dev/null
-  python bench.py --batch 32 --points 2048 --steps 50 --warmup 10 --no-cpu-baseline --graph > $O/b32g.json 2>/dev/null
-  python bench.py --batch 4096 --points 2048 --decoder-chunk 2048 --steps 5 --warmup 2 --no-cpu-baseline --no-workloads --no-parity --gemm bf16 > $O/b4096n2048_bf16.json 2>/dev/null
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_split16.json 2> $O/bench_split16.err; echo "default rc=$?"
+  python bench.py --full --steps 20 --warmup 5 --gemm bf16 --no-cpu-baseline --no-workloads > $O/bench_bf16.json 2> $O/bench_bf16.err; echo "bf16 rc=$?"
+  python bench.py --full --batch 32 --points 2048 --steps 50 --warmup 10 --no-cpu-baseline > $O/b32.json 2>/dev/null
+  python bench.py --full --batch 32 --points 2048 --steps 50 --warmup 10 --no-cpu-baseline --graph > $O/b32g.json 2>/dev/null
+  python bench.py --full --batch 4096 --points 2048 --decoder-chunk 2048 --steps 5 --warmup 2 --no-cpu-baseline --no-workloads --no-parity --gemm bf16 > $O/b4096n2048_bf16.json 2>/dev/null
   for f in bench_split16 bench_bf16 b32 b32g b4096n2048_bf16; do echo $f; cut -c90-300 $O/$f.json; done
   ;;
 B)
