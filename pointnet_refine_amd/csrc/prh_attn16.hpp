@@ -8,7 +8,8 @@
 //           a power-of-two scale taken from ITS OWN largest magnitude (wave-wide max: gradients of
 //           1e-6 keep their 22 bits) and each product is unscaled exactly; probabilities (<= 1)
 //           are split as they are;
-//   PREC 1: one bf16 plane, one product (bf16 mode, BASELINE config 3).
+//   PREC 1: one bf16 plane, one product.  The library launches the attention kernels with PREC 0
+//           only (every GEMM mode but 0); prh_attnfold.hpp uses the PREC 1 helpers.
 // A key tile costs 12 (forward) / 42 (backward) MFMAs of 32 cycles instead of 32 / 112 of 64:
 // the kernels become bound by what they read and write (K, V once; dK, dV once).
 //

@@ -471,10 +471,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_b16d_kernel(const NTParams p, 
   const int tile_n = vb % p.tiles_n, tile_m = vb / p.tiles_n;
   const int m0 = tile_m * 256, n0 = tile_n * 256;
   const int KT = p.K / B16_BK;
-  if ((p.flags & F_STAGGER) != 0 && blockIdx.x < 256 && (blockIdx.x & 1) != 0) {
-    const int n = __builtin_amdgcn_readfirstlane((KT * 5) >> 3);      // x 4096 cycles: about half a tile
-    for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(64);
-  }
 
   f32x4 acc[8][4];
 #pragma unroll

@@ -139,34 +139,14 @@ struct CoreOverride {
   explicit CoreOverride(int m) : old(t_core_override) { t_core_override = m; }
   ~CoreOverride() { t_core_override = old; }
 };
-// PRH_H2_GEN=1 keeps the split-fp16 NT GEMMs on the first-generation core (32x32x16 MFMA, BK 16)
-bool g_h2_gen2 = [] { const char* e = getenv("PRH_H2_GEN"); return !(e && strcmp(e, "1") == 0); }();
 // PRH_H2_PP=1: phase-split ("ping-pong") k-loop of the second-generation NT core (prh_gemm_h2.hpp)
 bool g_h2_pp = [] { const char* e = getenv("PRH_H2_PP"); return e && strcmp(e, "1") == 0; }();
-// PRH_TN_TR=0 keeps the split-fp16 wgrads on the column-staged core
-int g_tn_skew = [] { const char* e = getenv("PRH_TN_SKEW"); return e ? atoi(e) : 0; }();   // diagnostic
-// PRH_SMALL=0 keeps the launches the small-problem cores (prh_small.hpp) would take on the 128 x 128 fp32 cores
-bool g_small = [] { const char* e = getenv("PRH_SMALL"); return !(e && strcmp(e, "0") == 0); }();
-bool g_tn_pace = [] { const char* e = getenv("PRH_TN_PACE"); return !(e && strcmp(e, "0") == 0); }();
-bool g_tn_tr = [] { const char* e = getenv("PRH_TN_TR"); return !(e && strcmp(e, "0") == 0); }();
-// PRH_POOL_FUSED=0 keeps the dual pooling a separate pass over `fused` (A/B comparison)
-// Attention cores: 16-bit MFMA (two fp16 planes / three products with the fp32-accurate GEMM modes,
-// one bf16 plane in the bf16 modes); PRH_ATTN=fp32 or GEMM mode 0 keep the exact fp32 MFMA kernels
-bool g_attn_fp32 = [] { const char* e = getenv("PRH_ATTN"); return e && strcmp(e, "fp32") == 0; }();
+// Attention cores: 16-bit MFMA (two fp16 planes / three products) in every GEMM mode but 0, the bf16
+// modes included: at B=4096 one bf16 plane saved 12 ms of a 300 ms step and tripled the worst
+// per-tensor gradient error (0.29 against 0.064 vs the exact cores).  GEMM mode 0 keeps the exact
+// fp32 MFMA kernels.  -1: exact fp32 kernels; 0: two fp16 planes
 thread_local bool g_attn_kv16 = false;      // set by the *_kv16 entry points around the shared launch code
-bool g_attn_bf16 = [] { const char* e = getenv("PRH_ATTN"); return e && strcmp(e, "bf16") == 0; }();
-// -1: exact fp32 MFMA kernels (GEMM mode 0, PRH_ATTN=fp32); 0: two fp16 planes, three products - every
-// other mode, the bf16 modes included: at B=4096 one bf16 plane saves 12 ms of a 300 ms step and
-// triples the worst per-tensor gradient error (0.29 against 0.064 vs the exact cores); 1: one bf16
-// plane (PRH_ATTN=bf16, measurement only)
-inline int attn_prec() {
-  if (g_attn_fp32 || gemm_mode() == 0) return -1;
-  return g_attn_bf16 ? 1 : 0;
-}
-bool g_pool_fused = [] { const char* e = getenv("PRH_POOL_FUSED"); return !(e && strcmp(e, "0") == 0); }();
-// PRH_DGRAD_PARTIAL=1: the fusion dgrad skips the ReLU mask / statistics (and the z read) of the four conv blocks a
-// later dgrad completes (NTParams.mask_col0).  Off by default: see DESIGN.md section 7 (L2 sharing of the A tile)
-bool g_dgrad_partial = [] { const char* e = getenv("PRH_DGRAD_PARTIAL"); return e && strcmp(e, "1") == 0; }();
+inline int attn_prec() { return gemm_mode() == 0 ? -1 : 0; }
 inline const char* core_tag() { return core_mode() == 2 ? "b1" : (core_mode() == 3 ? "h2" : "s3"); }
 
 // largest |pro(A)| over [rows, cols] into *slot; part: ABSMAX_MAX_BLOCKS floats of scratch
@@ -236,10 +216,6 @@ static_assert(8 * 32 * EPI_LDW * 4 <= S3_LDS, "epilogue scratch must fit in the 
 // ------------------------------------------------------------------ bf16 mode launchers (prh_b16.hpp)
 // C[M,N] = pro(A) W^T on the bf16 NT core.  A bf16 (A16) or fp32, C / C2 / matrix E1 bf16 (C16)
 // or fp32.  p.wprep must hold b16_weight_bytes(N, K).  Leading dimensions in elements.
-// PRH_STAGGER=1: half of the first generation of workgroups of a large NT launch starts half a tile late
-bool g_stagger = [] { const char* e = getenv("PRH_STAGGER"); return e && strcmp(e, "1") == 0; }();
-// PRH_B16_DMA=0: plain-operand bf16 NT GEMMs stay on the register-staged core (A/B comparison)
-bool g_b16_dma = [] { const char* e = getenv("PRH_B16_DMA"); return !(e && strcmp(e, "0") == 0); }();
 template <int PRO, int EPI, bool A16, bool C16>
 int launch_nt_b16(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {
   if (p.M <= 0 || p.N <= 0) return PRH_OK;
@@ -267,10 +243,9 @@ int launch_nt_b16(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {
   ProfScope ps(nm, 2.0 * p.M * (double)p.N * p.K, by, st);
   if constexpr (PRO == PRO_NONE && A16) {
     // plain bf16 operand: both operands by LDS-DMA, phase-split loop (gemm_nt_b16d_kernel)
-    if (g_b16_dma && (p.K % B16_BK) == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0) {
+    if ((p.K % B16_BK) == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0) {
       static const int attr_d = allow_big_lds(gemm_nt_b16d_kernel<EPI, C16>);
       if (attr_d != PRH_OK) return attr_d;
-      if (g_stagger && (long)NTl * cdiv(p.M, 256) >= 1024) p.flags |= F_STAGGER;
       hipLaunchKernelGGL((gemm_nt_b16d_kernel<EPI, C16>), dim3((unsigned)(NTl * cdiv(p.M, 256))), dim3(512), (size_t)B16D_LDS, st,
                          p, (const char*)(p.wprep + S3_WHDR));
       LAUNCH_CHECK();
@@ -284,9 +259,8 @@ int launch_nt_b16(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {
   if (si) { si->count = 2 * cdiv(p.M, 256); si->rows = 128; }
   return PRH_OK;
 }
-int g_b16_min_rows = [] { const char* e = getenv("PRH_B16_MIN_ROWS"); return e ? atoi(e) : 512; }();   // diagnostic
 inline bool nt_b16_generic_ok(const NTParams& p) {      // fp32-storage Linear served by the bf16 core in mode 4
-  return p.M >= g_b16_min_rows && p.wprep != nullptr && (p.K & 7) == 0 && p.K >= 64 && p.K <= 8192 && (p.lda & 3) == 0 && (p.N & 3) == 0 &&
+  return p.wprep != nullptr && (p.K & 7) == 0 && p.K >= 64 && p.K <= 8192 && (p.lda & 3) == 0 && (p.N & 3) == 0 &&
          (p.ldc & 3) == 0 && (p.E1 == nullptr || (p.lde1 & 3) == 0) && p.M >= 512 && p.N >= 64 &&
          (long)cdiv(p.M, 256) * cdiv(p.N, 256) >= 16;
 }
@@ -333,8 +307,8 @@ int launch_tn_b16(TNParams& p, float* slab, float* colsum_slab, float* C, long l
   p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.splits = pl.splits; p.rows_per_split = pl.rows_per_split;
   p.slab = slab;
   p.colsum = colsum_out != nullptr ? colsum_slab : nullptr;
-  p.pace = nullptr; p.skew = 0;
-  if (g_tn_pace && pl.tiles_m * pl.tiles_n >= 8 && pl.splits <= ABSMAX_MAX_BLOCKS && pl.rows_per_split >= 16384) {
+  p.pace = nullptr;
+  if (pl.tiles_m * pl.tiles_n >= 8 && pl.splits <= ABSMAX_MAX_BLOCKS && pl.rows_per_split >= 16384) {
     p.pace = reinterpret_cast<int*>(slab + (size_t)pl.splits * p.Mo * p.Ni + 64);
     if (hipMemsetAsync(p.pace, 0, sizeof(int) * pl.splits, st) != hipSuccess)
       return fail(PRH_ERR_HIP, "gemm_tn_b16: memset of the pacing counters failed");
@@ -374,7 +348,7 @@ int launch_tn_b16(TNParams& p, float* slab, float* colsum_slab, float* C, long l
 inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 // launches the 128 x 128 tiling would turn into less than ~3/4 of a round of workgroups
 inline bool small_nt_ok(const NTParams& p, bool nn) {
-  if (!g_small || p.M < 1 || (p.K % SM_BK) != 0 || (p.lda & 3) || (p.ldw & 3) || !al16(p.A) || !al16(p.W)) return false;
+  if (p.M < 1 || (p.K % SM_BK) != 0 || (p.lda & 3) || (p.ldw & 3) || !al16(p.A) || !al16(p.W)) return false;
   if ((long)cdiv(p.M, BM) * cdiv(p.N, BN) >= 192) return false;
   if (nn && (p.N & 31)) return false;
   return true;
@@ -404,7 +378,7 @@ int launch_small(NTParams& p, hipStream_t st) {
 // wgrad: 64 x 64 tiles, rows split in multiples of 64 until ~2 rounds of workgroups exist
 constexpr int TN_SMALL_MAX_P = 16384;
 inline bool small_tn_dims_ok(int P, int Mo, int Ni) {
-  return g_small && P >= 64 && P <= TN_SMALL_MAX_P && (P & 63) == 0 && (Mo & 63) == 0 && (Ni & 63) == 0;
+  return P >= 64 && P <= TN_SMALL_MAX_P && (P & 63) == 0 && (Mo & 63) == 0 && (Ni & 63) == 0;
 }
 inline void small_tn_plan(int P, int Mo, int Ni, int& splits, int& rps) {
   const int tiles = (Mo / 64) * (Ni / 64), chunks = P / 64;
@@ -459,7 +433,7 @@ int launch_nt(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   // p.amax
                             (p.flags & F_E1_ROWVEC) == 0 && (p.C2 == nullptr || ((int)p.ldc2 & 3) == 0);
         const int KT2 = cdiv(p.K, H2_BK);
         const size_t lds = (size_t)H2_LDS + (PRO == PRO_NONE ? 0 : 2 * (size_t)(KT2 + 2) * H2_BK * 4);
-        if (mode == 3 && g_h2_gen2 && vec_ok && lds <= 160 * 1024) {
+        if (mode == 3 && vec_ok && lds <= 160 * 1024) {
           const long th2 = (long)NTl * 256 * KT2 * 4;
           hipLaunchKernelGGL(prep_weights_h2_kernel, dim3((unsigned)cdiv(th2, 256)), dim3(256), 0, st, p.W,
                              p.N, p.K, p.ldw, p.wprep + S3_WHDR, p.amaxW);
@@ -622,12 +596,11 @@ int launch_tn(TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, 
         }
         bool tr = false;
         if constexpr (PROA == PRO_NONE && (PROB == PRO_NONE || PROB == PRO_BNRELU))
-          tr = mode == 3 && g_tn_tr && ((p.Mo | p.Ni | (int)p.lda | (int)p.ldb) & 3) == 0;
+          tr = mode == 3 && ((p.Mo | p.Ni | (int)p.lda | (int)p.ldb) & 3) == 0;
         p.pace = nullptr;
-        p.skew = g_tn_skew > 0 ? (g_tn_skew > 1000 ? 1000 : g_tn_skew) : 0;
         // (only where many tiles share long splits: with 6 tiles per split the waits cost the
         // attention K/V wgrad 7 % and there is little to share)
-        if (tr && g_tn_pace && pl.tiles_m * pl.tiles_n >= 8 && pl.splits <= ABSMAX_MAX_BLOCKS &&
+        if (tr && pl.tiles_m * pl.tiles_n >= 8 && pl.splits <= ABSMAX_MAX_BLOCKS &&
             pl.rows_per_split >= 16384) {
           // progress counters live where the (already consumed) per-block maxima were
           p.pace = reinterpret_cast<int*>(slab + (size_t)pl.splits * p.Mo * p.Ni + 64);
@@ -658,7 +631,7 @@ int launch_tn(TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, 
     }
     if constexpr (PROA == PRO_NONE && PROB == PRO_NONE) {
       // short row ranges: one launch, no slab (prh_small.hpp, gemm_tn_direct_kernel)
-      if (!done && g_small && C != nullptr && p.P >= 64 && p.P <= 4096 && (p.P & 63) == 0 && (p.Mo & 31) == 0 &&
+      if (!done && C != nullptr && p.P >= 64 && p.P <= 4096 && (p.P & 63) == 0 && (p.Mo & 31) == 0 &&
           (p.Ni & 31) == 0 && (p.lda & 3) == 0 && (p.ldb & 3) == 0 && al16(p.A) && al16(p.B)) {
         p.tiles_m = p.Mo / 32; p.tiles_n = p.Ni / 32; p.splits = 1; p.rows_per_split = p.P;
         snprintf(nm, sizeof(nm), "gemm_tn_direct Mo=%d Ni=%d", p.Mo, p.Ni);
@@ -1346,7 +1319,7 @@ int prh_linear_backward_full(const float* x, long ldx, const float* w, const flo
   float *wT = lw.wT, *slab = lw.slab, *cslab = lw.cslab;
   const float* dy_amax = dy_amax_in;
   bool dx_done = false;
-  const bool big16 = gemm_mode() == 4 && rows >= g_b16_min_rows && (long)cdiv(rows, 256) * cdiv(k, 256) >= 16;
+  const bool big16 = gemm_mode() == 4 && rows >= 512 && (long)cdiv(rows, 256) * cdiv(k, 256) >= 16;
   if (dx != nullptr && !big16) {      // small problem: dgrad with the weight as stored (no transposed copy)
     NTParams p; memset(&p, 0, sizeof(p));
     p.A = dy; p.lda = n; p.W = w; p.ldw = k; p.C = dx; p.ldc = k; p.M = rows; p.N = k; p.K = n;
@@ -1547,7 +1520,7 @@ int prh_encoder_forward(const prh_encoder_params* prm, const float* ctx, int B, 
     p.flags = sv->gate ? F_STORE_GATE : 0;
     // dual pooling (src/model.py:58-60) on the epilogue that writes `fused`, when a segment is a
     // whole number of 128-row wave tiles and the vector epilogue serves the launch
-    const bool fuse_pool = gfeat != nullptr && (N % 128) == 0 && g_pool_fused && gemm_mode() == 3 && g_h2_gen2 &&
+    const bool fuse_pool = gfeat != nullptr && (N % 128) == 0 && gemm_mode() == 3 &&
                            nt_use_s3(P, od, 64) && (od & 3) == 0;
     if (fuse_pool) { p.flags |= F_POOL; p.ws_a = w.ws_a; p.ws_b = w.ws_b; p.ws_c = w.ws_c; }
     TRY((launch_nt<PRO_GATE1, EPI_GATE>(p, st)));
@@ -1645,9 +1618,6 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
     // layers 1..4 are recomputed by the dgrad that completes them
     p.ws_a = w.ws_a; p.ws_b = w.ws_b;
     p.flags = F_MASK | F_STATS;
-    // blocks 1..4 are partial here and are masked (and measured) by the conv dgrad that completes them:
-    // the epilogue reads z and takes sums for layer 5's block only (vector epilogue; 64-column granularity)
-    if (g_dgrad_partial && (d.off[4] & 63) == 0) p.mask_col0 = d.off[4];
     if (matf) TRY((launch_nt<PRO_NONE, EPI_DGRAD>(p, st, &si5)));
     else TRY((launch_nt<PRO_BNBWD, EPI_DGRAD>(p, st, &si5)));
     si5.ld = cat; si5.off = d.off[4];
@@ -1772,7 +1742,7 @@ int prh_encoder_forward_bf16(const prh_encoder_params* prm, const float* ctx, in
     p.C = f16p(fused); p.ldc = od; p.C2 = f16p(sv->gate); p.ldc2 = od;
     p.wprep = w.wprep;
     p.flags = sv->gate ? F_STORE_GATE : 0;
-    const bool fuse_pool = gfeat != nullptr && (N % 128) == 0 && g_pool_fused;
+    const bool fuse_pool = gfeat != nullptr && (N % 128) == 0;
     if (fuse_pool) { p.flags |= F_POOL; p.ws_a = w.ws_a; p.ws_b = w.ws_b; p.ws_c = w.ws_c; }
     TRY((launch_nt_b16<PRO_GATE1, EPI_GATE, true, true>(p, st)));
     if (fuse_pool) {
@@ -1846,7 +1816,6 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
     p.C = f16p(w.dy_cat); p.ldc = cat; p.E1 = f16p(z_cat); p.lde1 = cat; p.es = sv->bn_scale; p.et = sv->bn_shift;
     p.wprep = w.wprep; p.ws_a = w.ws_a; p.ws_b = w.ws_b;
     p.flags = F_MASK | F_STATS;
-    if (g_dgrad_partial && (d.off[4] & 63) == 0) p.mask_col0 = d.off[4];      // see prh_encoder_backward: blocks 1..4 are masked later
     TRY((launch_nt_b16<PRO_NONE, EPI_DGRAD, true, true>(p, st, &si)));
     si.ld = cat; si.off = d.off[4];
   }
@@ -2287,13 +2256,11 @@ int prh_context_build(const float* cloud, int npts, const float* dense, int n_de
 }
 
 // ------------------------------------------------------------------ fused cross-attention
-// PRH_ATTN_KSPLIT=0: never split the keys of a head over the waves of a workgroup (A/B comparison)
-bool g_attn_ksplit = [] { const char* e = getenv("PRH_ATTN_KSPLIT"); return !(e && strcmp(e, "0") == 0); }();
 // small batches (B x H heads would occupy a fraction of the chip's wave slots) with long key
 // ranges: up to eight waves per head, each a multiple of 32 keys
 static bool attn_ksplit(int B, int H, int N, int& keys_per_wave) {
   keys_per_wave = 0;
-  if (!g_attn_ksplit || (long)B * H > 1024 || N < 128) return false;
+  if ((long)B * H > 1024 || N < 128) return false;
   int nw = cdiv(N, 32) < 8 ? cdiv(N, 32) : 8;
   keys_per_wave = cdiv(cdiv(N, 32), nw) * 32;
   return true;
@@ -2318,23 +2285,18 @@ int prh_attn_forward(const float* q, long ldq, const float* k, long ldk, const f
   TRY(check_attn(a));
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  const int prec_ = attn_prec();
-  ProfScope ps(prec_ < 0 ? "attn_fwd" : (prec_ == 0 ? "attn16_fwd<split>" : "attn16_fwd<bf16>"),
+  const int prec = attn_prec();
+  ProfScope ps(prec < 0 ? "attn_fwd" : "attn16_fwd<split>",
                4.0 * B * H * (double)M * N * 32, 4.0 * (2.0 * B * N * H * 32 + 2.0 * B * M * H * 32), st);
   int wpb = (long)B * (H / 4) < 512 ? 1 : 4;      // one head per workgroup while the grid would not fill the chip
-  const int prec = attn_prec();
   if (g_attn_kv16 && prec < 0) return fail(PRH_ERR_ARG, "attention: bf16 K/V need the 16-bit attention cores");
   unsigned grid = (unsigned)(B * (H / wpb));
   if (prec >= 0 && attn_ksplit(B, H, N, a.ksplit)) { wpb = cdiv(N, a.ksplit); grid = (unsigned)(B * H); }
-  const size_t ldsf = (size_t)wpb * (prec == 0 ? a16_fwd_wave_lds<0>() : a16_fwd_wave_lds<1>());
-  if (prec == 0 && g_attn_kv16)
+  const size_t ldsf = (size_t)wpb * a16_fwd_wave_lds<0>();
+  if (prec >= 0 && g_attn_kv16)
     hipLaunchKernelGGL((attn16_fwd_kernel<0, true>), dim3(grid), dim3(64 * wpb), ldsf, st, a);
-  else if (prec == 1 && g_attn_kv16)
-    hipLaunchKernelGGL((attn16_fwd_kernel<1, true>), dim3(grid), dim3(64 * wpb), ldsf, st, a);
-  else if (prec == 0)
+  else if (prec >= 0)
     hipLaunchKernelGGL(attn16_fwd_kernel<0>, dim3(grid), dim3(64 * wpb), ldsf, st, a);
-  else if (prec == 1)
-    hipLaunchKernelGGL(attn16_fwd_kernel<1>, dim3(grid), dim3(64 * wpb), ldsf, st, a);
   else
     hipLaunchKernelGGL(attn_fwd_kernel, dim3(grid), dim3(64 * wpb), 0, st, a);
   LAUNCH_CHECK();
@@ -2365,52 +2327,33 @@ int prh_attn_backward_ex(const float* q, long ldq, const float* k, long ldk, con
   if (prec >= 0) {
     unsigned grid = (unsigned)(B * (H / wpb));
     if (attn_ksplit(B, H, N, a.ksplit)) { wpb = cdiv(N, a.ksplit); grid = (unsigned)(B * H); }
-    const size_t lds16 = (size_t)wpb * (4 * (prec == 0 ? 2 : 1) * A16_IMG + (prec == 0 ? 0 : AT_TILE * 4));
+    const size_t lds16 = (size_t)wpb * 4 * 2 * A16_IMG;
     static const int attr16 = [] {
       return (hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-              hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<1>),
+              hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0, true>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) ? 0 : 1;
     }();
     if (attr16) return fail(PRH_ERR_HIP, "attention_backward: cannot raise the dynamic LDS limit");
-    static const int attr16k = [] {
-      return (hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-              hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<1, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) ? 0 : 1;
-    }();
-    if (attr16k) return fail(PRH_ERR_HIP, "attention_backward: cannot raise the dynamic LDS limit");
     const double kvb = g_attn_kv16 ? 2.0 : 4.0;
-    ProfScope ps(prec == 0 ? "attn16_bwd<split>" : "attn16_bwd<bf16>", 14.0 * B * H * (double)M * N * 32,
+    ProfScope ps("attn16_bwd<split>", 14.0 * B * H * (double)M * N * 32,
                  kvb * 4.0 * B * N * H * 32 + 4.0 * 4.0 * B * M * H * 32, st);
     if (a.ksplit > 0) {
       static const int attr16s = [] {
         return (hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0, false, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<1, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
                 hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<1, true, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) ? 0 : 1;
       }();
       if (attr16s) return fail(PRH_ERR_HIP, "attention_backward: cannot raise the dynamic LDS limit");
-      if (prec == 0 && g_attn_kv16)
+      if (g_attn_kv16)
         hipLaunchKernelGGL((attn16_bwd_kernel<0, true, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
-      else if (g_attn_kv16)
-        hipLaunchKernelGGL((attn16_bwd_kernel<1, true, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
-      else if (prec == 0)
-        hipLaunchKernelGGL((attn16_bwd_kernel<0, false, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
       else
-        hipLaunchKernelGGL((attn16_bwd_kernel<1, false, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
-    } else if (prec == 0 && g_attn_kv16)
+        hipLaunchKernelGGL((attn16_bwd_kernel<0, false, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
+    } else if (g_attn_kv16)
       hipLaunchKernelGGL((attn16_bwd_kernel<0, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
-    else if (g_attn_kv16)
-      hipLaunchKernelGGL((attn16_bwd_kernel<1, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
-    else if (prec == 0)
-      hipLaunchKernelGGL(attn16_bwd_kernel<0>, dim3(grid), dim3(64 * wpb), lds16, st, a);
     else
-      hipLaunchKernelGGL(attn16_bwd_kernel<1>, dim3(grid), dim3(64 * wpb), lds16, st, a);
+      hipLaunchKernelGGL(attn16_bwd_kernel<0>, dim3(grid), dim3(64 * wpb), lds16, st, a);
     LAUNCH_CHECK();
     return PRH_OK;
   }

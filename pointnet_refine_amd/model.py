@@ -26,8 +26,6 @@ heads that are not 32 wide, a d_model other than 256 in the LayerNorm pass) rais
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -291,7 +289,7 @@ class LineRefineNet(nn.Module):
         GEMM mode (io.refine_scene(precision="fp16"), bench --gemm bf16), reference widths."""
         return (self.fold_kv_inference and not self.training and not torch.is_grad_enabled() and memory.is_cuda
                 and ops.bf16_mode() and self.d_model == 256 and noisy_line.shape[1] <= 32
-                and self.decoder_layers[0].cross_attn.num_heads == 8 and os.environ.get("PRH_ATTN_FOLD") != "0")
+                and self.decoder_layers[0].cross_attn.num_heads == 8)
 
     def decode(self, context, noisy_line, memory, tgt):
         """Iterative refinement (src/model.py:197-234) given memory (B,N,256) and the initial

@@ -81,3 +81,20 @@ def test_product_never_imports_oracle():
             if f.endswith((".py", ".hip", ".hpp", ".h")):
                 txt = open(os.path.join(dp, f)).read()
                 assert "import oracle" not in txt and "from oracle" not in txt, f
+
+
+def test_environment_switches_match_integration_table():
+    """Every PRH_* variable the library (getenv in csrc/) or the package (os.environ) reads has a row in
+    INTEGRATION.md section 6, and every PRH_* row there is read somewhere."""
+    pkg = os.path.join(ROOT, "pointnet_refine_amd")
+    read = set()
+    for f in os.listdir(os.path.join(pkg, "csrc")):
+        read |= set(re.findall(r'getenv\(\s*"(PRH_\w+)"', open(os.path.join(pkg, "csrc", f)).read()))
+    for f in os.listdir(pkg):
+        if f.endswith(".py"):
+            txt = open(os.path.join(pkg, f)).read()
+            read |= set(re.findall(r'os\.(?:environ\.get\(|environ\[|getenv\()\s*"(PRH_\w+)"', txt))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = re.search(r"^## 6\..*?(?=^## |\Z)", doc, flags=re.S | re.M).group(0)
+    listed = set(re.findall(r"^\| `(PRH_\w+)", sec, flags=re.M))
+    assert read == listed, f"read but not listed: {sorted(read - listed)}; listed but not read: {sorted(listed - read)}"
