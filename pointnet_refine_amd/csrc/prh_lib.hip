@@ -110,7 +110,8 @@ struct Arena {
 // bf16 cores (6 products, no range assumption); small / odd-shaped GEMMs stay on the fp32 cores.
 // -1: not initialised, 0: fp32 cores only, 1: split-bf16 (3 planes, 6 products, fp32-accurate)
 // for large GEMMs, 2: plain bf16 operands (1 plane) for large GEMMs - reduced precision,
-// opt-in only, 3: split-fp16 (2 scaled planes, 3 products, fp32-accurate) for large GEMMs
+// opt-in only, 3: split-fp16 (2 scaled planes, 3 products, fp32-accurate) for large GEMMs,
+// 4: bf16 operands and storage.  An exported entry point reads the mode once and passes Cores down.
 const unsigned* g_seed_src = nullptr;   // device word mixed into every dropout seed (prh_set_dropout_seed_source)
 int g_gemm_mode = -1;
 inline int gemm_mode() {
@@ -127,27 +128,27 @@ inline int gemm_mode() {
   }
   return g_gemm_mode;
 }
-// Mode 4 (bf16 operands AND bf16 activation storage, prh_b16.hpp) has its own encoder / Linear
-// entry points; whatever still goes through the generic fp32-storage launchers in that mode
-// (point_mlp stack, odd shapes) is served like mode 2: one bf16 plane on the first-generation cores.
-// (the point_mlp stack - 3-wide line coordinates in metres, B*32 rows - is the exception: in mode 4 it
-// runs on the fp32-accurate split-fp16 cores, see CoreOverride)
-thread_local int t_core_override = -1;
-inline int core_mode() { return t_core_override >= 0 ? t_core_override : (gemm_mode() == 4 ? 2 : gemm_mode()); }
-struct CoreOverride {
-  int old;
-  explicit CoreOverride(int m) : old(t_core_override) { t_core_override = m; }
-  ~CoreOverride() { t_core_override = old; }
+// What one call runs on.  core: the family of the generic fp32-storage launchers (launch_nt /
+// launch_tn), 0 fp32, 1 three bf16 planes, 2 one bf16 plane, 3 split-fp16.  Mode 4 has its own
+// encoder / Linear entry points; odd shapes that still reach the generic launchers are served like
+// mode 2, the point_mlp stack like mode 3 (stack_cores).
+struct Cores {
+  int mode, core;
+  bool split() const { return core != 0; }      // large GEMMs may leave the fp32 cores
+  // Attention cores: 16-bit MFMA (two fp16 planes / three products) in every GEMM mode but 0, the bf16
+  // modes included: at B=4096 one bf16 plane saved 12 ms of a 300 ms step and tripled the worst
+  // per-tensor gradient error (0.29 against 0.064 vs the exact cores).  GEMM mode 0 keeps the exact
+  // fp32 MFMA kernels.  -1: exact fp32 kernels; 0: two fp16 planes
+  int attn_prec() const { return mode == 0 ? -1 : 0; }
+  const char* tag() const { return core == 2 ? "b1" : (core == 3 ? "h2" : "s3"); }
 };
+inline Cores cores_of(int mode) { return Cores{mode, mode == 4 ? 2 : mode}; }
+// the point_mlp stack, i.e. the line encoder (Conv1d(3,64) on coordinates of +-25 m, src/model.py:150-152):
+// in mode 4 it keeps fp32-accurate operands on the split-fp16 cores - 131 k rows at B=4096, nothing
+// to gain from 8-bit mantissas
+inline Cores stack_cores(int mode) { return mode == 4 ? Cores{4, 3} : cores_of(mode); }
 // PRH_H2_PP=1: phase-split ("ping-pong") k-loop of the second-generation NT core (prh_gemm_h2.hpp)
 bool g_h2_pp = [] { const char* e = getenv("PRH_H2_PP"); return e && strcmp(e, "1") == 0; }();
-// Attention cores: 16-bit MFMA (two fp16 planes / three products) in every GEMM mode but 0, the bf16
-// modes included: at B=4096 one bf16 plane saved 12 ms of a 300 ms step and tripled the worst
-// per-tensor gradient error (0.29 against 0.064 vs the exact cores).  GEMM mode 0 keeps the exact
-// fp32 MFMA kernels.  -1: exact fp32 kernels; 0: two fp16 planes
-thread_local bool g_attn_kv16 = false;      // set by the *_kv16 entry points around the shared launch code
-inline int attn_prec() { return gemm_mode() == 0 ? -1 : 0; }
-inline const char* core_tag() { return core_mode() == 2 ? "b1" : (core_mode() == 3 ? "h2" : "s3"); }
 
 // largest |pro(A)| over [rows, cols] into *slot; part: ABSMAX_MAX_BLOCKS floats of scratch
 template <int PRO>
@@ -170,14 +171,13 @@ int measure_absmax(const float* A, long lda, const float* A2, long lda2, const f
   LAUNCH_CHECK();
   return PRH_OK;
 }
-inline bool split_enabled() { return gemm_mode() != 0; }
-inline bool nt_use_s3(int M, int N, int K) {
+inline bool nt_use_s3(Cores c, int M, int N, int K) {
   // K cap: coefficient LDS image.  Grid floor: a 256x256-tile grid of a few workgroups is
   // latency-bound (53 us for 4 workgroups measured); small GEMMs go to the 128x128 fp32 core.
-  return split_enabled() && K >= 64 && K <= 4096 && N >= 128 && M >= 512 &&
+  return c.split() && K >= 64 && K <= 4096 && N >= 128 && M >= 512 &&
          (long)cdiv(M, S3_BM) * cdiv(N, S3_BN) >= 32;
 }
-inline bool tn_use_s3(int P, int Mo, int Ni) { return split_enabled() && Mo >= 128 && Ni >= 64 && P >= 8192; }
+inline bool tn_use_s3(Cores c, int P, int Mo, int Ni) { return c.split() && Mo >= 128 && Ni >= 64 && P >= 8192; }
 
 // dy <- dz in place (split-fp16 mode), largest |dz| into hdr[0]; hdr: S3_HDR_FLOATS floats
 int materialize_dz(float* dy, long lddy, const float* z, long ldz, const float* ka, const float* kb,
@@ -192,24 +192,35 @@ int materialize_dz(float* dy, long lddy, const float* z, long ldz, const float* 
   return PRH_OK;
 }
 // dz is materialised when the layer is aligned for 16-B accesses and the split-fp16 cores are on
-inline bool dz_in_place(int cols, long lddy, long ldz) {
-  return core_mode() == 3 && (cols & 3) == 0 && (lddy & 3) == 0 && (ldz & 3) == 0;
+inline bool dz_in_place(Cores c, int cols, long lddy, long ldz) {
+  return c.core == 3 && (cols & 3) == 0 && (lddy & 3) == 0 && (ldz & 3) == 0;
 }
 
 // Statistics partials: `count` tiles of `rows` rows each
 struct StatInfo { int count = 0; int rows = 64; long ld = 0; long off = 0; };   // ld 0: = layer width
 inline int stat_tiles_max(int P) { return 2 * cdiv(P, BM); }   // largest count any producer writes
 
-template <typename K>
-int allow_big_lds(K kernel) {
+template <typename K, typename... More>
+int allow_big_lds(K kernel, More... more) {
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  return PRH_OK;
+  if constexpr (sizeof...(more) > 0) return allow_big_lds(more...);
+  else return PRH_OK;
 }
 // dynamic LDS of the NT split core: two stages + the prologue coefficient vectors
 inline size_t nt_s3_lds(int K, int pro) {
   const int KP = (cdiv(K, S3_BK) + 2) * S3_BK;
   return (size_t)S3_LDS + (pro == PRO_NONE ? 0 : (pro == PRO_BNBWD ? 3 : 2) * (size_t)KP * 4);
+}
+// the split cores' launch sites; launch_nt / launch_tn pick the plane count from Cores::core:
+// one bf16 plane (2), two fp16 planes (3), three bf16 planes (1)
+template <int PRO, int EPI, int PLANES>
+void launch_nt_s3(const NTParams& p, long tiles, const char* img, hipStream_t st) {
+  hipLaunchKernelGGL((gemm_nt_s3_kernel<PRO, EPI, PLANES>), dim3((unsigned)tiles), dim3(512), nt_s3_lds(p.K, PRO), st, p, img);
+}
+template <int PROA, int PROB, int PLANES>
+void launch_tn_s3(const TNParams& p, long blocks, hipStream_t st) {
+  hipLaunchKernelGGL((gemm_tn_s3_kernel<PROA, PROB, PLANES>), dim3((unsigned)blocks), dim3(512), S3_LDS, st, p);
 }
 static_assert(8 * 32 * EPI_LDW * 4 <= S3_LDS, "epilogue scratch must fit in the stage buffers");
 
@@ -390,14 +401,14 @@ inline void small_tn_plan(int P, int Mo, int Ni, int& splits, int& rps) {
 
 // ------------------------------------------------------------------ launch helpers
 template <int PRO, int EPI>
-int launch_nt(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   // p.amaxA is filled in when measured
+int launch_nt(Cores c, NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   // p.amaxA is filled in when measured
   if (p.M <= 0 || p.N <= 0) return PRH_OK;
   if ((p.K & 3) || (PRO != PRO_GATE1 && (p.lda & 3)) || (p.ldw & 3) ||
       (PRO == PRO_BNBWD && (p.lda2 & 3)))
     return fail(PRH_ERR_ARG, "gemm_nt: K/lda/ldw must be multiples of 4 (K=%d lda=%ld ldw=%ld)",
                 p.K, p.lda, p.ldw);
-  if constexpr (PRO == PRO_NONE && EPI == EPI_BIAS) {
-    if (gemm_mode() == 4 && t_core_override < 0 && nt_b16_generic_ok(p)) return launch_nt_b16<PRO_NONE, EPI_BIAS, false, false>(p, st, si);
+  if constexpr (PRO == PRO_NONE && EPI == EPI_BIAS) {     // a mode-4 Linear (not the point_mlp stack)
+    if (c.mode == 4 && c.core == 2 && nt_b16_generic_ok(p)) return launch_nt_b16<PRO_NONE, EPI_BIAS, false, false>(p, st, si);
   }
   // F_POOL is honoured by the vector epilogue only: cleared here, set again by the branch that
   // launches a kernel with that epilogue, so the caller can tell whether the partials exist
@@ -409,14 +420,13 @@ int launch_nt(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   // p.amax
                            (double)p.M * p.N * (EPI == EPI_GATE ? 3 : (EPI == EPI_DGRAD ? 2 : 1)) +
                            (double)p.N * p.K);
   {
-    if (p.wprep != nullptr && nt_use_s3(p.M, p.N, p.K) && p.lda <= 65536 && p.lda2 <= 65536 &&
+    if (p.wprep != nullptr && nt_use_s3(c, p.M, p.N, p.K) && p.lda <= 65536 && p.lda2 <= 65536 &&
         !(EPI == EPI_GATE && ((p.N | (int)p.ldc | (int)p.lde1 | (int)p.ldc2) & 3) != 0)) {
       const int KT = cdiv(p.K, S3_BK), NTl = cdiv(p.N, S3_BN);
       const long th = (long)NTl * 256 * KT * 2;
-      const int mode = core_mode();
       float* hdr = reinterpret_cast<float*>(p.wprep);
       const char* img = p.wprep + S3_WHDR;
-      if (mode == 3) {      // operand scales of the fp16-plane core
+      if (c.core == 3) {      // operand scales of the fp16-plane core
         if (p.amaxW == nullptr) {
           TRY_RC((measure_absmax<PRO_NONE>(p.W, p.ldw, nullptr, 0, nullptr, nullptr, nullptr, p.N, p.K, hdr, hdr + 64, st)));
           p.amaxW = hdr;
@@ -433,17 +443,15 @@ int launch_nt(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   // p.amax
                             (p.flags & F_E1_ROWVEC) == 0 && (p.C2 == nullptr || ((int)p.ldc2 & 3) == 0);
         const int KT2 = cdiv(p.K, H2_BK);
         const size_t lds = (size_t)H2_LDS + (PRO == PRO_NONE ? 0 : 2 * (size_t)(KT2 + 2) * H2_BK * 4);
-        if (mode == 3 && vec_ok && lds <= 160 * 1024) {
+        if (c.core == 3 && vec_ok && lds <= 160 * 1024) {
           const long th2 = (long)NTl * 256 * KT2 * 4;
           hipLaunchKernelGGL(prep_weights_h2_kernel, dim3((unsigned)cdiv(th2, 256)), dim3(256), 0, st, p.W,
                              p.N, p.K, p.ldw, p.wprep + S3_WHDR, p.amaxW);
           LAUNCH_CHECK();
           p.tiles_n = NTl;
           if (want_pool) p.flags |= F_POOL;
-          static const int attr_h2 = allow_big_lds(gemm_nt_h2_kernel<PRO, EPI>);
+          static const int attr_h2 = allow_big_lds(gemm_nt_h2_kernel<PRO, EPI>, gemm_nt_h2_kernel<PRO, EPI, true>);
           if (attr_h2 != PRH_OK) return attr_h2;
-          static const int attr_h2p = allow_big_lds(gemm_nt_h2_kernel<PRO, EPI, true>);
-          if (attr_h2p != PRH_OK) return attr_h2p;
           snprintf(nm, sizeof(nm), "gemm_nt_h2<%d,%d> K=%d N=%d", PRO, EPI, p.K, p.N);
           ProfScope ps(nm, 2.0 * p.M * (double)p.N * p.K, by, st);
           if (g_h2_pp)
@@ -458,27 +466,20 @@ int launch_nt(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   // p.amax
         }
       }
       hipLaunchKernelGGL(prep_weights_s3_kernel, dim3((unsigned)cdiv(th, 256)), dim3(256), 0, st,
-                         p.W, p.N, p.K, p.ldw, 0, p.wprep + S3_WHDR, mode == 3 ? p.amaxW : nullptr);
+                         p.W, p.N, p.K, p.ldw, 0, p.wprep + S3_WHDR, c.core == 3 ? p.amaxW : nullptr);
       LAUNCH_CHECK();
       p.tiles_n = NTl;
       const long tiles = (long)NTl * cdiv(p.M, S3_BM);
-      static const int attr_rc = allow_big_lds(gemm_nt_s3_kernel<PRO, EPI, 3>);
-      static const int attr_rc1 = allow_big_lds(gemm_nt_s3_kernel<PRO, EPI, 1>);
-      static const int attr_rc2 = allow_big_lds(gemm_nt_s3_kernel<PRO, EPI, 2>);
+      static const int attr_rc = allow_big_lds(gemm_nt_s3_kernel<PRO, EPI, 3>, gemm_nt_s3_kernel<PRO, EPI, 1>,
+                                               gemm_nt_s3_kernel<PRO, EPI, 2>);
       if (attr_rc != PRH_OK) return attr_rc;
-      if (attr_rc1 != PRH_OK) return attr_rc1;
-      if (attr_rc2 != PRH_OK) return attr_rc2;
-      snprintf(nm, sizeof(nm), "gemm_nt_%s<%d,%d> K=%d N=%d", mode == 3 ? "h2g1" : core_tag(), PRO, EPI, p.K, p.N);
+      snprintf(nm, sizeof(nm), "gemm_nt_%s<%d,%d> K=%d N=%d", c.core == 3 ? "h2g1" : c.tag(), PRO, EPI, p.K, p.N);
       ProfScope ps(nm, 2.0 * p.M * (double)p.N * p.K, by, st);
-      if (mode == 2)
-        hipLaunchKernelGGL((gemm_nt_s3_kernel<PRO, EPI, 1>), dim3((unsigned)tiles), dim3(512),
-                           nt_s3_lds(p.K, PRO), st, p, img);
-      else if (mode == 3)
-        hipLaunchKernelGGL((gemm_nt_s3_kernel<PRO, EPI, 2>), dim3((unsigned)tiles), dim3(512),
-                           nt_s3_lds(p.K, PRO), st, p, img);
-      else
-        hipLaunchKernelGGL((gemm_nt_s3_kernel<PRO, EPI, 3>), dim3((unsigned)tiles), dim3(512),
-                           nt_s3_lds(p.K, PRO), st, p, img);
+      switch (c.core) {
+        case 2: launch_nt_s3<PRO, EPI, 1>(p, tiles, img, st); break;
+        case 3: launch_nt_s3<PRO, EPI, 2>(p, tiles, img, st); break;
+        default: launch_nt_s3<PRO, EPI, 3>(p, tiles, img, st);
+      }
       LAUNCH_CHECK();
       if (si) { si->count = 2 * cdiv(p.M, S3_BM); si->rows = 128; }
       return PRH_OK;
@@ -502,9 +503,9 @@ int launch_nt(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   // p.amax
 
 constexpr int TN_S3_MAX_LD = 4096;   // widest operand row the split TN core accepts
 struct TNPlan { int tiles_m, tiles_n, splits, rows_per_split; bool s3; };
-inline TNPlan tn_plan(int P, int Mo, int Ni, bool allow_s3, long maxld = TN_S3_MAX_LD) {
+inline TNPlan tn_plan(Cores c, int P, int Mo, int Ni, bool allow_s3, long maxld = TN_S3_MAX_LD) {
   TNPlan pl;
-  pl.s3 = allow_s3 && tn_use_s3(P, Mo, Ni);
+  pl.s3 = allow_s3 && tn_use_s3(c, P, Mo, Ni);
   const int tile = pl.s3 ? 256 : 128, bk = pl.s3 ? S3_BK : BK;
   pl.tiles_m = cdiv(Mo, tile);
   pl.tiles_n = cdiv(Ni, tile);
@@ -540,27 +541,27 @@ inline TNPlan tn_plan(int P, int Mo, int Ni, bool allow_s3, long maxld = TN_S3_M
 }
 // floats behind a slab: [0] largest |proA(A)|, [1] largest |proB(B)|, [64..) per-block maxima
 constexpr int TN_HDR = S3_HDR_FLOATS;
-inline size_t tn_splits_bound(int P, int Mo, int Ni) {   // over both cores and any leading dimension
-  const size_t a = (size_t)tn_plan(P, Mo, Ni, true).splits, b = (size_t)tn_plan(P, Mo, Ni, false).splits;
-  size_t c = (size_t)tn_plan(P, Mo, Ni, true, 4).splits;
+inline size_t tn_splits_bound(Cores cores, int P, int Mo, int Ni) {   // over both cores and any leading dimension
+  const size_t a = (size_t)tn_plan(cores, P, Mo, Ni, true).splits, b = (size_t)tn_plan(cores, P, Mo, Ni, false).splits;
+  size_t c = (size_t)tn_plan(cores, P, Mo, Ni, true, 4).splits;
   if (small_tn_dims_ok(P, Mo, Ni)) {
     int ss, rr; small_tn_plan(P, Mo, Ni, ss, rr);
     if ((size_t)ss > c) c = (size_t)ss;
   }
   return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
-inline size_t tn_slab_floats(int P, int Mo, int Ni) { return tn_splits_bound(P, Mo, Ni) * Mo * Ni + TN_HDR; }
-inline size_t tn_colsum_floats(int P, int Mo, int Ni) { return tn_splits_bound(P, Mo, Ni) * Mo; }
+inline size_t tn_slab_floats(Cores c, int P, int Mo, int Ni) { return tn_splits_bound(c, P, Mo, Ni) * Mo * Ni + TN_HDR; }
+inline size_t tn_colsum_floats(Cores c, int P, int Mo, int Ni) { return tn_splits_bound(c, P, Mo, Ni) * Mo; }
 
 // C[Mo,Ni] (ld ldc) = proA(A)^T proB(B); colsum_out[Mo] = column sums of proA(A) (optional)
 template <int PROA, int PROB>
-int launch_tn(TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, float* colsum_out,
+int launch_tn(Cores c, TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, float* colsum_out,
               hipStream_t st) {   // p.amaxA / p.amaxB are filled in when the fp16-plane core measured them
   if (p.Mo <= 0 || p.Ni <= 0) return PRH_OK;
   const bool ld_ok = p.lda <= TN_S3_MAX_LD && p.ldb <= TN_S3_MAX_LD && p.lda2 <= TN_S3_MAX_LD;
   long maxld = p.lda > p.ldb ? p.lda : p.ldb;
   if (PROA == PRO_BNBWD && p.lda2 > maxld) maxld = p.lda2;
-  TNPlan pl = tn_plan(p.P, p.Mo, p.Ni, PROB != PRO_GATE1 && ld_ok, maxld);
+  TNPlan pl = tn_plan(c, p.P, p.Mo, p.Ni, PROB != PRO_GATE1 && ld_ok, maxld);
   if (!pl.s3 && ((p.Mo & 3) || (p.Ni & 3) || (p.lda & 3) || (PROB != PRO_GATE1 && (p.ldb & 3))))
     return fail(PRH_ERR_ARG, "gemm_tn: Mo/Ni/lda/ldb must be multiples of 4 (Mo=%d Ni=%d)", p.Mo,
                 p.Ni);
@@ -576,14 +577,10 @@ int launch_tn(TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, 
     bool done = false;
     if constexpr (PROB != PRO_GATE1) {
       if (pl.s3) {
-        static const int attr_rc = allow_big_lds(gemm_tn_s3_kernel<PROA, PROB, 3>);
-        static const int attr_rc1 = allow_big_lds(gemm_tn_s3_kernel<PROA, PROB, 1>);
-        static const int attr_rc2 = allow_big_lds(gemm_tn_s3_kernel<PROA, PROB, 2>);
+        static const int attr_rc = allow_big_lds(gemm_tn_s3_kernel<PROA, PROB, 3>, gemm_tn_s3_kernel<PROA, PROB, 1>,
+                                                 gemm_tn_s3_kernel<PROA, PROB, 2>);
         if (attr_rc != PRH_OK) return attr_rc;
-        if (attr_rc1 != PRH_OK) return attr_rc1;
-        if (attr_rc2 != PRH_OK) return attr_rc2;
-        const int mode = core_mode();
-        if (mode == 3) {
+        if (c.core == 3) {
           float* hdr = slab + (size_t)pl.splits * p.Mo * p.Ni;
           if (p.amaxA == nullptr) {
             TRY_RC((measure_absmax<PROA>(p.A, p.lda, p.A2, p.lda2, p.pa, p.pb, p.pc, p.P, p.Mo, hdr, hdr + 64, st)));
@@ -596,7 +593,7 @@ int launch_tn(TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, 
         }
         bool tr = false;
         if constexpr (PROA == PRO_NONE && (PROB == PRO_NONE || PROB == PRO_BNRELU))
-          tr = mode == 3 && ((p.Mo | p.Ni | (int)p.lda | (int)p.ldb) & 3) == 0;
+          tr = c.core == 3 && ((p.Mo | p.Ni | (int)p.lda | (int)p.ldb) & 3) == 0;
         p.pace = nullptr;
         // (only where many tiles share long splits: with 6 tiles per split the waits cost the
         // attention K/V wgrad 7 % and there is little to share)
@@ -607,7 +604,7 @@ int launch_tn(TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, 
           if (hipMemsetAsync(p.pace, 0, sizeof(int) * pl.splits, st) != hipSuccess)
             return fail(PRH_ERR_HIP, "gemm_tn: memset of the pacing counters failed");
         }
-        snprintf(nm, sizeof(nm), "gemm_tn_%s<%d,%d> Mo=%d Ni=%d", tr ? "h2tr" : core_tag(), PROA, PROB, p.Mo, p.Ni);
+        snprintf(nm, sizeof(nm), "gemm_tn_%s<%d,%d> Mo=%d Ni=%d", tr ? "h2tr" : c.tag(), PROA, PROB, p.Mo, p.Ni);
         ProfScope ps(nm, 2.0 * p.P * (double)p.Mo * p.Ni, by, st);
         if constexpr (PROA == PRO_NONE && (PROB == PRO_NONE || PROB == PRO_BNRELU)) {
           if (tr) {
@@ -616,16 +613,11 @@ int launch_tn(TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, 
             hipLaunchKernelGGL((gemm_tn_tr_kernel<PROB>), dim3((unsigned)blocks), dim3(512), TR_LDS, st, p);
           }
         }
-        if (tr) {
-        } else if (mode == 2)
-          hipLaunchKernelGGL((gemm_tn_s3_kernel<PROA, PROB, 1>), dim3((unsigned)blocks), dim3(512),
-                             S3_LDS, st, p);
-        else if (mode == 3)
-          hipLaunchKernelGGL((gemm_tn_s3_kernel<PROA, PROB, 2>), dim3((unsigned)blocks), dim3(512),
-                             S3_LDS, st, p);
-        else
-          hipLaunchKernelGGL((gemm_tn_s3_kernel<PROA, PROB, 3>), dim3((unsigned)blocks), dim3(512),
-                             S3_LDS, st, p);
+        if (!tr) switch (c.core) {
+          case 2: launch_tn_s3<PROA, PROB, 1>(p, blocks, st); break;
+          case 3: launch_tn_s3<PROA, PROB, 2>(p, blocks, st); break;
+          default: launch_tn_s3<PROA, PROB, 3>(p, blocks, st);
+        }
         done = true;
       }
     }
@@ -807,13 +799,13 @@ int bn_coeffs(const prh_bn_layer& ly, int P, int training, float momentum, float
 }
 
 // forward of the stack into z_cat (ld = ldz); coefficient vectors indexed by off_l
-int stack_forward(const prh_bn_layer* ly, int L, const float* x, int P, int training,
+int stack_forward(Cores c, const prh_bn_layer* ly, int L, const float* x, int P, int training,
                   float momentum, float eps, float* z_cat, long ldz, float* scale, float* shift,
                   float* mean, float* rstd, StackWS& w, hipStream_t st, float* op_amax = nullptr) {
   // op_amax (training): slot l receives the maximum of layer l's activation relu(BN_l(z_l)),
   // taken from the statistics epilogue - the operand scale of layer l+1's split-fp16 GEMM and,
   // kept by the caller, of the wgrads in backward: no pass over the activations
-  if (!training || gemm_mode() != 3) op_amax = nullptr;
+  if (!training || c.mode != 3) op_amax = nullptr;
   StackDims d = stack_dims(ly, L);
   const float* x0 = x; long ldx = d.cin0; const float* w0 = ly[0].w; int k0 = d.cin0;
   if (d.cin0p != d.cin0) {
@@ -830,13 +822,13 @@ int stack_forward(const prh_bn_layer* ly, int L, const float* x, int P, int trai
     StatInfo si;
     if (l == 0) {
       p.A = x0; p.lda = ldx; p.W = w0; p.ldw = k0; p.K = k0;
-      if (training) TRY((launch_nt<PRO_NONE, EPI_BIAS_STATS>(p, st, &si)));
-      else TRY((launch_nt<PRO_NONE, EPI_BIAS>(p, st)));
+      if (training) TRY((launch_nt<PRO_NONE, EPI_BIAS_STATS>(c, p, st, &si)));
+      else TRY((launch_nt<PRO_NONE, EPI_BIAS>(c, p, st)));
     } else {
       p.A = z_cat + d.off[l - 1]; p.lda = ldz; p.W = ly[l].w; p.ldw = ly[l].cin; p.K = ly[l].cin;
       p.pa = scale + d.off[l - 1]; p.pb = shift + d.off[l - 1];
-      if (training) TRY((launch_nt<PRO_BNRELU, EPI_BIAS_STATS>(p, st, &si)));
-      else TRY((launch_nt<PRO_BNRELU, EPI_BIAS>(p, st)));
+      if (training) TRY((launch_nt<PRO_BNRELU, EPI_BIAS_STATS>(c, p, st, &si)));
+      else TRY((launch_nt<PRO_BNRELU, EPI_BIAS>(c, p, st)));
     }
     TRY(bn_coeffs(ly[l], P, training, momentum, eps, w.ws_a, w.ws_b, w.stat2, si, mean + d.off[l],
                   rstd + d.off[l], scale + d.off[l], shift + d.off[l], st, w.ws_c, w.ws_d, w.apart,
@@ -853,12 +845,12 @@ int stack_forward(const prh_bn_layer* ly, int L, const float* x, int P, int trai
 // Scratch: coef [3*maxc], wT [max cin*cout], slab, colslab.
 struct StackBwdScratch { float* ca; float* cb; float* cc; float* wT; float* slab; float* colslab; float* dxpad; float* hdr; };
 
-int stack_backward(const prh_bn_layer* ly, int L, const float* x, int P, int training,
+int stack_backward(Cores c, const prh_bn_layer* ly, int L, const float* x, int P, int training,
                    float* dy_cat, long lddy, const float* z_cat, long ldz, const float* scale,
                    const float* shift, const float* mean, const float* rstd,
                    const prh_bn_layer_grad* gr, float* dx, StackWS& w, StackBwdScratch& sc,
                    StatInfo si, hipStream_t st, const float* op_amax = nullptr) {
-  if (!training || gemm_mode() != 3) op_amax = nullptr;   // slots as filled by stack_forward
+  if (!training || c.mode != 3) op_amax = nullptr;   // slots as filled by stack_forward
   StackDims d = stack_dims(ly, L);
   const float* x0 = x; long ldx = d.cin0; int k0 = d.cin0;
   if (d.cin0p != d.cin0) { x0 = w.xpad; ldx = d.cin0p; k0 = d.cin0p; }   // xpad filled by caller
@@ -875,7 +867,7 @@ int stack_backward(const prh_bn_layer* ly, int L, const float* x, int P, int tra
                        gr ? gr[l].db : nullptr);
     LAUNCH_CHECK();
     // 1b. split-fp16 mode: dy_l <- dz_l in place, so wgrad and dgrad read one plain operand
-    const bool mat = dz_in_place(co, lddy, ldz);
+    const bool mat = dz_in_place(c, co, lddy, ldz);
     const float* dz_amax = nullptr;     // largest |dz_l| once known
     if (mat) {
       TRY(materialize_dz(dy_cat + o, lddy, z_cat + o, ldz, sc.ca, sc.cb, sc.cc, P, co, sc.hdr, st));
@@ -890,16 +882,16 @@ int stack_backward(const prh_bn_layer* ly, int L, const float* x, int P, int tra
       if (l == 0) {
         t.B = x0; t.ldb = ldx; t.Ni = k0;
         float* out = k0 == d.cin0 ? gr[l].dw : sc.wT;   // padded input: reduce into scratch ...
-        if (mat) TRY((launch_tn<PRO_NONE, PRO_NONE>(t, sc.slab, sc.colslab, out, (long)k0, nullptr, st)));
-        else TRY((launch_tn<PRO_BNBWD, PRO_NONE>(t, sc.slab, sc.colslab, out, (long)k0, nullptr, st)));
+        if (mat) TRY((launch_tn<PRO_NONE, PRO_NONE>(c, t, sc.slab, sc.colslab, out, (long)k0, nullptr, st)));
+        else TRY((launch_tn<PRO_BNBWD, PRO_NONE>(c, t, sc.slab, sc.colslab, out, (long)k0, nullptr, st)));
         if (k0 != d.cin0)                                // ... then drop the pad columns
           TRY(copy_cols(sc.wT, k0, d.cin0, gr[l].dw, d.cin0, d.cin0, (size_t)co, st));
       } else {
         t.B = z_cat + d.off[l - 1]; t.ldb = ldz; t.Ni = ly[l].cin;
         t.qa = scale + d.off[l - 1]; t.qb = shift + d.off[l - 1];
         if (op_amax != nullptr) t.amaxB = op_amax + (l - 1);
-        if (mat) TRY((launch_tn<PRO_NONE, PRO_BNRELU>(t, sc.slab, sc.colslab, gr[l].dw, (long)ly[l].cin, nullptr, st)));
-        else TRY((launch_tn<PRO_BNBWD, PRO_BNRELU>(t, sc.slab, sc.colslab, gr[l].dw, (long)ly[l].cin, nullptr, st)));
+        if (mat) TRY((launch_tn<PRO_NONE, PRO_BNRELU>(c, t, sc.slab, sc.colslab, gr[l].dw, (long)ly[l].cin, nullptr, st)));
+        else TRY((launch_tn<PRO_BNBWD, PRO_BNRELU>(c, t, sc.slab, sc.colslab, gr[l].dw, (long)ly[l].cin, nullptr, st)));
       }
       dz_amax = t.amaxA;
     }
@@ -916,8 +908,8 @@ int stack_backward(const prh_bn_layer* ly, int L, const float* x, int P, int tra
       p.es = scale + d.off[l - 1]; p.et = shift + d.off[l - 1];
       p.ws_a = w.ws_a; p.ws_b = w.ws_b; p.wprep = w.wprep;
       p.flags = F_ACCUM | F_MASK | F_STATS;
-      if (mat) TRY((launch_nt<PRO_NONE, EPI_DGRAD>(p, st, &si)));
-      else TRY((launch_nt<PRO_BNBWD, EPI_DGRAD>(p, st, &si)));
+      if (mat) TRY((launch_nt<PRO_NONE, EPI_DGRAD>(c, p, st, &si)));
+      else TRY((launch_nt<PRO_BNBWD, EPI_DGRAD>(c, p, st, &si)));
       si.ld = 0; si.off = 0;
     } else if (dx != nullptr) {
       // dx = dz_0 W_0  (W_0^T is [cin0p, cout] with zero pad rows)
@@ -931,8 +923,8 @@ int stack_backward(const prh_bn_layer* ly, int L, const float* x, int P, int tra
       p.C = dx; p.ldc = d.cin0;
       p.flags = 0;
       p.amaxA = dz_amax;
-      if (mat) TRY((launch_nt<PRO_NONE, EPI_DGRAD>(p, st)));
-      else TRY((launch_nt<PRO_BNBWD, EPI_DGRAD>(p, st)));
+      if (mat) TRY((launch_nt<PRO_NONE, EPI_DGRAD>(c, p, st)));
+      else TRY((launch_nt<PRO_BNBWD, EPI_DGRAD>(c, p, st)));
     }
   }
   return PRH_OK;
@@ -951,7 +943,7 @@ size_t max_w(const prh_bn_layer* ly, int L) {
   }
   return m;
 }
-void stack_bwd_scratch_carve(Arena& a, StackBwdScratch& sc, int P, const prh_bn_layer* ly, int L,
+void stack_bwd_scratch_carve(Cores c, Arena& a, StackBwdScratch& sc, int P, const prh_bn_layer* ly, int L,
                              size_t extra_w, int extra_c) {
   int mc = max_cout(ly, L); if (extra_c > mc) mc = extra_c;
   size_t mw = max_w(ly, L); if (extra_w > mw) mw = extra_w;
@@ -961,7 +953,7 @@ void stack_bwd_scratch_carve(Arena& a, StackBwdScratch& sc, int P, const prh_bn_
   size_t slab = 0, cs = 0;
   for (int l = 0; l < L; ++l) {
     const int ci = (int)align_up((size_t)ly[l].cin, 4);
-    size_t s1 = tn_slab_floats(P, ly[l].cout, ci), s2 = tn_colsum_floats(P, ly[l].cout, ci);
+    size_t s1 = tn_slab_floats(c, P, ly[l].cout, ci), s2 = tn_colsum_floats(c, P, ly[l].cout, ci);
     slab = s1 > slab ? s1 : slab; cs = s2 > cs ? s2 : cs;
   }
   sc.slab = a.f(slab); sc.colslab = a.f(cs);
@@ -969,26 +961,26 @@ void stack_bwd_scratch_carve(Arena& a, StackBwdScratch& sc, int P, const prh_bn_
 
 // ---- workspace layouts of the entry points (measure with Arena(), carve with Arena(ptr,n))
 struct LinearBwdWS { float* wT; float* slab; float* cslab; char* wprep; };
-void linear_bwd_carve(Arena& a, LinearBwdWS& w, int rows, int k, int n) {
+void linear_bwd_carve(Cores c, Arena& a, LinearBwdWS& w, int rows, int k, int n) {
   w.wprep = (char*)a.f(s3_weight_bytes(k, n) / sizeof(float) + 64);
   w.wT = a.f((size_t)k * n);
-  w.slab = a.f(tn_slab_floats(rows, n, k));
-  w.cslab = a.f(tn_colsum_floats(rows, n, k));
+  w.slab = a.f(tn_slab_floats(c, rows, n, k));
+  w.cslab = a.f(tn_colsum_floats(c, rows, n, k));
 }
 struct MlpWS { StackWS w; StackBwdScratch sc; float* dy_cat; };
-void mlp_carve(Arena& a, MlpWS& m, int P, const prh_bn_layer* ly, int L) {
+void mlp_carve(Cores c, Arena& a, MlpWS& m, int P, const prh_bn_layer* ly, int L) {
   StackDims d = stack_dims(ly, L);
   stack_ws_carve(a, m.w, P, ly, L, max_cout(ly, L));
-  stack_bwd_scratch_carve(a, m.sc, P, ly, L, 0, 0);
+  stack_bwd_scratch_carve(c, a, m.sc, P, ly, L, 0, 0);
   m.dy_cat = a.f((size_t)P * d.off[L]);
 }
 struct EncWS { StackWS w; StackBwdScratch sc; float* fslab; float* fcslab; float* dy_cat; float* dyf; float* dU; float* gsum_a; float* gsum_b; };
-void enc_carve(Arena& a, EncWS& e, int P, const prh_bn_layer* conv, int cat, int od, int backward) {   // 2: no dyf carve
+void enc_carve(Cores c, Arena& a, EncWS& e, int P, const prh_bn_layer* conv, int cat, int od, int backward) {   // 2: no dyf carve
   stack_ws_carve(a, e.w, P, conv, 5, cat > od ? cat : od, od, cat);
   if (!backward) return;
-  stack_bwd_scratch_carve(a, e.sc, P, conv, 5, (size_t)od * cat, cat > od ? cat : od);
-  const size_t fs = tn_slab_floats(P, od, cat), gs = tn_slab_floats(P, od, 64);
-  const size_t fc = tn_colsum_floats(P, od, cat), gc = tn_colsum_floats(P, od, 64);
+  stack_bwd_scratch_carve(c, a, e.sc, P, conv, 5, (size_t)od * cat, cat > od ? cat : od);
+  const size_t fs = tn_slab_floats(c, P, od, cat), gs = tn_slab_floats(c, P, od, 64);
+  const size_t fc = tn_colsum_floats(c, P, od, cat), gc = tn_colsum_floats(c, P, od, 64);
   e.fslab = a.f(fs > gs ? fs : gs);
   e.fcslab = a.f(fc > gc ? fc : gc);
   e.dy_cat = a.f((size_t)P * cat);
@@ -1100,15 +1092,8 @@ size_t prh_linear_forward_workspace_bytes(int rows, int k, int n) {
 int prh_linear_forward_ex(const float* x, long ldx, const float* w, const float* b, float* y,
                           int rows, int k, int n, int relu, const float* x_amax, void* workspace,
                           size_t workspace_bytes, int device, void* stream) {
-  if (!x || !w || !y || rows < 0 || k <= 0 || n <= 0) return fail(PRH_ERR_ARG, "linear_forward: bad argument");
-  HIP_TRY(hipSetDevice(device));
-  NTParams p; memset(&p, 0, sizeof(p));
-  p.A = x; p.lda = ldx; p.W = w; p.ldw = k; p.C = y; p.ldc = n;
-  p.M = rows; p.N = n; p.K = k; p.bias = b; p.flags = relu ? F_RELU_OUT : 0;
-  if (workspace != nullptr && workspace_bytes >= s3_weight_bytes(n, k) + 256)
-    p.wprep = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  p.amaxA = x_amax;
-  return launch_nt<PRO_NONE, EPI_BIAS>(p, (hipStream_t)stream);
+  return prh_linear_forward_full(x, ldx, w, b, nullptr, 0, y, rows, k, n, relu, x_amax, nullptr, 0.f, 0u, workspace,
+                                 workspace_bytes, device, stream);
 }
 int prh_linear_forward_full(const float* x, long ldx, const float* w, const float* b, const float* resid,
                             long ldres, float* y, int rows, int k, int n, int relu, const float* x_amax,
@@ -1131,7 +1116,7 @@ int prh_linear_forward_full(const float* x, long ldx, const float* w, const floa
   if (workspace != nullptr && workspace_bytes >= s3_weight_bytes(n, k) + 256)
     p.wprep = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   p.amaxA = x_amax;
-  return launch_nt<PRO_NONE, EPI_BIAS>(p, (hipStream_t)stream);
+  return launch_nt<PRO_NONE, EPI_BIAS>(cores_of(gemm_mode()), p, (hipStream_t)stream);
 }
 int prh_linear_forward(const float* x, long ldx, const float* w, const float* b, float* y,
                        int rows, int k, int n, int relu, void* workspace, size_t workspace_bytes,
@@ -1175,7 +1160,8 @@ int prh_relu_mask_absmax(const float* dy, const float* y, float* out, long n, fl
 // 1 when a [rows,k] x [n,k]^T Linear GEMM (and its backward GEMMs) run on the split-fp16 cores,
 // i.e. when operand maxima are consumed at all
 int prh_linear_uses_operand_maxima(int rows, int k, int n) {
-  return (gemm_mode() == 3 && (nt_use_s3(rows, n, k) || nt_use_s3(rows, k, n) || tn_use_s3(rows, n, k))) ? 1 : 0;
+  const Cores c = cores_of(gemm_mode());
+  return (c.mode == 3 && (nt_use_s3(c, rows, n, k) || nt_use_s3(c, rows, k, n) || tn_use_s3(c, rows, n, k))) ? 1 : 0;
 }
 
 // ---- positional-encoding MLP, first layer (src/model.py:64-75) -------------------------
@@ -1293,7 +1279,7 @@ int prh_linear_small_backward(const float* x, const float* w, const float* dy, f
 
 size_t prh_linear_backward_workspace_bytes(int rows, int k, int n) {
   Arena a; LinearBwdWS w;
-  linear_bwd_carve(a, w, rows, k, n);
+  linear_bwd_carve(cores_of(gemm_mode()), a, w, rows, k, n);
   return a.off + 256;
 }
 
@@ -1312,18 +1298,19 @@ int prh_linear_backward_full(const float* x, long ldx, const float* w, const flo
   if ((k & 3) || (n & 3)) return fail(PRH_ERR_ARG, "linear_backward: k=%d and n=%d must be multiples of 4", k, n);
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
+  const Cores c = cores_of(gemm_mode());
   Arena a(workspace, workspace_bytes);
   LinearBwdWS lw;
-  linear_bwd_carve(a, lw, rows, k, n);
+  linear_bwd_carve(c, a, lw, rows, k, n);
   if (!a.ok) return fail(PRH_ERR_WORKSPACE, "linear_backward: workspace too small (%zu bytes)", workspace_bytes);
   float *wT = lw.wT, *slab = lw.slab, *cslab = lw.cslab;
   const float* dy_amax = dy_amax_in;
   bool dx_done = false;
-  const bool big16 = gemm_mode() == 4 && rows >= 512 && (long)cdiv(rows, 256) * cdiv(k, 256) >= 16;
+  const bool big16 = c.mode == 4 && rows >= 512 && (long)cdiv(rows, 256) * cdiv(k, 256) >= 16;
   if (dx != nullptr && !big16) {      // small problem: dgrad with the weight as stored (no transposed copy)
     NTParams p; memset(&p, 0, sizeof(p));
     p.A = dy; p.lda = n; p.W = w; p.ldw = k; p.C = dx; p.ldc = k; p.M = rows; p.N = k; p.K = n;
-    if (small_nt_ok(p, true) && !(nt_use_s3(rows, k, n))) {
+    if (small_nt_ok(p, true) && !(nt_use_s3(c, rows, k, n))) {
       TRY((launch_small<true>(p, st)));
       dx_done = true;
     }
@@ -1335,7 +1322,7 @@ int prh_linear_backward_full(const float* x, long ldx, const float* w, const flo
     p.wprep = lw.wprep;
     p.amaxA = dy_amax;
     p.amaxW = w_amax;        // max |W^T| = max |W|
-    TRY((launch_nt<PRO_NONE, EPI_BIAS>(p, st)));
+    TRY((launch_nt<PRO_NONE, EPI_BIAS>(c, p, st)));
     dy_amax = p.amaxA;       // measured once for both GEMMs (lives in the head of lw.wprep)
   }
   if (dw != nullptr || db != nullptr) {
@@ -1343,7 +1330,7 @@ int prh_linear_backward_full(const float* x, long ldx, const float* w, const flo
     t.amaxA = dy_amax;
     t.amaxB = x_amax;
     t.A = dy; t.lda = n; t.B = x; t.ldb = ldx; t.P = rows; t.Mo = n; t.Ni = k;
-    TRY((launch_tn<PRO_NONE, PRO_NONE>(t, slab, cslab, dw, (long)k, db, st)));
+    TRY((launch_tn<PRO_NONE, PRO_NONE>(c, t, slab, cslab, dw, (long)k, db, st)));
   }
   return PRH_OK;
 }
@@ -1358,7 +1345,7 @@ int prh_linear_backward(const float* x, long ldx, const float* w, const float* d
 size_t prh_mlp_stack_workspace_bytes(int P, int n_layers, const prh_bn_layer* layers) {
   if (n_layers < 1 || n_layers > PRH_MAX_LAYERS) return 0;
   Arena a; MlpWS m;
-  mlp_carve(a, m, P, layers, n_layers);
+  mlp_carve(stack_cores(gemm_mode()), a, m, P, layers, n_layers);
   return a.off + 256;
 }
 
@@ -1368,9 +1355,7 @@ int prh_mlp_stack_forward(const prh_bn_layer* layers, int n_layers, int relu_las
                           float* bn_mean, float* bn_rstd, void* workspace,
                           size_t workspace_bytes, int device, void* stream) {
   TRY(check_stack(layers, n_layers));
-  // bf16 mode: the line encoder (Conv1d(3,64) on coordinates of +-25 m, src/model.py:150-152) keeps
-  // fp32-accurate operands - 131 k rows at B=4096, nothing to gain from 8-bit mantissas
-  CoreOverride co_(gemm_mode() == 4 ? 3 : -1);
+  const Cores c = stack_cores(gemm_mode());
   if (!x || !z_cat || !y || !bn_scale || !bn_shift || !bn_mean || !bn_rstd || P <= 0)
     return fail(PRH_ERR_ARG, "mlp_stack_forward: bad argument");
   if (training && P < 2) return fail(PRH_ERR_ARG, "Expected more than 1 value per channel when training");
@@ -1379,11 +1364,11 @@ int prh_mlp_stack_forward(const prh_bn_layer* layers, int n_layers, int relu_las
   StackDims d = stack_dims(layers, n_layers);
   Arena a(workspace, workspace_bytes);
   MlpWS m;
-  mlp_carve(a, m, P, layers, n_layers);
+  mlp_carve(c, a, m, P, layers, n_layers);
   if (!a.ok) return fail(PRH_ERR_WORKSPACE, "mlp_stack_forward: workspace too small (%zu bytes)", workspace_bytes);
   StackWS& w = m.w;
   const long ldz = d.off[n_layers];
-  TRY(stack_forward(layers, n_layers, x, P, training, momentum, eps, z_cat, ldz, bn_scale,
+  TRY(stack_forward(c, layers, n_layers, x, P, training, momentum, eps, z_cat, ldz, bn_scale,
                     bn_shift, bn_mean, bn_rstd, w, st));
   const int L = n_layers, co = layers[L - 1].cout;
   hipLaunchKernelGGL(bn_apply_kernel, dim3(cdiv(P, 64), cdiv(co, 64)), dim3(256), 0, st,
@@ -1400,7 +1385,7 @@ int prh_mlp_stack_backward(const prh_bn_layer* layers, int n_layers, int relu_la
                            const prh_bn_layer_grad* grads, float* dx, void* workspace,
                            size_t workspace_bytes, int device, void* stream) {
   TRY(check_stack(layers, n_layers));
-  CoreOverride co_(gemm_mode() == 4 ? 3 : -1);
+  const Cores c = stack_cores(gemm_mode());
   if (!x || !dy || !z_cat || P <= 0) return fail(PRH_ERR_ARG, "mlp_stack_backward: bad argument");
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
@@ -1408,7 +1393,7 @@ int prh_mlp_stack_backward(const prh_bn_layer* layers, int n_layers, int relu_la
   const int L = n_layers;
   Arena a(workspace, workspace_bytes);
   MlpWS m;
-  mlp_carve(a, m, P, layers, L);
+  mlp_carve(c, a, m, P, layers, L);
   StackWS& w = m.w;
   StackBwdScratch& sc = m.sc;
   const long ldz = d.off[L];
@@ -1425,7 +1410,7 @@ int prh_mlp_stack_backward(const prh_bn_layer* layers, int n_layers, int relu_la
                      dy_cat + o, ldz, w.ws_a, w.ws_b);
   LAUNCH_CHECK();
   StatInfo si; si.count = cdiv(P, 64); si.rows = 64;
-  return stack_backward(layers, L, x, P, training, dy_cat, ldz, z_cat, ldz, bn_scale, bn_shift,
+  return stack_backward(c, layers, L, x, P, training, dy_cat, ldz, z_cat, ldz, bn_scale, bn_shift,
                         bn_mean, bn_rstd, grads, dx, w, sc, si, st);
 }
 
@@ -1443,7 +1428,7 @@ size_t prh_encoder_workspace_bytes(int B, int N, int in_channel, int out_dim, in
   for (int l = 0; l < 5; ++l) { ly[l].cin = ch[l]; ly[l].cout = ch[l + 1]; }
   const int cat = 64 + 128 + 256 + 512 + out_dim;
   Arena a; EncWS e;
-  enc_carve(a, e, P, ly, cat, out_dim, backward);
+  enc_carve(cores_of(gemm_mode()), a, e, P, ly, cat, out_dim, backward);
   return a.off + 256;
 }
 
@@ -1477,17 +1462,18 @@ int prh_encoder_forward(const prh_encoder_params* prm, const float* ctx, int B, 
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   const int cat = enc_cat(prm), od = prm->out_dim, C = prm->in_channel;
+  const Cores c = cores_of(gemm_mode());
   Arena a(workspace, workspace_bytes);
   EncWS ews;
-  enc_carve(a, ews, P, prm->conv, cat, od, 0);
+  enc_carve(c, a, ews, P, prm->conv, cat, od, 0);
   if (!a.ok) return fail(PRH_ERR_WORKSPACE, "encoder_forward: workspace too small (%zu bytes)", workspace_bytes);
   StackWS& w = ews.w;
 
   // conv1..5 (+bn, relu applied on load by the consumer)           src/model.py:43-47
   // operand maxima from the statistics epilogues (training, split-fp16 cores): slots 0..4 =
   // activations of conv1..5, slot 5 = their maximum = the fusion conv's operand
-  float* op_amax = (training && gemm_mode() == 3) ? sv->op_amax : nullptr;
-  TRY(stack_forward(prm->conv, 5, ctx, P, training, momentum, eps, sv->z_cat, (long)cat,
+  float* op_amax = (training && c.mode == 3) ? sv->op_amax : nullptr;
+  TRY(stack_forward(c, prm->conv, 5, ctx, P, training, momentum, eps, sv->z_cat, (long)cat,
                     sv->bn_scale, sv->bn_shift, sv->bn_mean, sv->bn_rstd, w, st, op_amax));
   // fusion conv over the (never materialised) concat               src/model.py:50-51
   {
@@ -1503,8 +1489,8 @@ int prh_encoder_forward(const prh_encoder_params* prm, const float* ctx, int B, 
       p.ws_c = w.ws_c; p.ws_d = w.ws_d;      // slot 6: max relu(BN(zf)) >= max of the gated output
     }
     StatInfo si;
-    if (training) TRY((launch_nt<PRO_BNRELU, EPI_BIAS_STATS>(p, st, &si)));
-    else TRY((launch_nt<PRO_BNRELU, EPI_BIAS>(p, st)));
+    if (training) TRY((launch_nt<PRO_BNRELU, EPI_BIAS_STATS>(c, p, st, &si)));
+    else TRY((launch_nt<PRO_BNRELU, EPI_BIAS>(c, p, st)));
     TRY(bn_coeffs(prm->fusion, P, training, momentum, eps, w.ws_a, w.ws_b, w.stat2, si, sv->bn_mean + cat,
                   sv->bn_rstd + cat, sv->bn_scale + cat, sv->bn_shift + cat, st, w.ws_c, w.ws_d, w.apart,
                   op_amax ? op_amax + 6 : nullptr));
@@ -1520,10 +1506,10 @@ int prh_encoder_forward(const prh_encoder_params* prm, const float* ctx, int B, 
     p.flags = sv->gate ? F_STORE_GATE : 0;
     // dual pooling (src/model.py:58-60) on the epilogue that writes `fused`, when a segment is a
     // whole number of 128-row wave tiles and the vector epilogue serves the launch
-    const bool fuse_pool = gfeat != nullptr && (N % 128) == 0 && gemm_mode() == 3 &&
-                           nt_use_s3(P, od, 64) && (od & 3) == 0;
+    const bool fuse_pool = gfeat != nullptr && (N % 128) == 0 && c.mode == 3 &&
+                           nt_use_s3(c, P, od, 64) && (od & 3) == 0;
     if (fuse_pool) { p.flags |= F_POOL; p.ws_a = w.ws_a; p.ws_b = w.ws_b; p.ws_c = w.ws_c; }
-    TRY((launch_nt<PRO_GATE1, EPI_GATE>(p, st)));
+    TRY((launch_nt<PRO_GATE1, EPI_GATE>(c, p, st)));
     if ((p.flags & F_POOL) != 0) {
       hipLaunchKernelGGL(pool_tiles_kernel, dim3(cdiv(od, 256), B), dim3(256), 0, st, (const float*)w.ws_a,
                          (const float*)w.ws_b, (const int*)w.ws_c, N / 128, N, od, gfeat, sv->argmax);
@@ -1552,11 +1538,12 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   const int cat = enc_cat(prm), od = prm->out_dim, C = prm->in_channel;
+  const Cores c = cores_of(gemm_mode());
   Arena a(workspace, workspace_bytes);
   EncWS ews;
   if (d_fused_scratch && (d_fused == nullptr || d_gfeat != nullptr))
     return fail(PRH_ERR_ARG, "encoder_backward: d_fused_scratch needs d_fused and no d_gfeat");
-  enc_carve(a, ews, P, prm->conv, cat, od, d_fused_scratch ? 2 : 1);
+  enc_carve(c, a, ews, P, prm->conv, cat, od, d_fused_scratch ? 2 : 1);
   StackWS& w = ews.w;
   StackBwdScratch& sc = ews.sc;
   // combine_bwd_kernel reads dF[i] and writes dy[i] from the same thread: dy_f may live in the caller's d_fused
@@ -1589,7 +1576,7 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
   //     with layer-5 BN-backward partials (the only block that is complete here)
   StatInfo si5;
   const float* dzf_amax = nullptr;
-  const bool matf = dz_in_place(od, (long)od, (long)od);
+  const bool matf = dz_in_place(c, od, (long)od, (long)od);
   if (matf) {       // split-fp16 mode: dyf <- dz_f in place
     TRY(materialize_dz(dyf, (long)od, sv->z_fus, (long)od, sc.ca, sc.cb, sc.cc, P, od, sc.hdr, st));
     dzf_amax = sc.hdr;
@@ -1600,9 +1587,9 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
     t.B = sv->z_cat; t.ldb = cat; t.qa = sv->bn_scale; t.qb = sv->bn_shift;
     t.P = P; t.Mo = od; t.Ni = cat;
     t.amaxA = dzf_amax;
-    if (training && gemm_mode() == 3 && sv->op_amax != nullptr) t.amaxB = sv->op_amax + 5;
-    if (matf) TRY((launch_tn<PRO_NONE, PRO_BNRELU>(t, fslab, fcslab, gr->fusion.dw, (long)cat, nullptr, st)));
-    else TRY((launch_tn<PRO_BNBWD, PRO_BNRELU>(t, fslab, fcslab, gr->fusion.dw, (long)cat, nullptr, st)));
+    if (training && c.mode == 3 && sv->op_amax != nullptr) t.amaxB = sv->op_amax + 5;
+    if (matf) TRY((launch_tn<PRO_NONE, PRO_BNRELU>(c, t, fslab, fcslab, gr->fusion.dw, (long)cat, nullptr, st)));
+    else TRY((launch_tn<PRO_BNBWD, PRO_BNRELU>(c, t, fslab, fcslab, gr->fusion.dw, (long)cat, nullptr, st)));
     dzf_amax = t.amaxA;
   }
   {
@@ -1618,13 +1605,13 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
     // layers 1..4 are recomputed by the dgrad that completes them
     p.ws_a = w.ws_a; p.ws_b = w.ws_b;
     p.flags = F_MASK | F_STATS;
-    if (matf) TRY((launch_nt<PRO_NONE, EPI_DGRAD>(p, st, &si5)));
-    else TRY((launch_nt<PRO_BNBWD, EPI_DGRAD>(p, st, &si5)));
+    if (matf) TRY((launch_nt<PRO_NONE, EPI_DGRAD>(c, p, st, &si5)));
+    else TRY((launch_nt<PRO_BNBWD, EPI_DGRAD>(c, p, st, &si5)));
     si5.ld = cat; si5.off = d.off[4];
   }
   // (3) conv5..conv1
   float* dx = d_ctx;
-  TRY(stack_backward(prm->conv, 5, ctx, P, training, dy_cat, (long)cat, sv->z_cat, (long)cat,
+  TRY(stack_backward(c, prm->conv, 5, ctx, P, training, dy_cat, (long)cat, sv->z_cat, (long)cat,
                      sv->bn_scale, sv->bn_shift, sv->bn_mean, sv->bn_rstd, gr->conv, dx, w, sc, si5,
                      st, sv->op_amax));
 
@@ -1634,7 +1621,7 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
     TNParams t; memset(&t, 0, sizeof(t));
     t.A = dG; t.lda = od; t.B = ctx + 3; t.ldb = C; t.qa = prm->gate_w1; t.qb = prm->gate_b1;
     t.P = P; t.Mo = od; t.Ni = 64;
-    TRY((launch_tn<PRO_NONE, PRO_GATE1>(t, fslab, fcslab, gr->d_gate_w2, 64L, gr->d_gate_b2, st)));
+    TRY((launch_tn<PRO_NONE, PRO_GATE1>(c, t, fslab, fcslab, gr->d_gate_w2, 64L, gr->d_gate_b2, st)));
     TRY(transpose(prm->gate_w2, od, 64, sc.wT, st));   // [64, od]
     NTParams p; memset(&p, 0, sizeof(p));
     p.A = dG; p.lda = od; p.W = sc.wT; p.ldw = od; p.M = P; p.N = 64; p.K = od;
@@ -1642,7 +1629,7 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
     p.ws_a = w.ws_a; p.ws_b = w.ws_b;
     p.flags = F_MASK | F_STATS | F_E1_ROWVEC;
     StatInfo sig;
-    TRY((launch_nt<PRO_NONE, EPI_DGRAD>(p, st, &sig)));
+    TRY((launch_nt<PRO_NONE, EPI_DGRAD>(c, p, st, &sig)));
     hipLaunchKernelGGL(partials_reduce_kernel, dim3(2), dim3(1024), 0, st, w.ws_a, w.ws_b,
                        sig.count, 64, gr->d_gate_b1 ? gr->d_gate_b1 : gsum_a,
                        gr->d_gate_w1 ? gr->d_gate_w1 : gsum_b);
@@ -2265,11 +2252,78 @@ static bool attn_ksplit(int B, int H, int N, int& keys_per_wave) {
   keys_per_wave = cdiv(cdiv(N, 32), nw) * 32;
   return true;
 }
-static int check_attn(const AttnParams& a) {
+// dropout fields of a call, and the checks every attention launch needs
+static int attn_prepare(AttnParams& a, float dropout_p) {
+  a.seed_src = g_seed_src;
+  if (dropout_p < 0.f || dropout_p >= 1.f) return fail(PRH_ERR_ARG, "attention: dropout_p must be in [0,1)");
+  a.keep_scale = 1.f / (1.f - dropout_p);
+  a.drop_thresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
   if (!a.q || !a.k || !a.v || !a.o || !a.lse || a.B <= 0 || a.M <= 0 || a.N <= 0)
     return fail(PRH_ERR_ARG, "attention: bad argument");
   if (a.H <= 0 || a.H % 4) return fail(PRH_ERR_ARG, "attention: heads (%d) must be a multiple of 4", a.H);
   if ((a.ldq | a.ldk | a.ldv | a.ldo) & 3) return fail(PRH_ERR_ARG, "attention: leading dimensions must be multiples of 4");
+  return PRH_OK;
+}
+
+// Launch code of the fp32 and the bf16 K / V entry points.  a: pointers, shapes, scale and seed of the
+// call (kv16: K / V, and dK / dV, hold bf16 bits); prec: Cores::attn_prec() of the call.
+static int attn_forward(AttnParams& a, bool kv16, int prec, float dropout_p, int device, hipStream_t st) {
+  TRY(attn_prepare(a, dropout_p));
+  HIP_TRY(hipSetDevice(device));
+  const int B = a.B, M = a.M, N = a.N, H = a.H;
+  ProfScope ps(prec < 0 ? "attn_fwd" : "attn16_fwd<split>",
+               4.0 * B * H * (double)M * N * 32, 4.0 * (2.0 * B * N * H * 32 + 2.0 * B * M * H * 32), st);
+  int wpb = (long)B * (H / 4) < 512 ? 1 : 4;      // one head per workgroup while the grid would not fill the chip
+  if (kv16 && prec < 0) return fail(PRH_ERR_ARG, "attention: bf16 K/V need the 16-bit attention cores");
+  unsigned grid = (unsigned)(B * (H / wpb));
+  if (prec >= 0 && attn_ksplit(B, H, N, a.ksplit)) { wpb = cdiv(N, a.ksplit); grid = (unsigned)(B * H); }
+  const size_t ldsf = (size_t)wpb * a16_fwd_wave_lds<0>();
+  if (prec >= 0 && kv16)
+    hipLaunchKernelGGL((attn16_fwd_kernel<0, true>), dim3(grid), dim3(64 * wpb), ldsf, st, a);
+  else if (prec >= 0)
+    hipLaunchKernelGGL(attn16_fwd_kernel<0>, dim3(grid), dim3(64 * wpb), ldsf, st, a);
+  else
+    hipLaunchKernelGGL(attn_fwd_kernel, dim3(grid), dim3(64 * wpb), 0, st, a);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+static int attn_backward(AttnParams& a, bool kv16, int prec, float dropout_p, int device, hipStream_t st) {
+  TRY(attn_prepare(a, dropout_p));
+  if (!a.dout || !a.dq || !a.dk || !a.dv) return fail(PRH_ERR_ARG, "attention_backward: null gradient pointer");
+  if ((a.lddo | a.lddq | a.lddk | a.lddv) & 3) return fail(PRH_ERR_ARG, "attention_backward: leading dimensions must be multiples of 4");
+  HIP_TRY(hipSetDevice(device));
+  const int B = a.B, M = a.M, N = a.N, H = a.H;
+  int wpb = (long)B * (H / 4) < 512 ? 1 : 4;
+  if (prec >= 0) {
+    unsigned grid = (unsigned)(B * (H / wpb));
+    if (attn_ksplit(B, H, N, a.ksplit)) { wpb = cdiv(N, a.ksplit); grid = (unsigned)(B * H); }
+    const size_t lds16 = (size_t)wpb * 4 * 2 * A16_IMG;
+    static const int attr16 = allow_big_lds(attn16_bwd_kernel<0>, attn16_bwd_kernel<0, true>);
+    if (attr16 != PRH_OK) return attr16;
+    const double kvb = kv16 ? 2.0 : 4.0;
+    ProfScope ps("attn16_bwd<split>", 14.0 * B * H * (double)M * N * 32,
+                 kvb * 4.0 * B * N * H * 32 + 4.0 * 4.0 * B * M * H * 32, st);
+    if (a.ksplit > 0) {
+      static const int attr16s = allow_big_lds(attn16_bwd_kernel<0, false, true>, attn16_bwd_kernel<0, true, true>);
+      if (attr16s != PRH_OK) return attr16s;
+      if (kv16)
+        hipLaunchKernelGGL((attn16_bwd_kernel<0, true, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
+      else
+        hipLaunchKernelGGL((attn16_bwd_kernel<0, false, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
+    } else if (kv16)
+      hipLaunchKernelGGL((attn16_bwd_kernel<0, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
+    else
+      hipLaunchKernelGGL(attn16_bwd_kernel<0>, dim3(grid), dim3(64 * wpb), lds16, st, a);
+    LAUNCH_CHECK();
+    return PRH_OK;
+  }
+  const size_t lds = (size_t)wpb * 4 * AT_TILE * sizeof(float);
+  static const int attr_rc = allow_big_lds(attn_bwd_kernel);
+  if (attr_rc != PRH_OK) return attr_rc;
+  ProfScope ps("attn_bwd", 14.0 * B * H * (double)M * N * 32, 4.0 * (4.0 * B * N * H * 32 + 4.0 * B * M * H * 32), st);
+  hipLaunchKernelGGL(attn_bwd_kernel, dim3((unsigned)(B * (H / wpb))), dim3(64 * wpb), lds, st, a);
+  LAUNCH_CHECK();
   return PRH_OK;
 }
 
@@ -2278,29 +2332,8 @@ int prh_attn_forward(const float* q, long ldq, const float* k, long ldk, const f
                      float dropout_p, unsigned seed, int device, void* stream) {
   AttnParams a; memset(&a, 0, sizeof(a));
   a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.o = o; a.ldo = ldo; a.lse = lse;
-  a.B = B; a.M = M; a.N = N; a.H = H; a.scale = scale; a.seed = seed; a.seed_src = g_seed_src;
-  if (dropout_p < 0.f || dropout_p >= 1.f) return fail(PRH_ERR_ARG, "attention: dropout_p must be in [0,1)");
-  a.keep_scale = 1.f / (1.f - dropout_p);
-  a.drop_thresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
-  TRY(check_attn(a));
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  const int prec = attn_prec();
-  ProfScope ps(prec < 0 ? "attn_fwd" : "attn16_fwd<split>",
-               4.0 * B * H * (double)M * N * 32, 4.0 * (2.0 * B * N * H * 32 + 2.0 * B * M * H * 32), st);
-  int wpb = (long)B * (H / 4) < 512 ? 1 : 4;      // one head per workgroup while the grid would not fill the chip
-  if (g_attn_kv16 && prec < 0) return fail(PRH_ERR_ARG, "attention: bf16 K/V need the 16-bit attention cores");
-  unsigned grid = (unsigned)(B * (H / wpb));
-  if (prec >= 0 && attn_ksplit(B, H, N, a.ksplit)) { wpb = cdiv(N, a.ksplit); grid = (unsigned)(B * H); }
-  const size_t ldsf = (size_t)wpb * a16_fwd_wave_lds<0>();
-  if (prec >= 0 && g_attn_kv16)
-    hipLaunchKernelGGL((attn16_fwd_kernel<0, true>), dim3(grid), dim3(64 * wpb), ldsf, st, a);
-  else if (prec >= 0)
-    hipLaunchKernelGGL(attn16_fwd_kernel<0>, dim3(grid), dim3(64 * wpb), ldsf, st, a);
-  else
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(grid), dim3(64 * wpb), 0, st, a);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  a.B = B; a.M = M; a.N = N; a.H = H; a.scale = scale; a.seed = seed;
+  return attn_forward(a, false, cores_of(gemm_mode()).attn_prec(), dropout_p, device, (hipStream_t)stream);
 }
 
 int prh_attn_backward_ex(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv,
@@ -2313,60 +2346,8 @@ int prh_attn_backward_ex(const float* q, long ldq, const float* k, long ldk, con
   a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.o = (float*)o; a.ldo = ldo;
   a.lse = (float*)lse; a.dout = dout; a.lddo = lddo; a.dq = dq; a.lddq = lddq; a.dk = dk; a.lddk = lddk;
   a.dv = dv; a.lddv = lddv;
-  a.B = B; a.M = M; a.N = N; a.H = H; a.scale = scale; a.seed = seed; a.seed_src = g_seed_src;
-  if (dropout_p < 0.f || dropout_p >= 1.f) return fail(PRH_ERR_ARG, "attention: dropout_p must be in [0,1)");
-  a.keep_scale = 1.f / (1.f - dropout_p);
-  a.drop_thresh = dropout_p > 0.f ? (unsigned)((double)dropout_p * 4294967296.0) : 0u;
-  TRY(check_attn(a));
-  if (!dout || !dq || !dk || !dv) return fail(PRH_ERR_ARG, "attention_backward: null gradient pointer");
-  if ((lddo | lddq | lddk | lddv) & 3) return fail(PRH_ERR_ARG, "attention_backward: leading dimensions must be multiples of 4");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  int wpb = (long)B * (H / 4) < 512 ? 1 : 4;
-  const int prec = attn_prec();
-  if (prec >= 0) {
-    unsigned grid = (unsigned)(B * (H / wpb));
-    if (attn_ksplit(B, H, N, a.ksplit)) { wpb = cdiv(N, a.ksplit); grid = (unsigned)(B * H); }
-    const size_t lds16 = (size_t)wpb * 4 * 2 * A16_IMG;
-    static const int attr16 = [] {
-      return (hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-              hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) ? 0 : 1;
-    }();
-    if (attr16) return fail(PRH_ERR_HIP, "attention_backward: cannot raise the dynamic LDS limit");
-    const double kvb = g_attn_kv16 ? 2.0 : 4.0;
-    ProfScope ps("attn16_bwd<split>", 14.0 * B * H * (double)M * N * 32,
-                 kvb * 4.0 * B * N * H * 32 + 4.0 * 4.0 * B * M * H * 32, st);
-    if (a.ksplit > 0) {
-      static const int attr16s = [] {
-        return (hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<0, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) ? 0 : 1;
-      }();
-      if (attr16s) return fail(PRH_ERR_HIP, "attention_backward: cannot raise the dynamic LDS limit");
-      if (g_attn_kv16)
-        hipLaunchKernelGGL((attn16_bwd_kernel<0, true, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
-      else
-        hipLaunchKernelGGL((attn16_bwd_kernel<0, false, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
-    } else if (g_attn_kv16)
-      hipLaunchKernelGGL((attn16_bwd_kernel<0, true>), dim3(grid), dim3(64 * wpb), lds16, st, a);
-    else
-      hipLaunchKernelGGL(attn16_bwd_kernel<0>, dim3(grid), dim3(64 * wpb), lds16, st, a);
-    LAUNCH_CHECK();
-    return PRH_OK;
-  }
-  const size_t lds = (size_t)wpb * 4 * AT_TILE * sizeof(float);
-  static const int attr_rc = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 0 : 1;
-  }();
-  if (attr_rc) return fail(PRH_ERR_HIP, "attention_backward: cannot raise the dynamic LDS limit");
-  ProfScope ps("attn_bwd", 14.0 * B * H * (double)M * N * 32, 4.0 * (4.0 * B * N * H * 32 + 4.0 * B * M * H * 32), st);
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3((unsigned)(B * (H / wpb))), dim3(64 * wpb), lds, st, a);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  a.B = B; a.M = M; a.N = N; a.H = H; a.scale = scale; a.seed = seed;
+  return attn_backward(a, false, cores_of(gemm_mode()).attn_prec(), dropout_p, device, (hipStream_t)stream);
 }
 /* Inference-only cross-attention over the RAW memory rows with the layer's key / value projections
  * folded in (csrc/prh_attnfold.hpp).  prh_cast_perm_bf16: fp32 [rows, 256] (ld) -> the bf16 row image
@@ -2431,25 +2412,25 @@ int prh_attn_forward_kv16(const float* q, long ldq, const uint16_t* k, long ldk,
                           long ldo, float* lse, int B, int M, int N, int H, float scale, float dropout_p,
                           unsigned seed, int device, void* stream) {
   if ((ldk | ldv) & 7) return fail(PRH_ERR_ARG, "attention (bf16 K/V): leading dimensions must be multiples of 8");
-  g_attn_kv16 = true;
-  const int rc = prh_attn_forward(q, ldq, reinterpret_cast<const float*>(k), ldk, reinterpret_cast<const float*>(v), ldv, o,
-                                  ldo, lse, B, M, N, H, scale, dropout_p, seed, device, stream);
-  g_attn_kv16 = false;
-  return rc;
+  AttnParams a; memset(&a, 0, sizeof(a));
+  a.q = q; a.ldq = ldq; a.k = reinterpret_cast<const float*>(k); a.ldk = ldk; a.v = reinterpret_cast<const float*>(v);
+  a.ldv = ldv; a.o = o; a.ldo = ldo; a.lse = lse;
+  a.B = B; a.M = M; a.N = N; a.H = H; a.scale = scale; a.seed = seed;
+  return attn_forward(a, true, cores_of(gemm_mode()).attn_prec(), dropout_p, device, (hipStream_t)stream);
 }
 int prh_attn_backward_kv16(const float* q, long ldq, const uint16_t* k, long ldk, const uint16_t* v, long ldv,
                            const float* o, long ldo, const float* lse, const float* dout, long lddo, float* dq,
                            long lddq, uint16_t* dk, long lddk, uint16_t* dv, long lddv, int B, int M, int N, int H,
                            float scale, float dropout_p, unsigned seed, int device, void* stream) {
   if ((ldk | ldv | lddk | lddv) & 7) return fail(PRH_ERR_ARG, "attention (bf16 K/V): leading dimensions must be multiples of 8");
-  if (attn_prec() < 0) return fail(PRH_ERR_ARG, "attention: bf16 K/V need the 16-bit attention cores");
-  g_attn_kv16 = true;
-  const int rc = prh_attn_backward_ex(q, ldq, reinterpret_cast<const float*>(k), ldk, reinterpret_cast<const float*>(v), ldv,
-                                      o, ldo, lse, dout, lddo, dq, lddq, reinterpret_cast<float*>(dk), lddk,
-                                      reinterpret_cast<float*>(dv), lddv, B, M, N, H, scale, dropout_p, seed, nullptr,
-                                      device, stream);
-  g_attn_kv16 = false;
-  return rc;
+  const int prec = cores_of(gemm_mode()).attn_prec();
+  if (prec < 0) return fail(PRH_ERR_ARG, "attention: bf16 K/V need the 16-bit attention cores");
+  AttnParams a; memset(&a, 0, sizeof(a));
+  a.q = q; a.ldq = ldq; a.k = reinterpret_cast<const float*>(k); a.ldk = ldk; a.v = reinterpret_cast<const float*>(v);
+  a.ldv = ldv; a.o = (float*)o; a.ldo = ldo; a.lse = (float*)lse; a.dout = dout; a.lddo = lddo; a.dq = dq; a.lddq = lddq;
+  a.dk = reinterpret_cast<float*>(dk); a.lddk = lddk; a.dv = reinterpret_cast<float*>(dv); a.lddv = lddv;
+  a.B = B; a.M = M; a.N = N; a.H = H; a.scale = scale; a.seed = seed;
+  return attn_backward(a, true, prec, dropout_p, device, (hipStream_t)stream);
 }
 int prh_attn_backward(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv,
                       const float* o, long ldo, const float* lse, const float* dout, long lddo,
@@ -2504,7 +2485,7 @@ int prh_test_gemm_nt(const float* a, const float* w, float* c, int m, int n, int
   p.A = a; p.lda = k; p.W = w; p.ldw = k; p.C = c; p.ldc = n; p.M = m; p.N = n; p.K = k;
   if (workspace != nullptr && workspace_bytes >= s3_weight_bytes(n, k) + 256)
     p.wprep = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  return launch_nt<PRO_NONE, EPI_BIAS>(p, (hipStream_t)stream);
+  return launch_nt<PRO_NONE, EPI_BIAS>(cores_of(gemm_mode()), p, (hipStream_t)stream);
 }
 int prh_test_xcc_map(int blocks, int lds_bytes, int* out, int device, void* stream) {
   HIP_TRY(hipSetDevice(device));
@@ -2518,21 +2499,23 @@ int prh_test_xcc_map(int blocks, int lds_bytes, int* out, int device, void* stre
   return PRH_OK;
 }
 size_t prh_test_gemm_tn_workspace_bytes(int p, int mo, int ni) {
+  const Cores c = cores_of(gemm_mode());
   Arena a;
-  a.f(tn_slab_floats(p, mo, ni));
-  a.f(tn_colsum_floats(p, mo, ni));
+  a.f(tn_slab_floats(c, p, mo, ni));
+  a.f(tn_colsum_floats(c, p, mo, ni));
   return a.off + 256;
 }
 int prh_test_gemm_tn(const float* a, const float* b, float* c, float* colsum, int p, int mo, int ni,
                      void* workspace, size_t workspace_bytes, int device, void* stream) {
   HIP_TRY(hipSetDevice(device));
+  const Cores cores = cores_of(gemm_mode());
   Arena ar(workspace, workspace_bytes);
-  float* slab = ar.f(tn_slab_floats(p, mo, ni));
-  float* cs = ar.f(tn_colsum_floats(p, mo, ni));
+  float* slab = ar.f(tn_slab_floats(cores, p, mo, ni));
+  float* cs = ar.f(tn_colsum_floats(cores, p, mo, ni));
   if (!ar.ok) return fail(PRH_ERR_WORKSPACE, "test_gemm_tn: workspace too small");
   TNParams t; memset(&t, 0, sizeof(t));
   t.A = a; t.lda = mo; t.B = b; t.ldb = ni; t.P = p; t.Mo = mo; t.Ni = ni;
-  return launch_tn<PRO_NONE, PRO_NONE>(t, slab, cs, c, (long)ni, colsum, (hipStream_t)stream);
+  return launch_tn<PRO_NONE, PRO_NONE>(cores, t, slab, cs, c, (long)ni, colsum, (hipStream_t)stream);
 }
 
 }  // extern "C"
