@@ -359,6 +359,32 @@ int prh_context_build(const float* cloud, int npts, const float* dense, int n_de
                       float* dbg_weights, void* workspace, size_t workspace_bytes, int device,
                       void* stream);
 
+/* Scene evaluation (inference_whole_scene.py:26-92,299-365), fp64 throughout, FMA contraction off,
+ * distances as sqrt((dx*dx + dy*dy) + dz*dz) - the numpy order - so results match the
+ * reference's float64 numpy / scipy code to rounding even at UTM-sized coordinates.
+ * Per line (one wave each):
+ *   noisy, refined [n_lines,m,3] (m = 2..128; noisy is the resampled line the crop is matched to)
+ *   gt [*,3] ground-truth polylines as CSR with gt_offsets [n_gt+1] (int64);
+ *   gt_index [n_lines] polyline of each line, -1 = none
+ *   info [n_lines,4] int32: crop_start, crop_end, reversed, valid (crop_gt_to_pred_range, :26-70;
+ *        argmin ties to the first index)
+ *   resampled [n_lines,m,3] the crop resampled to m points (src/dataset.py:8-29)
+ *   metrics [n_lines,6]: ade_noisy, ade_refined, cd_noisy, cd_refined, lat_noisy, lat_refined
+ *        (ADE against the resample; Chamfer and lat = mean line->crop nearest distance against
+ *        the crop vertices, compute_chamfer_distance :72-92)
+ * Lines whose polyline has fewer than 2 vertices (or index -1) get valid = 0, crop -1/-1, a
+ * zero resample and NaN metrics. */
+int prh_line_metrics(const double* noisy, const double* refined, int n_lines, int m, const double* gt,
+                     const long long* gt_offsets, int n_gt, const int* gt_index, int* info, double* resampled,
+                     double* metrics, int device, void* stream);
+/* Alignment sweep (calibrate_alignment's inner loop, :170-193) for n_shifts shifts in one call:
+ *   out[s] = mean_p min_g |pred_p + (dx_s, dy_s, 0) - gt_g|,  pred [n_pred,3], gt [n_gt,3],
+ *   shifts [n_shifts,2] (dx, dy), out [n_shifts], all fp64.  Brute force over gt; per-block
+ * partial sums reduced in a fixed order: bitwise identical from run to run. */
+size_t prh_shift_sweep_workspace_bytes(int n_pred, int n_gt, int n_shifts);
+int prh_shift_sweep(const double* pred, int n_pred, const double* gt, int n_gt, const double* shifts, int n_shifts,
+                    double* out, void* workspace, size_t workspace_bytes, int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

@@ -5,6 +5,8 @@ context_proj, line point-MLP) behind the reference's nn.Module surface.
 """
 from .model import (DetrTransformerDecoderLayer, LineRefineNet, MultiScalePointNetEncoder,  # noqa: F401
                     PositionalEncoding)
+from .metrics import calibrate_alignment, evaluate_scene, line_metrics, shift_sweep  # noqa: F401
 
 __all__ = ["LineRefineNet", "MultiScalePointNetEncoder", "PositionalEncoding",
-           "DetrTransformerDecoderLayer"]
+           "DetrTransformerDecoderLayer",
+           "line_metrics", "shift_sweep", "calibrate_alignment", "evaluate_scene"]

@@ -76,6 +76,7 @@ EXPORTS = [
     "prh_profile_enable", "prh_profile_count", "prh_profile_reset", "prh_profile_read",
     "prh_attn_forward", "prh_attn_backward", "prh_attn_backward_ex",
     "prh_context_workspace_bytes", "prh_context_build",
+    "prh_line_metrics", "prh_shift_sweep_workspace_bytes", "prh_shift_sweep",
     "prh_l1_loss_workspace_bytes", "prh_l1_loss", "prh_adam_step",
     "prh_add_dropout_layernorm_forward", "prh_add_dropout_layernorm_workspace_bytes",
     "prh_add_dropout_layernorm_backward",
@@ -204,6 +205,12 @@ def _bind(lib):
     lib.prh_context_build.restype = i
     lib.prh_context_build.argtypes = [vp, i, vp, i, vp, i, i, f, f, i, i, C.c_ulonglong, vp, vp, vp, vp,
                                       C.c_size_t, i, vp]
+    lib.prh_line_metrics.restype = i
+    lib.prh_line_metrics.argtypes = [vp, vp, i, i, vp, vp, i, vp, vp, vp, vp, i, vp]
+    lib.prh_shift_sweep_workspace_bytes.restype = sz
+    lib.prh_shift_sweep_workspace_bytes.argtypes = [i, i, i]
+    lib.prh_shift_sweep.restype = i
+    lib.prh_shift_sweep.argtypes = [vp, i, vp, i, vp, i, vp, vp, sz, i, vp]
     lib.prh_add_dropout_layernorm_forward.restype = i
     lib.prh_add_dropout_layernorm_forward.argtypes = [vp, vp, vp, vp, lg, i, f, f, C.c_uint, vp, vp, vp, i, vp]
     lib.prh_add_dropout_layernorm_workspace_bytes.restype = C.c_size_t

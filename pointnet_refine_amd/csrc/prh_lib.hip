@@ -24,6 +24,7 @@
 #include "prh_attnfold.hpp"
 #include "prh_fused.hpp"
 #include "prh_context.hpp"
+#include "prh_metrics.hpp"
 #include "prh_kernels.hpp"
 
 using namespace prh;
@@ -2238,6 +2239,47 @@ int prh_context_build(const float* cloud, int npts, const float* dense, int n_de
   hipLaunchKernelGGL(ctx_select_kernel, dim3(n_lines), dim3(256), 0, st, cloud, line, m, (const int*)counts,
                      (const int*)w.cand, max_candidates, decay_scale, n_samples, (uint64_t)seed, w.keys, out,
                      dbg_weights);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ scene evaluation metrics
+int prh_line_metrics(const double* noisy, const double* refined, int n_lines, int m, const double* gt,
+                     const long long* gt_offsets, int n_gt, const int* gt_index, int* info, double* resampled,
+                     double* metrics, int device, void* stream) {
+  if (n_lines < 0 || n_gt < 0 || (n_lines > 0 && (!noisy || !refined || !gt_index || !info || !resampled || !metrics)) ||
+      (n_gt > 0 && (!gt || !gt_offsets)))
+    return fail(PRH_ERR_ARG, "line_metrics: bad argument");
+  if (m < 2 || m > MET_MAX_M) return fail(PRH_ERR_ARG, "line_metrics: m must be 2..%d", MET_MAX_M);
+  if (n_lines == 0) return PRH_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(met_line_kernel, dim3(n_lines), dim3(64), 0, st, noisy, refined, m, gt, gt_offsets, n_gt,
+                     gt_index, info, resampled, metrics);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+size_t prh_shift_sweep_workspace_bytes(int n_pred, int n_gt, int n_shifts) {
+  (void)n_gt;
+  if (n_pred <= 0 || n_shifts <= 0) return 0;
+  return (size_t)cdiv(n_pred, SW_THREADS) * (size_t)n_shifts * sizeof(double) + 256;
+}
+int prh_shift_sweep(const double* pred, int n_pred, const double* gt, int n_gt, const double* shifts, int n_shifts,
+                    double* out, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (!pred || !gt || !shifts || !out || n_pred <= 0 || n_gt <= 0 || n_shifts <= 0)
+    return fail(PRH_ERR_ARG, "shift_sweep: bad argument (needs at least one point, one GT point and one shift)");
+  if (cdiv(n_shifts, SW_SB) > 65535) return fail(PRH_ERR_ARG, "shift_sweep: at most %d shifts per call", 65535 * SW_SB);
+  if (workspace == nullptr || workspace_bytes < prh_shift_sweep_workspace_bytes(n_pred, n_gt, n_shifts))
+    return fail(PRH_ERR_WORKSPACE, "shift_sweep: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  const int n_qt = cdiv(n_pred, SW_THREADS);
+  double* partial = (double*)workspace;
+  hipLaunchKernelGGL(met_sweep_kernel, dim3(n_qt, cdiv(n_shifts, SW_SB)), dim3(SW_THREADS), 0, st, pred, n_pred, gt,
+                     n_gt, shifts, n_shifts, partial, n_qt);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(met_sweep_reduce_kernel, dim3(cdiv(n_shifts, 256)), dim3(256), 0, st, (const double*)partial,
+                     n_qt, n_shifts, n_pred, out);
   LAUNCH_CHECK();
   return PRH_OK;
 }

@@ -9,7 +9,8 @@
                      tools/generate_train_data.py:184-209)
   refine_scene       inference_whole_scene.py:94-146 for all lines of a scene at once: contexts
                      from the GPU builder (context.py), batched eval forward, refined line =
-                     resampled noisy line + last-layer offset
+                     resampled noisy line + last-layer offset (model side: scene_offsets, shared
+                     with metrics.evaluate_scene)
 """
 import json
 
@@ -83,13 +84,26 @@ def refine_scene(model, pcd_points, raw_lines, num_line_points=32, num_context_p
     BASELINE config 5's batched reduced-precision forward - encoder on one fp16 plane, decoder
     GEMMs on one bf16 plane (GEMM mode 4) for the duration of the call; "layers" = the per-layer
     kernels (the round-1 path, kept for comparison)."""
+    if len(raw_lines) == 0:
+        return np.zeros((0, num_line_points, 3)), np.zeros((0, num_line_points, 3))
+    offset, noisy_c, centres = scene_offsets(model, pcd_points, raw_lines, num_line_points, num_context_points,
+                                             crop_radius, decay_scale, batch_lines, seed, precision)
+    noisy = noisy_c + centres[:, None, :]
+    return (noisy + offset).cpu().numpy(), noisy.cpu().numpy()                                 # :146
+
+
+@torch.no_grad()
+def scene_offsets(model, pcd_points, raw_lines, num_line_points=32, num_context_points=1024,
+                  crop_radius=0.3, decay_scale=2.0, batch_lines=2048, seed=0, precision=None):
+    """The model side of refine_scene for a non-empty list of lines: contexts from the GPU builder
+    and the batched eval forward.  Returns CUDA float32 tensors (offset (L,M,3) = last-layer
+    output, noisy_c (L,M,3) = resampled line centred on centres (L,3)); the refined line is
+    noisy_c + centres + offset."""
     dev = next(model.parameters()).device
     cloud = pcd_points if torch.is_tensor(pcd_points) else torch.from_numpy(np.ascontiguousarray(pcd_points, dtype=np.float32))
     cloud = cloud.to(dev, torch.float32)
     if cloud.dim() == 2 and cloud.shape[1] > 4:
         cloud = cloud[:, :4]                      # ASCII PCDs may carry extra fields: x y z intensity come first
-    if len(raw_lines) == 0:
-        return np.zeros((0, num_line_points, 3)), np.zeros((0, num_line_points, 3))
     was_training = model.training
     model.eval()
     from . import ops as _ops
@@ -110,9 +124,7 @@ def refine_scene(model, pcd_points, raw_lines, num_line_points=32, num_context_p
             outs = []
             for s in range(0, ctx.shape[0], batch_lines):
                 outs.append(model(ctx[s:s + batch_lines], noisy_c[s:s + batch_lines])[-1])   # last layer, :139-141
-            offset = torch.cat(outs)
-            noisy = noisy_c + centres[:, None, :]
-            return (noisy + offset).cpu().numpy(), noisy.cpu().numpy()                         # :146
+            return torch.cat(outs), noisy_c, centres
     finally:
         model.train(was_training)
         if enc is not None:
