@@ -385,6 +385,51 @@ size_t prh_shift_sweep_workspace_bytes(int n_pred, int n_gt, int n_shifts);
 int prh_shift_sweep(const double* pred, int n_pred, const double* gt, int n_gt, const double* shifts, int n_shifts,
                     double* out, void* workspace, size_t workspace_bytes, int device, void* stream);
 
+/* Drive slicing (tools/generate_train_data.py:134-182,247-273; tools/augment_train_data.py:18-54).
+ * poses [n_slices,7] fp64 = x y z qx qy qz qw (the quaternion is normalised).  A point of cloud
+ * [npts,4] float32 belongs to slice s when, in float32 with every operation rounded separately,
+ * (x - f32(pose.x))^2 + (y - f32(pose.y))^2 < f32(radius^2), and its fp64 local x (inverse
+ * rotation of xyz - pose.xyz) lies in [-segment_len/2, segment_len/2].
+ *   prh_drive_slice_count  offsets [n_slices+1] int64: slice s owns rows offsets[s]..offsets[s+1]
+ *   prh_drive_slice_write  points [capacity,4] fp64 local xyz + the untouched intensity, in cloud
+ *                          order inside each slice; source_index [capacity] int64 cloud row of
+ *                          each emitted point.  Needs the SAME arguments, offsets and workspace
+ *                          (contents untouched) as the count call before it, and capacity >=
+ *                          offsets[n_slices]; rows beyond capacity are never written.
+ * No atomics: bitwise identical from run to run.  n_slices = 0 or npts = 0 give zero offsets. */
+size_t prh_drive_slice_workspace_bytes(int npts, int n_slices);
+int prh_drive_slice_count(const float* cloud, int npts, const double* poses, int n_slices, double segment_len,
+                          double radius, long long* offsets, void* workspace, size_t workspace_bytes, int device,
+                          void* stream);
+int prh_drive_slice_write(const float* cloud, int npts, const double* poses, int n_slices, double segment_len,
+                          double radius, const long long* offsets, double* points, long long* source_index,
+                          long long capacity, void* workspace, size_t workspace_bytes, int device, void* stream);
+/* clip_polyline_by_x (:145-182) of every polyline in every slice frame, fp64, one thread per
+ * (slice, line).  lines [*,3] with CSR line_offsets [n_lines+1] (int64).
+ *   prh_drive_clip_count  counts [n_slices*n_lines] int32: output vertices of pair s*n_lines + l
+ *                         (0- and 1-vertex inputs as the reference; the caller keeps counts > 1)
+ *   prh_drive_clip_write  out [*,3] at 3 * out_offsets[pair] (int64 exclusive prefix of counts) */
+size_t prh_drive_clip_workspace_bytes(int n_slices);
+int prh_drive_clip_count(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                         int n_slices, double segment_len, int* counts, void* workspace, size_t workspace_bytes,
+                         int device, void* stream);
+int prh_drive_clip_write(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                         int n_slices, double segment_len, const long long* out_offsets, double* out,
+                         void* workspace, size_t workspace_bytes, int device, void* stream);
+/* generate_noisy_line (augment_train_data.py:18-54) for n_scales (1..8) candidates of every line:
+ *   out [n_scales,n_verts,3] = (p - centroid) @ R(yaw).T + centroid + shift + jitter, fp64.
+ * lines [n_verts,3] with CSR line_offsets [n_lines+1]; vertex_line [n_verts] int32 line of each
+ * vertex.  draw != 0: yaw ~ U(+-5 deg * s) (stored in rad), dx, dy ~ U(+-s), dz ~ U(+-0.1),
+ * jitter ~ N(0, 0.05 / 0.05 / 0.025) from a counter hash of (seed, line id, candidate, vertex,
+ * component) - line id = line_ids[l], or l when line_ids is NULL - written to draws_u
+ * [n_lines,n_scales,4] and draws_j [n_scales,n_verts,3]; draw == 0: both are inputs and scales
+ * and seed are ignored.  Same distribution as numpy's generator, not the same numbers. */
+size_t prh_drive_noise_workspace_bytes(int n_lines);
+int prh_drive_noise(const double* lines, const long long* line_offsets, const int* vertex_line, long long n_verts,
+                    int n_lines, const int* line_ids, const double* scales, int n_scales, unsigned long long seed,
+                    int draw, double* draws_u, double* draws_j, double* out, void* workspace,
+                    size_t workspace_bytes, int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

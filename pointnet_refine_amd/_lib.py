@@ -77,6 +77,9 @@ EXPORTS = [
     "prh_attn_forward", "prh_attn_backward", "prh_attn_backward_ex",
     "prh_context_workspace_bytes", "prh_context_build",
     "prh_line_metrics", "prh_shift_sweep_workspace_bytes", "prh_shift_sweep",
+    "prh_drive_slice_workspace_bytes", "prh_drive_slice_count", "prh_drive_slice_write",
+    "prh_drive_clip_workspace_bytes", "prh_drive_clip_count", "prh_drive_clip_write",
+    "prh_drive_noise_workspace_bytes", "prh_drive_noise",
     "prh_l1_loss_workspace_bytes", "prh_l1_loss", "prh_adam_step",
     "prh_add_dropout_layernorm_forward", "prh_add_dropout_layernorm_workspace_bytes",
     "prh_add_dropout_layernorm_backward",
@@ -211,6 +214,24 @@ def _bind(lib):
     lib.prh_shift_sweep_workspace_bytes.argtypes = [i, i, i]
     lib.prh_shift_sweep.restype = i
     lib.prh_shift_sweep.argtypes = [vp, i, vp, i, vp, i, vp, vp, sz, i, vp]
+    ll, dbl = C.c_longlong, C.c_double
+    lib.prh_drive_slice_workspace_bytes.restype = sz
+    lib.prh_drive_slice_workspace_bytes.argtypes = [i, i]
+    lib.prh_drive_slice_count.restype = i
+    lib.prh_drive_slice_count.argtypes = [vp, i, vp, i, dbl, dbl, vp, vp, sz, i, vp]
+    lib.prh_drive_slice_write.restype = i
+    lib.prh_drive_slice_write.argtypes = [vp, i, vp, i, dbl, dbl, vp, vp, vp, ll, vp, sz, i, vp]
+    lib.prh_drive_clip_workspace_bytes.restype = sz
+    lib.prh_drive_clip_workspace_bytes.argtypes = [i]
+    lib.prh_drive_clip_count.restype = i
+    lib.prh_drive_clip_count.argtypes = [vp, vp, i, vp, i, dbl, vp, vp, sz, i, vp]
+    lib.prh_drive_clip_write.restype = i
+    lib.prh_drive_clip_write.argtypes = [vp, vp, i, vp, i, dbl, vp, vp, vp, sz, i, vp]
+    lib.prh_drive_noise_workspace_bytes.restype = sz
+    lib.prh_drive_noise_workspace_bytes.argtypes = [i]
+    lib.prh_drive_noise.restype = i
+    lib.prh_drive_noise.argtypes = [vp, vp, vp, ll, i, vp, C.POINTER(dbl), i, C.c_ulonglong, i, vp, vp, vp, vp, sz,
+                                    i, vp]
     lib.prh_add_dropout_layernorm_forward.restype = i
     lib.prh_add_dropout_layernorm_forward.argtypes = [vp, vp, vp, vp, lg, i, f, f, C.c_uint, vp, vp, vp, i, vp]
     lib.prh_add_dropout_layernorm_workspace_bytes.restype = C.c_size_t

@@ -25,6 +25,7 @@
 #include "prh_fused.hpp"
 #include "prh_context.hpp"
 #include "prh_metrics.hpp"
+#include "prh_drive.hpp"
 #include "prh_kernels.hpp"
 
 using namespace prh;
@@ -2280,6 +2281,155 @@ int prh_shift_sweep(const double* pred, int n_pred, const double* gt, int n_gt, 
   LAUNCH_CHECK();
   hipLaunchKernelGGL(met_sweep_reduce_kernel, dim3(cdiv(n_shifts, 256)), dim3(256), 0, st, (const double*)partial,
                      n_qt, n_shifts, n_pred, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ drive slicing
+struct DrvWS { DrvPose* pose; int* cnt; long long* tile; };
+void drv_carve(Arena& a, DrvWS& w, int npts, int S) {
+  const size_t n_units = (size_t)cdiv(npts, DRV_UNIT), n_tiles = (size_t)cdiv((long)n_units, DRV_TILE);
+  w.pose = (DrvPose*)a.f((size_t)S * sizeof(DrvPose) / sizeof(float));
+  w.cnt = (int*)a.f(n_units * S);
+  w.tile = (long long*)a.f(n_tiles * S * 2);
+}
+size_t prh_drive_slice_workspace_bytes(int npts, int n_slices) {
+  if (npts < 0 || n_slices < 0) return 0;
+  Arena a; DrvWS w;
+  drv_carve(a, w, npts, n_slices);
+  return a.off + 256;
+}
+static int drv_slice(bool fill, const float* cloud, int npts, const double* poses, int S, double segment_len,
+                     double radius, long long* offsets, double* points, long long* source_index,
+                     long long capacity, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const char* what = fill ? "drive_slice_write" : "drive_slice_count";
+  if (npts < 0 || S < 0 || !offsets || (npts > 0 && !cloud) || (S > 0 && !poses) || !(segment_len >= 0.0) ||
+      !(radius >= 0.0))
+    return fail(PRH_ERR_ARG, "%s: bad argument", what);
+  if (fill && (capacity < 0 || (capacity > 0 && (!points || !source_index))))
+    return fail(PRH_ERR_ARG, "%s: bad output buffer", what);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  if (S == 0 || npts == 0) {
+    if (!fill) HIP_TRY(hipMemsetAsync(offsets, 0, (size_t)(S + 1) * sizeof(long long), st));
+    return PRH_OK;
+  }
+  Arena a(workspace, workspace_bytes);
+  DrvWS w;
+  drv_carve(a, w, npts, S);
+  if (!workspace || !a.ok) return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  const long n_units = cdiv(npts, DRV_UNIT), n_tiles = cdiv(n_units, DRV_TILE);
+  const float r2 = (float)(radius * radius);
+  const double half = segment_len / 2;
+  const int nblk = cdiv(n_units, 4);
+  if (!fill) {
+    hipLaunchKernelGGL(drv_pose_kernel, dim3(cdiv(S, 256)), dim3(256), 0, st, poses, S, w.pose);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL((drv_slice_kernel<false>), dim3(nblk), dim3(256), 0, st, (const float4*)cloud, npts,
+                       (const DrvPose*)w.pose, S, r2, half, w.cnt, (const long long*)nullptr,
+                       (const long long*)nullptr, (double*)nullptr, (long long*)nullptr, 0ll);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(drv_tile_scan_kernel, dim3((unsigned)n_tiles, cdiv(S, 256)), dim3(256), 0, st, w.cnt,
+                       (long long)n_units, S, w.tile);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(drv_tile_base_kernel, dim3(1), dim3(256), 0, st, w.tile, (long long)n_tiles, S, offsets);
+    LAUNCH_CHECK();
+    return PRH_OK;
+  }
+  if (capacity == 0) return PRH_OK;
+  hipLaunchKernelGGL((drv_slice_kernel<true>), dim3(nblk), dim3(256), 0, st, (const float4*)cloud, npts,
+                     (const DrvPose*)w.pose, S, r2, half, w.cnt, (const long long*)w.tile,
+                     (const long long*)offsets, points, source_index, capacity);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_drive_slice_count(const float* cloud, int npts, const double* poses, int n_slices, double segment_len,
+                          double radius, long long* offsets, void* workspace, size_t workspace_bytes, int device,
+                          void* stream) {
+  return drv_slice(false, cloud, npts, poses, n_slices, segment_len, radius, offsets, nullptr, nullptr, 0, workspace,
+                   workspace_bytes, device, stream);
+}
+int prh_drive_slice_write(const float* cloud, int npts, const double* poses, int n_slices, double segment_len,
+                          double radius, const long long* offsets, double* points, long long* source_index,
+                          long long capacity, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  return drv_slice(true, cloud, npts, poses, n_slices, segment_len, radius, (long long*)offsets, points,
+                   source_index, capacity, workspace, workspace_bytes, device, stream);
+}
+size_t prh_drive_clip_workspace_bytes(int n_slices) {
+  if (n_slices < 0) return 0;
+  return align_up((size_t)n_slices * sizeof(DrvPose), 256) + 256;
+}
+static int drv_clip(bool write, const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                    int S, double segment_len, int* counts, const long long* out_offsets, double* out,
+                    void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const char* what = write ? "drive_clip_write" : "drive_clip_count";
+  if (n_lines < 0 || S < 0 || !(segment_len >= 0.0)) return fail(PRH_ERR_ARG, "%s: bad argument", what);
+  if (n_lines == 0 || S == 0) return PRH_OK;
+  if (!lines || !line_offsets || !poses || (write ? (!out_offsets || !out) : !counts))
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if ((long long)S * n_lines > 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "%s: too many (slice, line) pairs", what);
+  if (!workspace || workspace_bytes < prh_drive_clip_workspace_bytes(S))
+    return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  DrvPose* pose = (DrvPose*)workspace;
+  hipLaunchKernelGGL(drv_pose_kernel, dim3(cdiv(S, 256)), dim3(256), 0, st, poses, S, pose);
+  LAUNCH_CHECK();
+  const int nblk = cdiv((long)S * n_lines, 256);
+  if (write)
+    hipLaunchKernelGGL((drv_clip_kernel<true>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, n_lines,
+                       (const DrvPose*)pose, S, segment_len / 2, (int*)nullptr, out_offsets, out);
+  else
+    hipLaunchKernelGGL((drv_clip_kernel<false>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, n_lines,
+                       (const DrvPose*)pose, S, segment_len / 2, counts, (const long long*)nullptr, (double*)nullptr);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_drive_clip_count(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                         int n_slices, double segment_len, int* counts, void* workspace, size_t workspace_bytes,
+                         int device, void* stream) {
+  return drv_clip(false, lines, line_offsets, n_lines, poses, n_slices, segment_len, counts, nullptr, nullptr,
+                  workspace, workspace_bytes, device, stream);
+}
+int prh_drive_clip_write(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                         int n_slices, double segment_len, const long long* out_offsets, double* out,
+                         void* workspace, size_t workspace_bytes, int device, void* stream) {
+  return drv_clip(true, lines, line_offsets, n_lines, poses, n_slices, segment_len, nullptr, out_offsets, out,
+                  workspace, workspace_bytes, device, stream);
+}
+size_t prh_drive_noise_workspace_bytes(int n_lines) {
+  if (n_lines < 0) return 0;
+  return align_up((size_t)n_lines * 3 * sizeof(double), 256) + 256;
+}
+int prh_drive_noise(const double* lines, const long long* line_offsets, const int* vertex_line, long long n_verts,
+                    int n_lines, const int* line_ids, const double* scales, int n_scales, unsigned long long seed,
+                    int draw, double* draws_u, double* draws_j, double* out, void* workspace,
+                    size_t workspace_bytes, int device, void* stream) {
+  if (n_lines < 0 || n_verts < 0 || n_scales < 1 || n_scales > DRV_MAX_SCALES || (draw && !scales))
+    return fail(PRH_ERR_ARG, "drive_noise: bad argument (1..%d scales)", DRV_MAX_SCALES);
+  if (n_lines == 0 || n_verts == 0) return PRH_OK;
+  if (!lines || !line_offsets || !vertex_line || !draws_u || !draws_j || !out)
+    return fail(PRH_ERR_ARG, "drive_noise: null pointer");
+  if (n_verts * n_scales > 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "drive_noise: too many vertices");
+  if (!workspace || workspace_bytes < prh_drive_noise_workspace_bytes(n_lines))
+    return fail(PRH_ERR_WORKSPACE, "drive_noise: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  double* centroid = (double*)workspace;
+  DrvScales sc;
+  for (int k = 0; k < DRV_MAX_SCALES; ++k) sc.s[k] = (draw && k < n_scales) ? scales[k] : 0.0;
+  hipLaunchKernelGGL(drv_centroid_kernel, dim3(cdiv(3l * n_lines, 256)), dim3(256), 0, st, lines, line_offsets,
+                     n_lines, centroid);
+  LAUNCH_CHECK();
+  const int nblk = cdiv(n_verts * n_scales, 256);
+  if (draw)
+    hipLaunchKernelGGL((drv_noise_kernel<true>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, vertex_line,
+                       n_verts, n_lines, line_ids, sc, n_scales, (uint64_t)seed, (const double*)centroid, draws_u,
+                       draws_j, out);
+  else
+    hipLaunchKernelGGL((drv_noise_kernel<false>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, vertex_line,
+                       n_verts, n_lines, line_ids, sc, n_scales, (uint64_t)seed, (const double*)centroid, draws_u,
+                       draws_j, out);
   LAUNCH_CHECK();
   return PRH_OK;
 }

@@ -157,11 +157,20 @@ class SceneSampleStream:
     batch cannot dead-lock.  ``batch_size=None`` keeps one batch per scene (single-rank use: the number
     of batches then depends on which scenes a rank drew from).  ``rank`` / ``world_size`` default to
     the initialised process group (else 0 / 1).  Iterating yields dicts of CUDA tensors with a leading
-    sample dimension; ``len()`` is the number of samples this rank sees per epoch."""
+    sample dimension; ``len()`` is the number of samples this rank sees per epoch.
+
+    ``augment=None`` takes the candidates stored in the scene files (written by the reference's
+    ``augment_train_data.py``: three frozen draws per GT line).  ``augment=(s0, s1, ...)`` - noise
+    scales, ``(0.1, 0.25, 0.4)`` in the reference - needs no stored candidates: every item whose
+    ``position`` has at least 2 vertices counts, stored ``noisy_candidates`` are ignored, and
+    candidate k of an item is drawn on the device with scale ``augment[k]`` from a counter hash of
+    (seed, epoch, scene, item, k) (``drive.noisy_candidates``), so every epoch sees fresh noise and
+    the same epoch always the same.  Everything else - ``len()``, sharding, padding, batching - works
+    on the (item, k) pairs as before."""
 
     def __init__(self, data_root, num_line_points=32, num_context_points=2048, crop_radius=4.0,
                  decay_scale=2.0, split="train", device="cuda", seed=0, batch_size=None, shuffle=True,
-                 rank=None, world_size=None, mix_scenes=4, drop_last=False):
+                 rank=None, world_size=None, mix_scenes=4, drop_last=False, augment=None):
         import os
         import torch.distributed as dist
         self.num_line_points, self.num_context_points = num_line_points, num_context_points
@@ -174,6 +183,9 @@ class SceneSampleStream:
             raise ValueError(f"SceneSampleStream: rank {self.rank} outside world_size {self.world}")
         self.batch_size, self.shuffle = batch_size, bool(shuffle)
         self.mix_scenes, self.drop_last = max(1, int(mix_scenes)), bool(drop_last)
+        self.augment = None if augment is None else tuple(float(s) for s in augment)
+        if self.augment is not None and not 1 <= len(self.augment) <= 8:
+            raise ValueError("SceneSampleStream: augment takes 1..8 noise scales")
         self.scenes = []                       # (pcd_path, json_path, [(item_idx, noise_idx), ...])
         for name in sorted(f for f in os.listdir(data_root) if f.endswith(".json")):
             json_path = os.path.join(data_root, name)
@@ -182,9 +194,13 @@ class SceneSampleStream:
                 continue                                             # :149-150
             with open(json_path, "r") as f:
                 data = json.load(f)
-            pairs = [(i, k) for i, item in enumerate(data.get("items", []))
-                     if "noisy_candidates" in item and "position" in item               # :156-157
-                     for k in range(len(item["noisy_candidates"]))]
+            if self.augment is None:
+                pairs = [(i, k) for i, item in enumerate(data.get("items", []))
+                         if "noisy_candidates" in item and "position" in item               # :156-157
+                         for k in range(len(item["noisy_candidates"]))]
+            else:
+                pairs = [(i, k) for i, item in enumerate(data.get("items", []))
+                         if len(item.get("position") or []) >= 2 for k in range(len(self.augment))]
             if pairs:
                 self.scenes.append((pcd_path, json_path, pairs))
         self.epoch = 0
@@ -218,7 +234,15 @@ class SceneSampleStream:
         cloud = torch.from_numpy(np.atleast_2d(load_pcd_data(pcd_path))[:, :4].astype(np.float32, copy=False))
         cloud = cloud.to(self.device, torch.float32).contiguous()
         items = load_scene_items(json_path)
-        raw_noisy = [items[i]["noisy_candidates"][k] for i, k in pairs]
+        if self.augment is None:
+            raw_noisy = [items[i]["noisy_candidates"][k] for i, k in pairs]
+        else:
+            from .drive import stream_candidates
+            used = sorted({i for i, _ in pairs})
+            row = {i: r for r, i in enumerate(used)}
+            cands = stream_candidates([items[i]["position"] for i in used], used, self.augment,
+                                      (int(self.seed) * 1000003 + self.epoch) * 65537 + si, self.device)
+            raw_noisy = [cands[k][row[i]] for i, k in pairs]
         gt = np.stack([resample_polyline(items[i]["position"], self.num_line_points) for i, _ in pairs])
         ctx, noisy_c, centres, counts = build_contexts(
             cloud, raw_noisy, self.num_line_points, self.num_context_points, self.crop_radius, self.decay_scale,
