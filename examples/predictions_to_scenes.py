@@ -1,0 +1,61 @@
+"""Prediction scenes (the reference's tools/generate_inference_data_vma.py): DRIVE_DIR holds
+pose/*.json and merged.pcd, GT_JSON the drive's GT polylines, RESULTS_JSON the lane detector's
+per-frame BEV-pixel polylines; OUT_DIR receives one TS.pcd / TS.json scene per camera frame, each
+prediction paired with the GT line the global assignment gives it - the files
+examples/evaluate_scenes.py reads.  Every frame of the drive goes through one slice, one clip, one
+cost and one assignment launch on the GPU.
+
+    python examples/predictions_to_scenes.py DRIVE_DIR GT_JSON RESULTS_JSON OUT_DIR [--evaluate CHECKPOINT]
+
+--evaluate CHECKPOINT scores what was written with metrics.evaluate_scene (CHECKPOINT: a
+LineRefineNet state_dict, or "procedural" for deterministic weights that exercise the path only)
+and prints the mean ADE / Lat before and after over valid, non-bad-match rows.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("drive_dir")
+    ap.add_argument("gt_json")
+    ap.add_argument("results_json")
+    ap.add_argument("out_dir")
+    ap.add_argument("--evaluate", metavar="CHECKPOINT", default=None)
+    args = ap.parse_args()
+    from pointnet_refine_amd import io, metrics, predictions
+    res = predictions.predictions_to_scenes(args.drive_dir, args.gt_json, args.results_json, args.out_dir)
+    if args.evaluate is None:
+        return
+    import torch
+    from pointnet_refine_amd.model import LineRefineNet
+    model = LineRefineNet()
+    if args.evaluate == "procedural":
+        from oracle import procedural as P
+        model.load_state_dict(P.linerefine_state_dict(0))
+    else:
+        model.load_state_dict(torch.load(args.evaluate, map_location="cpu"))
+    model = model.cuda().eval()
+    keep = {k: [] for k in ("ade_noisy", "ade_refined", "lat_noisy", "lat_refined")}
+    rows = bad = 0
+    for ts in res["written"]:
+        items = io.load_scene_items(os.path.join(args.out_dir, f"{ts}.json"))
+        ev = metrics.evaluate_scene(model, io.load_pcd_data(os.path.join(args.out_dir, f"{ts}.pcd")), items)
+        use = ev["valid"] & ~ev["bad_match"]
+        rows, bad = rows + len(use), bad + int(ev["bad_match"].sum())
+        for k in keep:
+            keep[k] += ev[k][use].tolist()
+    mean = {k: (float(np.mean(v)) if v else float("nan")) for k, v in keep.items()}
+    print(f"EVALUATION over {len(res['written'])} scenes, {rows} predictions, {len(keep['ade_noisy'])} scored, "
+          f"{bad} bad matches: ADE {mean['ade_noisy']:.3f}->{mean['ade_refined']:.3f} | "
+          f"Lat {mean['lat_noisy']:.3f}->{mean['lat_refined']:.3f}")
+
+
+if __name__ == "__main__":
+    main()

@@ -430,6 +430,45 @@ int prh_drive_noise(const double* lines, const long long* line_offsets, const in
                     int draw, double* draws_u, double* draws_j, double* out, void* workspace,
                     size_t workspace_bytes, int device, void* stream);
 
+/* ---- prediction scenes (tools/generate_inference_data_vma.py of the reference) ---------------
+ * Per camera frame: GT polylines clipped into the ego frame by that tool's rule, a (prediction x
+ * GT) matrix of one-way xy Chamfer costs, and the minimum-cost assignment.  fp64 throughout, no
+ * atomics: every output is bitwise reproducible.
+ *
+ * Clipping: as prh_drive_clip_* (same buffers, poses [n_frames,7]), with this tool's rule: a line
+ * counts only if some vertex has -segment_len/2 < local x < segment_len/2 (else count 0), and is
+ * cut by two half-plane passes without de-duplication, an edge with |dx| < 1e-6 giving its first
+ * vertex as the intersection. */
+size_t prh_match_clip_workspace_bytes(int n_frames);
+int prh_match_clip_count(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                         int n_frames, double segment_len, int* counts, void* workspace, size_t workspace_bytes,
+                         int device, void* stream);
+int prh_match_clip_write(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                         int n_frames, double segment_len, const long long* out_offsets, double* out,
+                         void* workspace, size_t workspace_bytes, int device, void* stream);
+/* Costs: pred_xy / gt_xy [*,2] fp64 vertices; *_line_offsets int64 vertex CSR over lines;
+ * *_frame_offsets [n_frames+1] int64 line CSR over frames; frame f's (P_f, G_f) row-major matrix
+ * goes to costs + cost_offsets[f]: cost[i,j] = mean over the vertices of prediction i of the
+ * distance to the nearest vertex of GT line j. */
+size_t prh_match_costs_workspace_bytes(long long n_pred_lines);
+int prh_match_costs(const double* pred_xy, const long long* pred_line_offsets, const long long* pred_frame_offsets,
+                    long long n_pred_lines, const double* gt_xy, const long long* gt_line_offsets,
+                    const long long* gt_frame_offsets, int n_frames, const long long* cost_offsets, double* costs,
+                    void* workspace, size_t workspace_bytes, int device, void* stream);
+/* Assignment (needs no workspace): shapes [n_frames,2] int32 (P_f, G_f), each side at most
+ * prh_match_max_side(); max_cells >= the largest P_f * G_f of the call (it sizes the LDS image).
+ * match + row_offsets[f] [P_f] int32: the GT column of each prediction or -1, also -1 where
+ * use_threshold and the pair's cost is not < threshold; total [n_frames]: the optimal sum before
+ * the threshold; status [n_frames] int32: 0 solved, 1 a non-finite cost (all -1, total NaN),
+ * 2 above the size bound.  row_dual (at row_offsets) / col_dual (at col_offsets), both optional:
+ * the potentials u, v the solver ended with, cost[i,j] - u[i] - v[j] >= 0 with equality on the
+ * assigned pairs. */
+int prh_match_max_side(void);
+int prh_match_assign(const double* costs, const long long* cost_offsets, const int* shapes, const long long* row_offsets,
+                     const long long* col_offsets, int n_frames, long long max_cells, double threshold,
+                     int use_threshold, int* match, double* total, int* status, double* row_dual, double* col_dual,
+                     int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

@@ -80,6 +80,8 @@ EXPORTS = [
     "prh_drive_slice_workspace_bytes", "prh_drive_slice_count", "prh_drive_slice_write",
     "prh_drive_clip_workspace_bytes", "prh_drive_clip_count", "prh_drive_clip_write",
     "prh_drive_noise_workspace_bytes", "prh_drive_noise",
+    "prh_match_clip_workspace_bytes", "prh_match_clip_count", "prh_match_clip_write",
+    "prh_match_costs_workspace_bytes", "prh_match_costs", "prh_match_max_side", "prh_match_assign",
     "prh_l1_loss_workspace_bytes", "prh_l1_loss", "prh_adam_step",
     "prh_add_dropout_layernorm_forward", "prh_add_dropout_layernorm_workspace_bytes",
     "prh_add_dropout_layernorm_backward",
@@ -232,6 +234,20 @@ def _bind(lib):
     lib.prh_drive_noise.restype = i
     lib.prh_drive_noise.argtypes = [vp, vp, vp, ll, i, vp, C.POINTER(dbl), i, C.c_ulonglong, i, vp, vp, vp, vp, sz,
                                     i, vp]
+    lib.prh_match_clip_workspace_bytes.restype = sz
+    lib.prh_match_clip_workspace_bytes.argtypes = [i]
+    lib.prh_match_clip_count.restype = i
+    lib.prh_match_clip_count.argtypes = [vp, vp, i, vp, i, dbl, vp, vp, sz, i, vp]
+    lib.prh_match_clip_write.restype = i
+    lib.prh_match_clip_write.argtypes = [vp, vp, i, vp, i, dbl, vp, vp, vp, sz, i, vp]
+    lib.prh_match_costs_workspace_bytes.restype = sz
+    lib.prh_match_costs_workspace_bytes.argtypes = [ll]
+    lib.prh_match_costs.restype = i
+    lib.prh_match_costs.argtypes = [vp, vp, vp, ll, vp, vp, vp, i, vp, vp, vp, sz, i, vp]
+    lib.prh_match_max_side.restype = i
+    lib.prh_match_max_side.argtypes = []
+    lib.prh_match_assign.restype = i
+    lib.prh_match_assign.argtypes = [vp, vp, vp, vp, vp, i, ll, dbl, i, vp, vp, vp, vp, vp, i, vp]
     lib.prh_add_dropout_layernorm_forward.restype = i
     lib.prh_add_dropout_layernorm_forward.argtypes = [vp, vp, vp, vp, lg, i, f, f, C.c_uint, vp, vp, vp, i, vp]
     lib.prh_add_dropout_layernorm_workspace_bytes.restype = C.c_size_t

@@ -26,6 +26,7 @@
 #include "prh_context.hpp"
 #include "prh_metrics.hpp"
 #include "prh_drive.hpp"
+#include "prh_match.hpp"
 #include "prh_kernels.hpp"
 
 using namespace prh;
@@ -2430,6 +2431,93 @@ int prh_drive_noise(const double* lines, const long long* line_offsets, const in
     hipLaunchKernelGGL((drv_noise_kernel<false>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, vertex_line,
                        n_verts, n_lines, line_ids, sc, n_scales, (uint64_t)seed, (const double*)centroid, draws_u,
                        draws_j, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ prediction scenes
+size_t prh_match_clip_workspace_bytes(int n_frames) { return prh_drive_clip_workspace_bytes(n_frames); }
+static int mt_clip(bool write, const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                   int F, double segment_len, int* counts, const long long* out_offsets, double* out,
+                   void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const char* what = write ? "match_clip_write" : "match_clip_count";
+  if (n_lines < 0 || F < 0 || !(segment_len >= 0.0)) return fail(PRH_ERR_ARG, "%s: bad argument", what);
+  if (n_lines == 0 || F == 0) return PRH_OK;
+  if (!lines || !line_offsets || !poses || (write ? (!out_offsets || !out) : !counts))
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if ((long long)F * n_lines > 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "%s: too many (frame, line) pairs", what);
+  if (!workspace || workspace_bytes < prh_match_clip_workspace_bytes(F))
+    return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  DrvPose* pose = (DrvPose*)workspace;
+  hipLaunchKernelGGL(drv_pose_kernel, dim3(cdiv(F, 256)), dim3(256), 0, st, poses, F, pose);
+  LAUNCH_CHECK();
+  const int nblk = cdiv((long)F * n_lines, 256);
+  if (write)
+    hipLaunchKernelGGL((mt_clip_kernel<true>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, n_lines,
+                       (const DrvPose*)pose, F, segment_len / 2, (int*)nullptr, out_offsets, out);
+  else
+    hipLaunchKernelGGL((mt_clip_kernel<false>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, n_lines,
+                       (const DrvPose*)pose, F, segment_len / 2, counts, (const long long*)nullptr, (double*)nullptr);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_match_clip_count(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                         int n_frames, double segment_len, int* counts, void* workspace, size_t workspace_bytes,
+                         int device, void* stream) {
+  return mt_clip(false, lines, line_offsets, n_lines, poses, n_frames, segment_len, counts, nullptr, nullptr,
+                 workspace, workspace_bytes, device, stream);
+}
+int prh_match_clip_write(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
+                         int n_frames, double segment_len, const long long* out_offsets, double* out,
+                         void* workspace, size_t workspace_bytes, int device, void* stream) {
+  return mt_clip(true, lines, line_offsets, n_lines, poses, n_frames, segment_len, nullptr, out_offsets, out,
+                 workspace, workspace_bytes, device, stream);
+}
+size_t prh_match_costs_workspace_bytes(long long n_pred_lines) {
+  if (n_pred_lines < 0) return 0;
+  return align_up((size_t)n_pred_lines * sizeof(int), 256) + 256;
+}
+int prh_match_costs(const double* pred_xy, const long long* pred_line_offsets, const long long* pred_frame_offsets,
+                    long long n_pred_lines, const double* gt_xy, const long long* gt_line_offsets,
+                    const long long* gt_frame_offsets, int n_frames, const long long* cost_offsets, double* costs,
+                    void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (n_frames < 0 || n_pred_lines < 0) return fail(PRH_ERR_ARG, "match_costs: bad argument");
+  if (n_frames == 0 || n_pred_lines == 0) return PRH_OK;
+  if (n_pred_lines > 0x7fffffffll) return fail(PRH_ERR_ARG, "match_costs: at most 2^31 - 1 prediction lines per call");
+  if (!pred_line_offsets || !pred_frame_offsets || !gt_line_offsets || !gt_frame_offsets || !cost_offsets)
+    return fail(PRH_ERR_ARG, "match_costs: null pointer");
+  if (!workspace || workspace_bytes < prh_match_costs_workspace_bytes(n_pred_lines))
+    return fail(PRH_ERR_WORKSPACE, "match_costs: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* line_frame = (int*)workspace;
+  hipLaunchKernelGGL(mt_line_frame_kernel, dim3(cdiv(n_frames, 256)), dim3(256), 0, st, pred_frame_offsets, n_frames,
+                     line_frame);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(mt_cost_kernel, dim3((unsigned)n_pred_lines), dim3(MT_COST_THREADS), 0, st, pred_xy,
+                     pred_line_offsets, pred_frame_offsets, (const int*)line_frame, gt_xy, gt_line_offsets,
+                     gt_frame_offsets, cost_offsets, costs);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_match_max_side(void) { return MT_MAX_SIDE; }
+int prh_match_assign(const double* costs, const long long* cost_offsets, const int* shapes, const long long* row_offsets,
+                     const long long* col_offsets, int n_frames, long long max_cells, double threshold,
+                     int use_threshold, int* match, double* total, int* status, double* row_dual, double* col_dual,
+                     int device, void* stream) {
+  if (n_frames < 0 || max_cells < 0 || max_cells > (long long)MT_MAX_SIDE * MT_MAX_SIDE)
+    return fail(PRH_ERR_ARG, "match_assign: bad argument (at most %d lines per side per frame)", MT_MAX_SIDE);
+  if (n_frames == 0) return PRH_OK;
+  if (!cost_offsets || !shapes || !row_offsets || !col_offsets || !total || !status)
+    return fail(PRH_ERR_ARG, "match_assign: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = mt_assign_lds(max_cells);
+  if (lds > 64 * 1024) TRY_RC(allow_big_lds(mt_assign_kernel));
+  hipLaunchKernelGGL(mt_assign_kernel, dim3(n_frames), dim3(64), lds, st, costs, cost_offsets, shapes, row_offsets,
+                     col_offsets, max_cells, threshold, use_threshold, match, total, status, row_dual, col_dual);
   LAUNCH_CHECK();
   return PRH_OK;
 }
