@@ -2,11 +2,14 @@
 """The reference's training loop (train_dist.py:143-242) on the MI355X path with synthetic
 data: the ONLY model-side change against the reference is the import line.
 
-    python examples/train_synthetic.py                       # one GPU
+    python examples/train_synthetic.py [--vis DIR]           # one GPU
     torchrun --nproc_per_node=8 --master-addr 127.0.0.1 examples/train_synthetic.py
 
 DistributedDataParallel over backend "nccl" (= RCCL on ROCm) is used exactly as the reference
-does (find_unused_parameters=True, per-rank BatchNorm statistics, rank-0 logging/checkpoint)."""
+does (find_unused_parameters=True, per-rank BatchNorm statistics, rank-0 logging/checkpoint).
+--vis DIR writes the reference's per-epoch picture of sample 0 of the first batch
+(train_dist.py:18-56,213-217) as DIR/vis_epoch_NNN.png, rendered on the GPU (bev.render_sample)."""
+import argparse
 import os
 import sys
 
@@ -21,6 +24,9 @@ from pointnet_refine_amd.synth import synthetic_batch
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--vis", default=None, metavar="DIR", help="write vis_epoch_NNN.png of sample 0 per epoch")
+    args = ap.parse_args()
     distributed = "LOCAL_RANK" in os.environ
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     rank = int(os.environ.get("RANK", "0"))
@@ -50,6 +56,11 @@ def main():
             loss.backward()
             optimizer.step()
             total += loss.item()
+            if it == 0 and rank == 0 and args.vis:                   # train_dist.py:213-217
+                from pointnet_refine_amd import bev
+                os.makedirs(args.vis, exist_ok=True)
+                bev.write_png(os.path.join(args.vis, f"vis_epoch_{epoch + 1:03d}.png"),
+                              bev.render_sample(context, noisy_line, pred_offsets_stack[-1], target_offset))
         if rank == 0:
             print(f"Epoch [{epoch + 1}/{EPOCHS}] avg loss {total / STEPS_PER_EPOCH:.4f}")
     if rank == 0:

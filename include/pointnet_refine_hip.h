@@ -469,6 +469,75 @@ int prh_match_assign(const double* costs, const long long* cost_offsets, const i
                      int use_threshold, int* match, double* total, int* status, double* row_dual, double* col_dual,
                      int device, void* stream);
 
+/* ---- BEV rendering (tools/vis_inference_bev.py and train_dist.py:18-56 of the reference) -----
+ * Intensity image (:74-104).  points [n,4] x y z intensity, fp32 or fp64 (is_double), contiguous.
+ * prh_bev_bounds: info [5] fp64 = x_min x_max y_min y_max of the points (exact) and 1.0 when an x,
+ * y or intensity is NaN or infinite.  prh_bev_raster: image [n_slices,height,width] fp32; slice s
+ * owns points offsets[s]..offsets[s+1] (offsets NULL: one slice).  In the dtype of the points,
+ * one rounding per operation: u = int32((y - y_min) / resolution), v = int32((x_max - x) /
+ * resolution), toward zero; points outside 0 <= u < width, 0 <= v < height are dropped; a pixel
+ * holds the maximum float32 intensity of its points and 0.0 when it has none (integer atomicMax of
+ * an order-preserving key: the same bits every run).  *bad (device int) = 1 when a value is not
+ * finite; the image is then unspecified. */
+size_t prh_bev_bounds_workspace_bytes(void);
+int prh_bev_bounds(const void* points, long long n, int is_double, double* info, void* workspace,
+                   size_t workspace_bytes, int device, void* stream);
+int prh_bev_raster(const void* points, const long long* offsets, int n_slices, long long n, int is_double,
+                   double y_min, double x_max, double resolution, int height, int width, float* image, int* bad,
+                   int device, void* stream);
+/* Tone map (:143-148).  prh_bev_select: per slice of image [n_slices,pixels] the two order
+ * statistics of the pixels > 0 that numpy's percentile (method 'linear') interpolates between, by
+ * an exact radix select over the float bits: out [n_slices,4] fp64 = count of positive pixels,
+ * a[floor(i)], a[floor(i) + 1] (or a[count - 1] twice at the top), weight i - floor(i), with
+ * i = (count - 1) * quantile in fp32, as numpy computes it for an fp32 array; all zero for a slice
+ * without a positive pixel.
+ * prh_bev_tone: out = p[s] > 0 ? powf(clip(image / p[s], 0, 1), gamma) : image, fp32.
+ * prh_bev_colorize: out RGBA bytes = table[min(int(norm * 256), 255)] (table [256] packed RGBA, R
+ * in the low byte), opaque black where image == 0. */
+size_t prh_bev_select_workspace_bytes(int n_slices);
+int prh_bev_select(const float* image, int n_slices, long long pixels, float quantile, double* out, void* workspace,
+                   size_t workspace_bytes, int device, void* stream);
+int prh_bev_tone(const float* image, int n_slices, long long pixels, const float* p, float gamma, float* out,
+                 int device, void* stream);
+int prh_bev_colorize(const float* norm, const float* image, long long pixels, const unsigned* table, unsigned* out,
+                     int device, void* stream);
+/* Views.  Packed views: view k is an (H_k, W_k) RGBA image at pixel_offsets[k] of one buffer.
+ * prh_bev_crop: views [n_views,4] int32 = u0, v0, H_k, W_k; pixel (v, u) of view k is pixel
+ * (v + v0, u + u0) of rgba [height,width], opaque black outside it.
+ *
+ * Overlays - the rule.  A view shows a window (y_lo, y_hi, x_lo, x_hi) in metres at `resolution`
+ * metres per pixel: column u grows with y, row v grows with decreasing x, pixel (v, u) has its
+ * centre at (u + 0.5, v + 0.5) in pixel units, so a point (x, y) lies at ((y - y_lo) / resolution,
+ * (x_hi - x) / resolution).  A polyline has a colour (RGB, 0..255), a width w in pixels, an
+ * opacity a and a dash (on, off) in pixels measured along the line from its first vertex (off = 0:
+ * solid).  For a pixel centre at distance d from the nearest point of a segment, that segment
+ * covers the pixel by clamp(w / 2 + 0.5 - d, 0, 1), and by zero when that nearest point lies in an
+ * "off" stretch (arc length modulo (on + off) >= on).  A line covers a pixel by the maximum c over
+ * its segments.  Lines are composited in the order given: rgb = rgb * (1 - a * c) + colour * (a *
+ * c), in fp64, rounded to the nearest integer once after the last line; alpha is kept.  A pixel
+ * no line covers is not written.
+ * segments [n_segments,5] fp64 = ax ay bx by in the pixel units of the line's view and the arc
+ * length at a; segment_line the line of each (ascending); styles [n_lines,7] fp64 = r g b a w on
+ * off; line_view the view of each line; view_dims [n_views,4] int32 = H, W, tiles across, tiles
+ * down (tiles of prh_bev_tile() pixels); tile_base [n_views] the first tile of each view;
+ * tile_view [n_tiles] the view of each tile.  prh_bev_draw_count: tile_count [n_tiles] = segments
+ * whose bounding box, grown by w / 2 + 0.5, touches the tile; the caller's exclusive scan of it is
+ * tile_offsets [n_tiles+1], n_items its last entry.  prh_bev_draw composites into canvas (packed
+ * views).  Work: one bounding-box walk per segment and, per pixel, the segments binned to its
+ * tile.  Bitwise reproducible. */
+int prh_bev_crop(const unsigned* rgba, int height, int width, const int* views, const long long* pixel_offsets,
+                 int n_views, long long total_pixels, unsigned* out, int device, void* stream);
+int prh_bev_tile(void);
+int prh_bev_draw_count(const double* segments, const int* segment_line, int n_segments, const double* styles,
+                       const int* line_view, const int* view_dims, const long long* tile_base, long long n_tiles,
+                       int* tile_count, int device, void* stream);
+size_t prh_bev_draw_workspace_bytes(long long n_tiles, long long n_items);
+int prh_bev_draw(const double* segments, const int* segment_line, int n_segments, const double* styles,
+                 const int* line_view, const int* view_dims, const long long* tile_base,
+                 const long long* pixel_offsets, const int* tile_view, const long long* tile_offsets,
+                 long long n_tiles, long long n_items, unsigned* canvas, void* workspace, size_t workspace_bytes,
+                 int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

@@ -82,6 +82,9 @@ EXPORTS = [
     "prh_drive_noise_workspace_bytes", "prh_drive_noise",
     "prh_match_clip_workspace_bytes", "prh_match_clip_count", "prh_match_clip_write",
     "prh_match_costs_workspace_bytes", "prh_match_costs", "prh_match_max_side", "prh_match_assign",
+    "prh_bev_bounds_workspace_bytes", "prh_bev_bounds", "prh_bev_raster", "prh_bev_select_workspace_bytes",
+    "prh_bev_select", "prh_bev_tone", "prh_bev_colorize", "prh_bev_crop", "prh_bev_tile", "prh_bev_draw_count",
+    "prh_bev_draw_workspace_bytes", "prh_bev_draw",
     "prh_l1_loss_workspace_bytes", "prh_l1_loss", "prh_adam_step",
     "prh_add_dropout_layernorm_forward", "prh_add_dropout_layernorm_workspace_bytes",
     "prh_add_dropout_layernorm_backward",
@@ -248,6 +251,30 @@ def _bind(lib):
     lib.prh_match_max_side.argtypes = []
     lib.prh_match_assign.restype = i
     lib.prh_match_assign.argtypes = [vp, vp, vp, vp, vp, i, ll, dbl, i, vp, vp, vp, vp, vp, i, vp]
+    lib.prh_bev_bounds_workspace_bytes.restype = sz
+    lib.prh_bev_bounds_workspace_bytes.argtypes = []
+    lib.prh_bev_bounds.restype = i
+    lib.prh_bev_bounds.argtypes = [vp, ll, i, vp, vp, sz, i, vp]
+    lib.prh_bev_raster.restype = i
+    lib.prh_bev_raster.argtypes = [vp, vp, i, ll, i, dbl, dbl, dbl, i, i, vp, vp, i, vp]
+    lib.prh_bev_select_workspace_bytes.restype = sz
+    lib.prh_bev_select_workspace_bytes.argtypes = [i]
+    lib.prh_bev_select.restype = i
+    lib.prh_bev_select.argtypes = [vp, i, ll, f, vp, vp, sz, i, vp]
+    lib.prh_bev_tone.restype = i
+    lib.prh_bev_tone.argtypes = [vp, i, ll, vp, f, vp, i, vp]
+    lib.prh_bev_colorize.restype = i
+    lib.prh_bev_colorize.argtypes = [vp, vp, ll, vp, vp, i, vp]
+    lib.prh_bev_crop.restype = i
+    lib.prh_bev_crop.argtypes = [vp, i, i, vp, vp, i, ll, vp, i, vp]
+    lib.prh_bev_tile.restype = i
+    lib.prh_bev_tile.argtypes = []
+    lib.prh_bev_draw_count.restype = i
+    lib.prh_bev_draw_count.argtypes = [vp, vp, i, vp, vp, vp, vp, ll, vp, i, vp]
+    lib.prh_bev_draw_workspace_bytes.restype = sz
+    lib.prh_bev_draw_workspace_bytes.argtypes = [ll, ll]
+    lib.prh_bev_draw.restype = i
+    lib.prh_bev_draw.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, ll, ll, vp, vp, sz, i, vp]
     lib.prh_add_dropout_layernorm_forward.restype = i
     lib.prh_add_dropout_layernorm_forward.argtypes = [vp, vp, vp, vp, lg, i, f, f, C.c_uint, vp, vp, vp, i, vp]
     lib.prh_add_dropout_layernorm_workspace_bytes.restype = C.c_size_t

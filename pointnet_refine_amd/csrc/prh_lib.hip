@@ -27,6 +27,7 @@
 #include "prh_metrics.hpp"
 #include "prh_drive.hpp"
 #include "prh_match.hpp"
+#include "prh_bev.hpp"
 #include "prh_kernels.hpp"
 
 using namespace prh;
@@ -2518,6 +2519,182 @@ int prh_match_assign(const double* costs, const long long* cost_offsets, const i
   if (lds > 64 * 1024) TRY_RC(allow_big_lds(mt_assign_kernel));
   hipLaunchKernelGGL(mt_assign_kernel, dim3(n_frames), dim3(64), lds, st, costs, cost_offsets, shapes, row_offsets,
                      col_offsets, max_cells, threshold, use_threshold, match, total, status, row_dual, col_dual);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ BEV rendering
+size_t prh_bev_bounds_workspace_bytes(void) {
+  return align_up((size_t)BEV_BOUNDS_BLOCKS * 4 * sizeof(double), 256) + align_up((size_t)BEV_BOUNDS_BLOCKS * sizeof(int), 256);
+}
+int prh_bev_bounds(const void* points, long long n, int is_double, double* info, void* workspace,
+                   size_t workspace_bytes, int device, void* stream) {
+  if (n <= 0 || !points || !info) return fail(PRH_ERR_ARG, "bev_bounds: bad argument");
+  if (!workspace || workspace_bytes < prh_bev_bounds_workspace_bytes())
+    return fail(PRH_ERR_WORKSPACE, "bev_bounds: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* bad = (int*)((char*)workspace + align_up((size_t)BEV_BOUNDS_BLOCKS * 4 * sizeof(double), 256));
+  const long want = (n + BEV_THREADS - 1) / BEV_THREADS;
+  const int nblk = (int)(want < BEV_BOUNDS_BLOCKS ? want : BEV_BOUNDS_BLOCKS);
+  if (is_double) {
+    hipLaunchKernelGGL(bev_bounds_kernel<double>, dim3(nblk), dim3(BEV_THREADS), 0, st, (const double*)points, n,
+                       (double*)workspace, bad);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(bev_bounds_final<double>, dim3(1), dim3(BEV_THREADS), 0, st, (const double*)workspace,
+                       (const int*)bad, nblk, info);
+  } else {
+    hipLaunchKernelGGL(bev_bounds_kernel<float>, dim3(nblk), dim3(BEV_THREADS), 0, st, (const float*)points, n,
+                       (float*)workspace, bad);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(bev_bounds_final<float>, dim3(1), dim3(BEV_THREADS), 0, st, (const float*)workspace,
+                       (const int*)bad, nblk, info);
+  }
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_bev_raster(const void* points, const long long* offsets, int n_slices, long long n, int is_double,
+                   double y_min, double x_max, double resolution, int height, int width, float* image, int* bad,
+                   int device, void* stream) {
+  if (n < 0 || n_slices < 0 || height < 0 || width < 0 || !bad) return fail(PRH_ERR_ARG, "bev_raster: bad argument");
+  const long long cells = (long long)n_slices * height * width;
+  if (cells >= 256ll * 0x7fffffff || n >= 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "bev_raster: too large");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
+  if (cells == 0) return PRH_OK;
+  if (!image || (n > 0 && !points)) return fail(PRH_ERR_ARG, "bev_raster: null pointer");
+  HIP_TRY(hipMemsetAsync(image, 0, (size_t)cells * sizeof(float), st));
+  if (n > 0) {
+    const unsigned nblk = (unsigned)((n + BEV_THREADS - 1) / BEV_THREADS);
+    if (is_double)
+      hipLaunchKernelGGL(bev_raster_kernel<double>, dim3(nblk), dim3(BEV_THREADS), 0, st, (const double*)points,
+                         offsets, n_slices, n, y_min, x_max, resolution, height, width, (unsigned*)image, bad);
+    else
+      hipLaunchKernelGGL(bev_raster_kernel<float>, dim3(nblk), dim3(BEV_THREADS), 0, st, (const float*)points, offsets,
+                         n_slices, n, (float)y_min, (float)x_max, (float)resolution, height, width, (unsigned*)image,
+                         bad);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(bev_finalize_kernel, dim3((unsigned)((cells + BEV_THREADS - 1) / BEV_THREADS)), dim3(BEV_THREADS),
+                     0, st, (unsigned*)image, cells);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+size_t prh_bev_select_workspace_bytes(int n_slices) {
+  if (n_slices < 0) return 0;
+  return align_up((size_t)n_slices * sizeof(BevSel), 256) + align_up((size_t)n_slices * 512 * sizeof(unsigned), 256);
+}
+int prh_bev_select(const float* image, int n_slices, long long pixels, float quantile, double* out, void* workspace,
+                   size_t workspace_bytes, int device, void* stream) {
+  if (n_slices < 0 || pixels < 0 || !(quantile >= 0.f && quantile <= 1.f) || n_slices > 65535)
+    return fail(PRH_ERR_ARG, "bev_select: bad argument");
+  if (n_slices == 0) return PRH_OK;
+  if (!out || (pixels > 0 && !image)) return fail(PRH_ERR_ARG, "bev_select: null pointer");
+  if (!workspace || workspace_bytes < prh_bev_select_workspace_bytes(n_slices))
+    return fail(PRH_ERR_WORKSPACE, "bev_select: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  BevSel* sel = (BevSel*)workspace;
+  unsigned* hist = (unsigned*)((char*)workspace + align_up((size_t)n_slices * sizeof(BevSel), 256));
+  HIP_TRY(hipMemsetAsync(workspace, 0, prh_bev_select_workspace_bytes(n_slices), st));
+  HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_slices * 4 * sizeof(double), st));
+  long want = (pixels + 4L * BEV_THREADS - 1) / (4L * BEV_THREADS);
+  const int bx = (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));
+  for (int pass = 0; pass < 4; ++pass) {
+    hipLaunchKernelGGL(bev_hist_kernel, dim3(bx, n_slices), dim3(BEV_THREADS), 0, st, image, pixels, pass,
+                       (const BevSel*)sel, hist);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(bev_pick_kernel, dim3(cdiv(2L * n_slices, 64)), dim3(64), 0, st, sel, hist, n_slices, pass,
+                       quantile, out);
+    LAUNCH_CHECK();
+  }
+  return PRH_OK;
+}
+int prh_bev_tone(const float* image, int n_slices, long long pixels, const float* p, float gamma, float* out,
+                 int device, void* stream) {
+  if (n_slices < 0 || pixels < 0 || n_slices > 65535 || pixels >= 256ll * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "bev_tone: bad argument");
+  if (n_slices == 0 || pixels == 0) return PRH_OK;
+  if (!image || !p || !out) return fail(PRH_ERR_ARG, "bev_tone: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(bev_tone_kernel, dim3((unsigned)((pixels + BEV_THREADS - 1) / BEV_THREADS), n_slices),
+                     dim3(BEV_THREADS), 0, (hipStream_t)stream, image, pixels, p, gamma, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_bev_colorize(const float* norm, const float* image, long long pixels, const unsigned* table, unsigned* out,
+                     int device, void* stream) {
+  if (pixels < 0 || pixels >= 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "bev_colorize: bad argument");
+  if (pixels == 0) return PRH_OK;
+  if (!norm || !image || !table || !out) return fail(PRH_ERR_ARG, "bev_colorize: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(bev_colorize_kernel, dim3((unsigned)((pixels + BEV_THREADS - 1) / BEV_THREADS)),
+                     dim3(BEV_THREADS), 0, (hipStream_t)stream, norm, image, pixels, table, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_bev_crop(const unsigned* rgba, int height, int width, const int* views, const long long* pixel_offsets,
+                 int n_views, long long total_pixels, unsigned* out, int device, void* stream) {
+  if (height < 0 || width < 0 || n_views < 0 || total_pixels < 0 || total_pixels >= 256ll * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "bev_crop: bad argument");
+  if (n_views == 0 || total_pixels == 0) return PRH_OK;
+  if (!views || !pixel_offsets || !out || ((long long)height * width > 0 && !rgba))
+    return fail(PRH_ERR_ARG, "bev_crop: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(bev_crop_kernel, dim3((unsigned)((total_pixels + BEV_THREADS - 1) / BEV_THREADS)),
+                     dim3(BEV_THREADS), 0, (hipStream_t)stream, rgba, height, width, views, pixel_offsets, n_views,
+                     total_pixels, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_bev_tile(void) { return BEV_TILE; }
+int prh_bev_draw_count(const double* segments, const int* segment_line, int n_segments, const double* styles,
+                       const int* line_view, const int* view_dims, const long long* tile_base, long long n_tiles,
+                       int* tile_count, int device, void* stream) {
+  if (n_segments < 0 || n_tiles < 0) return fail(PRH_ERR_ARG, "bev_draw_count: bad argument");
+  if (n_tiles == 0) return PRH_OK;
+  if (!tile_count) return fail(PRH_ERR_ARG, "bev_draw_count: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(tile_count, 0, (size_t)n_tiles * sizeof(int), st));
+  if (n_segments == 0) return PRH_OK;
+  if (!segments || !segment_line || !styles || !line_view || !view_dims || !tile_base)
+    return fail(PRH_ERR_ARG, "bev_draw_count: null pointer");
+  hipLaunchKernelGGL((bev_bin_kernel<false>), dim3(cdiv(n_segments, BEV_THREADS)), dim3(BEV_THREADS), 0, st, segments,
+                     segment_line, n_segments, styles, line_view, view_dims, tile_base, tile_count,
+                     (const long long*)nullptr, (int*)nullptr);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+size_t prh_bev_draw_workspace_bytes(long long n_tiles, long long n_items) {
+  if (n_tiles < 0 || n_items < 0) return 0;
+  return align_up((size_t)n_tiles * sizeof(int), 256) + 2 * align_up((size_t)n_items * sizeof(int), 256) + 256;
+}
+int prh_bev_draw(const double* segments, const int* segment_line, int n_segments, const double* styles,
+                 const int* line_view, const int* view_dims, const long long* tile_base,
+                 const long long* pixel_offsets, const int* tile_view, const long long* tile_offsets,
+                 long long n_tiles, long long n_items, unsigned* canvas, void* workspace, size_t workspace_bytes,
+                 int device, void* stream) {
+  if (n_segments < 0 || n_tiles < 0 || n_items < 0 || n_tiles > 0x7fffffffll)
+    return fail(PRH_ERR_ARG, "bev_draw: bad argument");
+  if (n_segments == 0 || n_tiles == 0 || n_items == 0) return PRH_OK;
+  if (!segments || !segment_line || !styles || !line_view || !view_dims || !tile_base || !pixel_offsets ||
+      !tile_view || !tile_offsets || !canvas)
+    return fail(PRH_ERR_ARG, "bev_draw: null pointer");
+  if (!workspace || workspace_bytes < prh_bev_draw_workspace_bytes(n_tiles, n_items))
+    return fail(PRH_ERR_WORKSPACE, "bev_draw: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* cursor = (int*)workspace;
+  int* items = (int*)((char*)workspace + align_up((size_t)n_tiles * sizeof(int), 256));
+  int* sorted = (int*)((char*)items + align_up((size_t)n_items * sizeof(int), 256));
+  HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)n_tiles * sizeof(int), st));
+  hipLaunchKernelGGL((bev_bin_kernel<true>), dim3(cdiv(n_segments, BEV_THREADS)), dim3(BEV_THREADS), 0, st, segments,
+                     segment_line, n_segments, styles, line_view, view_dims, tile_base, cursor, tile_offsets, items);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(bev_draw_kernel, dim3((unsigned)n_tiles), dim3(BEV_THREADS), 0, st, segments, segment_line, styles,
+                     view_dims, tile_base, pixel_offsets, tile_view, tile_offsets, (const int*)items, sorted, canvas);
   LAUNCH_CHECK();
   return PRH_OK;
 }
