@@ -430,6 +430,60 @@ int prh_drive_noise(const double* lines, const long long* line_offsets, const in
                     int draw, double* draws_u, double* draws_j, double* out, void* workspace,
                     size_t workspace_bytes, int device, void* stream);
 
+/* ---- PCD text codec (save_pcd, tools/generate_train_data.py:184-190; src/dataset.py:31-76) ----
+ * Integer arithmetic, no atomics: every output is bitwise reproducible.
+ *
+ * Formatter.  points [n_rows,4] fp64 (is_fp64 != 0) or fp32, 16-byte aligned.  The text of a row
+ * is "%.4f %.4f %.4f %d\n" byte for byte as C printf / Python's % operator write it: %.4f rounds
+ * half to even on the exact binary value, a negative value that rounds to zero and -0.0 keep
+ * their sign, %d truncates toward zero.  Domain: finite x, y, z with |v| < 2^40 and finite
+ * intensity with |v| < 2^53; a row outside it has length 0 and no byte is written for it.
+ * Rows are formatted in groups of prh_pcd_group_rows() (64), G = ceil(n_rows / 64).
+ *   prh_pcd_format_count  row_bytes [n_rows] u8 length of each row, group_bytes [G] int32 their
+ *                         sums; status [1] int64 = the first row outside the domain, or -1
+ *   prh_pcd_format_write  group_offsets [G+1] int64 = exclusive prefix sum of group_bytes (the
+ *                         caller's scan); text [capacity] the rows back to back (bytes at or past
+ *                         capacity are never written); offsets [n_slices+1] int64 rows of each
+ *                         slice (NULL: one slice of all rows) -> byte_offsets [n_slices+1] int64,
+ *                         slice s is text[byte_offsets[s] .. byte_offsets[s+1])
+ *
+ * Parser.  payload [n_bytes] is the text after the header, any alignment, any length.
+ *   prh_pcd_index_blocks  NB, blocks of 4096 bytes on the 16-byte aligned address grid (pure)
+ *   prh_pcd_index_count   block_lines [NB] int32 newlines per block
+ *   prh_pcd_index_write   block_offsets [NB+1] int64 = exclusive prefix sum of block_lines;
+ *                         row_start [n_rows+1] int64: row r is payload[row_start[r] ..
+ *                         row_start[r+1]); n_rows = newlines + 1 if the last byte is not one
+ *   prh_pcd_parse         out [n_rows,ncols] float32 = float32(correctly rounded double), the bits
+ *                         np.loadtxt(dtype=float32) returns.  Fields are separated by runs of
+ *                         blanks or tabs, "\r\n" is accepted.  Served: tokens
+ *                         [+-]?(d+(.d*)?|.d+)([eE][+-]?d+)? whose digits after leading zeros are
+ *                         an integer <= 2^53 (at most 19 digits) and whose decimal exponent minus
+ *                         fraction digits lies in [-22, 22].  status [1] int64 = the first row
+ *                         with any other token or byte, no field (blank line) or a field count
+ *                         other than ncols, else -1; out is then not to be used.
+ *
+ * prh_pcd_unpack14: payload of n_points 14-byte records (x y z float32, intensity uint16, little
+ * endian, any alignment) -> out [n_points,4] float32. */
+int prh_pcd_group_rows(void);
+size_t prh_pcd_format_workspace_bytes(long long n_rows);
+int prh_pcd_format_count(const void* points, int is_fp64, long long n_rows, unsigned char* row_bytes,
+                         int* group_bytes, long long* status, void* workspace, size_t workspace_bytes, int device,
+                         void* stream);
+int prh_pcd_format_write(const void* points, int is_fp64, long long n_rows, const unsigned char* row_bytes,
+                         const long long* group_offsets, const long long* offsets, int n_slices,
+                         unsigned char* text, long long capacity, long long* byte_offsets, int device,
+                         void* stream);
+long long prh_pcd_index_blocks(const void* payload, long long n_bytes);
+int prh_pcd_index_count(const unsigned char* payload, long long n_bytes, int* block_lines, int device,
+                        void* stream);
+int prh_pcd_index_write(const unsigned char* payload, long long n_bytes, const long long* block_offsets,
+                        long long* row_start, long long n_rows, int device, void* stream);
+size_t prh_pcd_parse_workspace_bytes(long long n_rows);
+int prh_pcd_parse(const unsigned char* payload, long long n_bytes, const long long* row_start, long long n_rows,
+                  int ncols, float* out, long long* status, void* workspace, size_t workspace_bytes, int device,
+                  void* stream);
+int prh_pcd_unpack14(const unsigned char* payload, long long n_points, float* out, int device, void* stream);
+
 /* ---- prediction scenes (tools/generate_inference_data_vma.py of the reference) ---------------
  * Per camera frame: GT polylines clipped into the ego frame by that tool's rule, a (prediction x
  * GT) matrix of one-way xy Chamfer costs, and the minimum-cost assignment.  fp64 throughout, no

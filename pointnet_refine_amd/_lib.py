@@ -85,6 +85,9 @@ EXPORTS = [
     "prh_bev_bounds_workspace_bytes", "prh_bev_bounds", "prh_bev_raster", "prh_bev_select_workspace_bytes",
     "prh_bev_select", "prh_bev_tone", "prh_bev_colorize", "prh_bev_crop", "prh_bev_tile", "prh_bev_draw_count",
     "prh_bev_draw_workspace_bytes", "prh_bev_draw",
+    "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
+    "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
+    "prh_pcd_parse", "prh_pcd_unpack14",
     "prh_l1_loss_workspace_bytes", "prh_l1_loss", "prh_adam_step",
     "prh_add_dropout_layernorm_forward", "prh_add_dropout_layernorm_workspace_bytes",
     "prh_add_dropout_layernorm_backward",
@@ -275,6 +278,26 @@ def _bind(lib):
     lib.prh_bev_draw_workspace_bytes.argtypes = [ll, ll]
     lib.prh_bev_draw.restype = i
     lib.prh_bev_draw.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, ll, ll, vp, vp, sz, i, vp]
+    lib.prh_pcd_group_rows.restype = i
+    lib.prh_pcd_group_rows.argtypes = []
+    lib.prh_pcd_format_workspace_bytes.restype = sz
+    lib.prh_pcd_format_workspace_bytes.argtypes = [ll]
+    lib.prh_pcd_format_count.restype = i
+    lib.prh_pcd_format_count.argtypes = [vp, i, ll, vp, vp, vp, vp, sz, i, vp]
+    lib.prh_pcd_format_write.restype = i
+    lib.prh_pcd_format_write.argtypes = [vp, i, ll, vp, vp, vp, i, vp, ll, vp, i, vp]
+    lib.prh_pcd_index_blocks.restype = ll
+    lib.prh_pcd_index_blocks.argtypes = [vp, ll]
+    lib.prh_pcd_index_count.restype = i
+    lib.prh_pcd_index_count.argtypes = [vp, ll, vp, i, vp]
+    lib.prh_pcd_index_write.restype = i
+    lib.prh_pcd_index_write.argtypes = [vp, ll, vp, vp, ll, i, vp]
+    lib.prh_pcd_parse_workspace_bytes.restype = sz
+    lib.prh_pcd_parse_workspace_bytes.argtypes = [ll]
+    lib.prh_pcd_parse.restype = i
+    lib.prh_pcd_parse.argtypes = [vp, ll, vp, ll, i, vp, vp, vp, sz, i, vp]
+    lib.prh_pcd_unpack14.restype = i
+    lib.prh_pcd_unpack14.argtypes = [vp, ll, vp, i, vp]
     lib.prh_add_dropout_layernorm_forward.restype = i
     lib.prh_add_dropout_layernorm_forward.argtypes = [vp, vp, vp, vp, lg, i, f, f, C.c_uint, vp, vp, vp, i, vp]
     lib.prh_add_dropout_layernorm_workspace_bytes.restype = C.c_size_t

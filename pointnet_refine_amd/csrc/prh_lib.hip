@@ -28,6 +28,7 @@
 #include "prh_drive.hpp"
 #include "prh_match.hpp"
 #include "prh_bev.hpp"
+#include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
 using namespace prh;
@@ -2432,6 +2433,135 @@ int prh_drive_noise(const double* lines, const long long* line_offsets, const in
     hipLaunchKernelGGL((drv_noise_kernel<false>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, vertex_line,
                        n_verts, n_lines, line_ids, sc, n_scales, (uint64_t)seed, (const double*)centroid, draws_u,
                        draws_j, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ PCD text codec
+int prh_pcd_group_rows(void) { return PCD_GROUP; }
+size_t prh_pcd_format_workspace_bytes(long long n_rows) {
+  if (n_rows < 0) return 0;
+  return align_up((size_t)((n_rows + PCD_GROUP - 1) / PCD_GROUP) * sizeof(long long), 256) + 256;
+}
+int prh_pcd_format_count(const void* points, int is_fp64, long long n_rows, unsigned char* row_bytes,
+                         int* group_bytes, long long* status, void* workspace, size_t workspace_bytes, int device,
+                         void* stream) {
+  if (n_rows < 0 || !status || (n_rows > 0 && (!points || !row_bytes || !group_bytes)))
+    return fail(PRH_ERR_ARG, "pcd_format_count: bad argument");
+  const long long G = (n_rows + PCD_GROUP - 1) / PCD_GROUP;
+  if (G > 4ll * 0x7fffffff) return fail(PRH_ERR_ARG, "pcd_format_count: too many rows");
+  if (n_rows > 0 && (!workspace || workspace_bytes < prh_pcd_format_workspace_bytes(n_rows)))
+    return fail(PRH_ERR_WORKSPACE, "pcd_format_count: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  long long* bad = (long long*)workspace;
+  if (n_rows > 0) {
+    const unsigned nblk = (unsigned)((G + 3) / 4);
+    if (is_fp64)
+      hipLaunchKernelGGL((pcd_format_kernel<double, false>), dim3(nblk), dim3(256), 0, st, (const double*)points,
+                         n_rows, row_bytes, group_bytes, bad, (const long long*)nullptr, (unsigned char*)nullptr, 0ll);
+    else
+      hipLaunchKernelGGL((pcd_format_kernel<float, false>), dim3(nblk), dim3(256), 0, st, (const float*)points,
+                         n_rows, row_bytes, group_bytes, bad, (const long long*)nullptr, (unsigned char*)nullptr, 0ll);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(pcd_first_kernel, dim3(1), dim3(256), 0, st, (const long long*)bad, G, status);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_pcd_format_write(const void* points, int is_fp64, long long n_rows, const unsigned char* row_bytes,
+                         const long long* group_offsets, const long long* offsets, int n_slices,
+                         unsigned char* text, long long capacity, long long* byte_offsets, int device,
+                         void* stream) {
+  if (n_rows < 0 || n_slices < 0 || capacity < 0 || !byte_offsets ||
+      (n_rows > 0 && (!points || !row_bytes || !group_offsets)) || (capacity > 0 && !text))
+    return fail(PRH_ERR_ARG, "pcd_format_write: bad argument");
+  const long long G = (n_rows + PCD_GROUP - 1) / PCD_GROUP;
+  if (G > 4ll * 0x7fffffff) return fail(PRH_ERR_ARG, "pcd_format_write: too many rows");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  const int S = offsets ? n_slices : 1;
+  hipLaunchKernelGGL(pcd_slice_bytes_kernel, dim3(cdiv(S + 1, 256)), dim3(256), 0, st, offsets, S, n_rows, row_bytes,
+                     group_offsets, byte_offsets);
+  LAUNCH_CHECK();
+  if (n_rows == 0 || capacity == 0) return PRH_OK;
+  const unsigned nblk = (unsigned)((G + 3) / 4);
+  if (is_fp64)
+    hipLaunchKernelGGL((pcd_format_kernel<double, true>), dim3(nblk), dim3(256), 0, st, (const double*)points, n_rows,
+                       (unsigned char*)nullptr, (int*)nullptr, (long long*)nullptr, group_offsets, text, capacity);
+  else
+    hipLaunchKernelGGL((pcd_format_kernel<float, true>), dim3(nblk), dim3(256), 0, st, (const float*)points, n_rows,
+                       (unsigned char*)nullptr, (int*)nullptr, (long long*)nullptr, group_offsets, text, capacity);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+long long prh_pcd_index_blocks(const void* payload, long long n_bytes) {
+  if (n_bytes <= 0) return 0;
+  return (((long long)((uintptr_t)payload & 15)) + n_bytes + PCD_BLOCK_BYTES - 1) / PCD_BLOCK_BYTES;
+}
+int prh_pcd_index_count(const unsigned char* payload, long long n_bytes, int* block_lines, int device,
+                        void* stream) {
+  if (n_bytes < 0 || (n_bytes > 0 && (!payload || !block_lines)))
+    return fail(PRH_ERR_ARG, "pcd_index_count: bad argument");
+  const long long nb = prh_pcd_index_blocks(payload, n_bytes);
+  if (nb > 0x7fffffffll) return fail(PRH_ERR_ARG, "pcd_index_count: payload too large");
+  if (nb == 0) return PRH_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL((pcd_lines_kernel<false>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, payload, n_bytes,
+                     block_lines, (const long long*)nullptr, (long long*)nullptr, 0ll);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_pcd_index_write(const unsigned char* payload, long long n_bytes, const long long* block_offsets,
+                        long long* row_start, long long n_rows, int device, void* stream) {
+  if (n_bytes < 0 || n_rows < 0 || !row_start || (n_bytes > 0 && (!payload || !block_offsets)))
+    return fail(PRH_ERR_ARG, "pcd_index_write: bad argument");
+  const long long nb = prh_pcd_index_blocks(payload, n_bytes);
+  if (nb > 0x7fffffffll) return fail(PRH_ERR_ARG, "pcd_index_write: payload too large");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  if (nb == 0) {
+    HIP_TRY(hipMemsetAsync(row_start, 0, (size_t)(n_rows + 1) * sizeof(long long), st));
+    return PRH_OK;
+  }
+  hipLaunchKernelGGL((pcd_lines_kernel<true>), dim3((unsigned)nb), dim3(256), 0, st, payload, n_bytes, (int*)nullptr,
+                     block_offsets, row_start, n_rows);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+size_t prh_pcd_parse_workspace_bytes(long long n_rows) {
+  if (n_rows < 0) return 0;
+  return align_up((size_t)((n_rows + 255) / 256) * sizeof(long long), 256) + 256;
+}
+int prh_pcd_parse(const unsigned char* payload, long long n_bytes, const long long* row_start, long long n_rows,
+                  int ncols, float* out, long long* status, void* workspace, size_t workspace_bytes, int device,
+                  void* stream) {
+  if (n_bytes < 0 || n_rows < 0 || ncols < 1 || !status || (n_rows > 0 && (!payload || !row_start || !out)))
+    return fail(PRH_ERR_ARG, "pcd_parse: bad argument");
+  const long long nb = (n_rows + 255) / 256;
+  if (nb > 0x7fffffffll) return fail(PRH_ERR_ARG, "pcd_parse: too many rows");
+  if (n_rows > 0 && (!workspace || workspace_bytes < prh_pcd_parse_workspace_bytes(n_rows)))
+    return fail(PRH_ERR_WORKSPACE, "pcd_parse: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  long long* bad = (long long*)workspace;
+  if (n_rows > 0) {
+    hipLaunchKernelGGL(pcd_parse_kernel, dim3((unsigned)nb), dim3(256), 0, st, payload, row_start, n_rows, ncols, out,
+                       bad);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(pcd_first_kernel, dim3(1), dim3(256), 0, st, (const long long*)bad, nb, status);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_pcd_unpack14(const unsigned char* payload, long long n_points, float* out, int device, void* stream) {
+  if (n_points < 0 || (n_points > 0 && (!payload || !out))) return fail(PRH_ERR_ARG, "pcd_unpack14: bad argument");
+  const long long nb = (n_points + PCD_UNPACK_POINTS - 1) / PCD_UNPACK_POINTS;
+  if (nb > 0x7fffffffll) return fail(PRH_ERR_ARG, "pcd_unpack14: too many points");
+  if (nb == 0) return PRH_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(pcd_unpack14_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, payload, n_points,
+                     (float4*)out);
   LAUNCH_CHECK();
   return PRH_OK;
 }

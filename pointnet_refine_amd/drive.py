@@ -12,6 +12,7 @@ slice; here every slice of a drive comes out of two HIP passes over the cloud
   apply_noise                HIP: the deterministic half of generate_noisy_line (augment :18-54)
   noisy_candidates           HIP: the same with the draws from a counter hash, fresh per seed
   write_scene / slice_drive  host: the reference's two files (:184-209) and the whole pipeline
+                             (slice_drive's .pcd text is formatted on the device: pcd.write_pcds)
 
     res = slice_drive("DRIVE_annotation_raw_data", "DRIVE.bag.json", "train_data")
     stream = SceneSampleStream("train_data", augment=(0.1, 0.25, 0.4), batch_size=32)
@@ -107,6 +108,20 @@ def load_gt_items(json_path):
 
 def _xyz_dicts(points):
     return [{"x": float(p[0]), "y": float(p[1]), "z": float(p[2])} for p in points]
+
+
+def _write_scene_json(json_path, items, ref_ts):
+    """write_scene's JSON file on its own (slice_drive writes the .pcd files through pcd.write_pcds).
+    Keep identical to the JSON half of write_scene below; tests/test_pcd_gpu.py
+    (test_slice_drive_files_equal_write_scene) compares the two byte for byte."""
+    output = {"timestamp": ref_ts, "items": []}
+    for item in items:
+        entry = {"category": item["category"], "attributes": item["attributes"], "position": _xyz_dicts(item["points"])}
+        if "noisy_candidates" in item:
+            entry["noisy_candidates"] = [_xyz_dicts(c) for c in item["noisy_candidates"]]
+        output["items"].append(entry)
+    with open(json_path, "w") as f:
+        json.dump(output, f, indent=4)
 
 
 def write_scene(pcd_path, json_path, points, items, ref_ts):
@@ -322,6 +337,7 @@ def slice_drive(drive_dir, gt_json, out_dir=None, candidates=False, noise_scales
     'points' (T,4) CUDA, 'offsets', 'source_index', 'items' [per slice list of item dicts],
     'written' [names]}."""
     from .io import load_pcd_data
+    from .pcd import write_pcds
     poses = load_poses(os.path.join(drive_dir, "pose"))
     res = {"pose_index": [], "names": [], "points": None, "offsets": None, "source_index": None, "items": [],
            "written": []}
@@ -347,7 +363,7 @@ def slice_drive(drive_dir, gt_json, out_dir=None, candidates=False, noise_scales
                source_index=index)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
-    pts_host = points.cpu().numpy() if out_dir is not None else None
+    pcd_paths = [None] * len(res["names"])
     for s, name in enumerate(res["names"]):
         items = [{"category": gt_items[l]["category"], "points": v, "attributes": gt_items[l]["attributes"]}
                  for l, v in clipped[s]]
@@ -357,9 +373,11 @@ def slice_drive(drive_dir, gt_json, out_dir=None, candidates=False, noise_scales
                 it["noisy_candidates"] = c
         res["items"].append(items)
         if out_dir is not None and off[s + 1] > off[s]:
-            write_scene(os.path.join(out_dir, f"{name}.pcd"), os.path.join(out_dir, f"{name}.json"),
-                        pts_host[off[s]:off[s + 1]], items, name)
+            pcd_paths[s] = os.path.join(out_dir, f"{name}.pcd")
+            _write_scene_json(os.path.join(out_dir, f"{name}.json"), items, name)
             res["written"].append(name)
+    if out_dir is not None:
+        write_pcds(pcd_paths, points, off)              # the text of every slice from one device pass
     if verbose:
         print(f"  Generated {len(res['written']) if out_dir is not None else int((np.diff(off) > 0).sum())} samples.")
     return res

@@ -231,7 +231,11 @@ class SceneSampleStream:
     def _scene_samples(self, si, pairs):
         from .context import resample_polyline
         pcd_path, json_path, _ = self.scenes[si]
-        cloud = torch.from_numpy(np.atleast_2d(load_pcd_data(pcd_path))[:, :4].astype(np.float32, copy=False))
+        if self.device.type == "cuda":
+            from .pcd import read_pcd                    # parsed on the device: same values, bit for bit
+            cloud = read_pcd(pcd_path, device=self.device)[:, :4]
+        else:
+            cloud = torch.from_numpy(np.atleast_2d(load_pcd_data(pcd_path))[:, :4].astype(np.float32, copy=False))
         cloud = cloud.to(self.device, torch.float32).contiguous()
         items = load_scene_items(json_path)
         if self.augment is None:

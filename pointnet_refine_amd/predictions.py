@@ -122,6 +122,14 @@ def write_prediction_scene(pcd_path, json_path, points, items, pose_ts, result_t
         json.dump({"timestamp": str(pose_ts), "result_timestamp": str(result_ts), "items": items}, f, indent=4)
 
 
+def _write_prediction_json(json_path, items, pose_ts, result_ts):
+    """write_prediction_scene's JSON file on its own (the .pcd files go through pcd.write_pcds).
+    Keep identical to the JSON half of write_prediction_scene above; tests/test_pcd_gpu.py
+    (test_predictions_to_scenes_files_equal_write_prediction_scene) compares the two byte for byte."""
+    with open(json_path, "w") as f:
+        json.dump({"timestamp": str(pose_ts), "result_timestamp": str(result_ts), "items": items}, f, indent=4)
+
+
 # ------------------------------------------------------------------ GPU side
 def _device():
     if not torch.cuda.is_available():
@@ -314,6 +322,7 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
     'items' [per frame list of item dicts, [] for a skipped frame], 'matches', 'costs', 'gt_index'
     [per frame the GT item of each context line], 'written' [result ts]}."""
     from .io import load_pcd_data
+    from .pcd import write_pcds
     _device()
     poses = load_frame_poses(os.path.join(drive_dir, "pose"))
     res = {"frames": [], "pose_index": [], "pose_ts": [], "points": None, "offsets": None, "slice": [], "items": [],
@@ -334,7 +343,7 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
     preds = [[pixel_to_ego(px) for px in frames[n]["pixels"]] for n in with_pose]
     matched = match_predictions(preds, [[v for _, v in c] for c in clipped], threshold)
     off = offsets.cpu().numpy()
-    pts_host = points.cpu().numpy() if out_dir is not None else None
+    pcd_paths = [None] * (len(off) - 1)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
     slot = {int(n): s for s, n in enumerate(with_pose)}
@@ -364,9 +373,11 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
                 print(f"  Skipping {fr['ts']}: " + ("no point in the slice" if off[s + 1] == off[s] else
                                                     "No predictions found in JSON."))
         elif out_dir is not None:
-            write_prediction_scene(os.path.join(out_dir, f"{fr['ts']}.pcd"), os.path.join(out_dir, f"{fr['ts']}.json"),
-                                   pts_host[off[s]:off[s + 1]], items, poses[chosen[n]]["ts"], fr["ts"])
+            pcd_paths[s] = os.path.join(out_dir, f"{fr['ts']}.pcd")
+            _write_prediction_json(os.path.join(out_dir, f"{fr['ts']}.json"), items, poses[chosen[n]]["ts"], fr["ts"])
             res["written"].append(fr["ts"])
+    if out_dir is not None:
+        write_pcds(pcd_paths, points, off)              # the text of every frame's slice from one device pass
     res.update(points=points, offsets=offsets)
     if verbose:
         kept = len(res["written"]) if out_dir is not None else sum(1 for it in res["items"] if it)
