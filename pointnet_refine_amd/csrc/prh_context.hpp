@@ -34,8 +34,9 @@ __device__ __forceinline__ uint64_t ctx_mix(uint64_t x) {      // splitmix64 fin
 __device__ __forceinline__ uint64_t ctx_hash(uint64_t seed, unsigned line, unsigned idx) {
   return ctx_mix(ctx_mix(seed ^ ((uint64_t)line << 32 | idx)));
 }
-// uniform in (0,1), 24 bits
-__device__ __forceinline__ float ctx_u01(uint64_t h) { return ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f); }
+// uniform strictly inside (0,1), 23 bits: (k + 0.5) / 2^23 is exact in fp32 for every k < 2^23
+// (24 bits would need 25 significant bits from 2^23 on and round the top value to 1.0f, G = +inf)
+__device__ __forceinline__ float ctx_u01(uint64_t h) { return ((float)(h >> 41) + 0.5f) * (1.0f / 8388608.0f); }
 // order-preserving map float -> uint32
 __device__ __forceinline__ unsigned ctx_sortable(float f) {
   const unsigned u = __float_as_uint(f);

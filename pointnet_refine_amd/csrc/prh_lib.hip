@@ -2195,8 +2195,10 @@ int prh_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
 
 // ------------------------------------------------------------------ context builder (row f2)
 struct CtxWS { int* blkcnt; int* blkoff; int* cand; unsigned* keys; float* box; };
+// 256-point blocks of the crop passes: at least one, so that an empty cloud still has a count per line
+int ctx_nblk(int npts) { return cdiv(npts, 256) < 1 ? 1 : cdiv(npts, 256); }
 void ctx_carve(Arena& a, CtxWS& w, int npts, int L, int max_cand) {
-  const size_t nblk = (size_t)cdiv(npts, 256);
+  const size_t nblk = (size_t)ctx_nblk(npts);
   w.blkcnt = (int*)a.f(nblk * L);
   w.blkoff = (int*)a.f(nblk * L);
   w.cand = (int*)a.f((size_t)L * max_cand);
@@ -2228,7 +2230,7 @@ int prh_context_build(const float* cloud, int npts, const float* dense, int n_de
   CtxWS w;
   ctx_carve(a, w, npts, n_lines, max_candidates);
   if (!a.ok) return fail(PRH_ERR_WORKSPACE, "context_build: workspace too small (%zu bytes)", workspace_bytes);
-  const int nblk = cdiv(npts, 256) < 1 ? 1 : cdiv(npts, 256);
+  const int nblk = ctx_nblk(npts);
   const float r2 = radius * radius;
   hipLaunchKernelGGL(ctx_bbox_kernel, dim3(n_lines), dim3(64), 0, st, dense, n_dense, radius, w.box);
   LAUNCH_CHECK();
