@@ -28,8 +28,8 @@ import zlib
 import numpy as np
 import torch
 
+from . import _gpu as G
 from . import _lib as L
-from .drive import _ptr, _stream, _ws
 
 RESOLUTION = 0.05            # vis_inference_bev.py:24
 PADDING = 5.0                # :74
@@ -149,22 +149,14 @@ class Views:
 
 
 # ------------------------------------------------------------------ GPU side
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("pointnet_refine_amd.bev needs a GPU (there is no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _points_t(points, dev, what):
-    if torch.is_tensor(points):
-        if not points.is_cuda:
-            raise RuntimeError(f"{what}: tensors must be CUDA tensors (there is no CPU fallback)")
-        p = points.detach()
-    else:
-        p = np.asarray(points)
-        if p.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what}: points must be float32 or float64, got {p.dtype}")
-        p = torch.from_numpy(np.ascontiguousarray(p[:, :4]) if p.ndim == 2 and p.shape[1] >= 4 else p).to(dev)
+    if not torch.is_tensor(points):
+        points = np.asarray(points)
+        if points.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{what}: points must be float32 or float64, got {points.dtype}")
+        if points.ndim == 2 and points.shape[1] >= 4:
+            points = points[:, :4]
+    p = G.as_cuda(points, dev, what)
     if p.dtype not in (torch.float32, torch.float64) or p.dim() != 2 or p.shape[1] < 4:
         raise ValueError(f"{what}: points must be (n, >=4) float32 or float64, got {tuple(p.shape)} {p.dtype}")
     return p[:, :4].contiguous()
@@ -186,10 +178,10 @@ def _geometry(T, bounds, padding, resolution):
 def _raster(p, offsets, n_slices, h, w, extent, resolution, dev, what):
     image = torch.empty((n_slices, h, w), dtype=torch.float32, device=dev)
     bad = torch.zeros((1,), dtype=torch.int32, device=dev)
-    L.check(L.lib().prh_bev_raster(_ptr(p), _ptr(offsets) if offsets is not None else None, n_slices, p.shape[0],
+    L.check(L.lib().prh_bev_raster(G.ptr(p), G.ptr(offsets) if offsets is not None else None, n_slices, p.shape[0],
                                    int(p.dtype == torch.float64), float(extent[0]), float(extent[3]),
                                    float((np.float64 if p.dtype == torch.float64 else np.float32)(resolution)),
-                                   h, w, _ptr(image), _ptr(bad), dev.index, _stream(dev)), "prh_bev_raster")
+                                   h, w, G.ptr(image), G.ptr(bad), dev.index, G.stream(dev)), "prh_bev_raster")
     if int(bad.item()):
         raise ValueError(f"{what}: a NaN or infinite x, y or intensity")
     return image
@@ -205,7 +197,7 @@ def bev_map(points, resolution=RESOLUTION, padding=PADDING, extent=None):
     when it has none.  extent=(y_min, y_max, x_min, x_max): the bounds are these, no padding.
     Returns (image (H, W) float32 CUDA, [y_min, y_max, x_min, x_max] scalars of the points' dtype).
     Bitwise reproducible.  ValueError for n = 0 and for a NaN or infinite x, y or intensity."""
-    dev = _device()
+    dev = G.device("bev")
     p = _points_t(points, dev, "bev_map")
     dev = p.device
     if p.shape[0] == 0:
@@ -214,10 +206,10 @@ def bev_map(points, resolution=RESOLUTION, padding=PADDING, extent=None):
     if extent is None:
         lib = L.lib()
         nb = lib.prh_bev_bounds_workspace_bytes()
-        ws = _ws(nb, dev)
+        ws = G.workspace(nb, dev)
         info = torch.empty((5,), dtype=torch.float64, device=dev)
-        L.check(lib.prh_bev_bounds(_ptr(p), p.shape[0], int(T is np.float64), _ptr(info), _ptr(ws), nb, dev.index,
-                                   _stream(dev)), "prh_bev_bounds")
+        L.check(lib.prh_bev_bounds(G.ptr(p), p.shape[0], int(T is np.float64), G.ptr(info), G.ptr(ws), nb, dev.index,
+                                   G.stream(dev)), "prh_bev_bounds")
         info = info.cpu().numpy()
         if info[4] != 0.0:
             raise ValueError("bev_map: a NaN or infinite x, y or intensity")
@@ -231,7 +223,7 @@ def bev_maps(points, offsets, extent, resolution=RESOLUTION):
     """bev_map(points[offsets[s]:offsets[s+1]], extent=extent) for every slice s of a CSR-packed
     cloud (what drive.slice_cloud returns) in one launch sequence: (S, H, W) float32 CUDA; an empty
     slice is all zero."""
-    dev = _device()
+    dev = G.device("bev")
     p = _points_t(points, dev, "bev_maps")
     dev = p.device
     off = (offsets.detach() if torch.is_tensor(offsets) else torch.from_numpy(np.asarray(offsets))).to(dev, torch.int64)
@@ -250,7 +242,7 @@ def _image_t(image, what):
             raise RuntimeError(f"{what} needs a GPU (there is no CPU fallback)")
         if torch.is_tensor(image):
             raise RuntimeError(f"{what}: tensors must be CUDA tensors (there is no CPU fallback)")
-        image = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(_device())
+        image = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(G.device("bev"))
     if image.dtype != torch.float32 or image.dim() not in (2, 3):
         raise ValueError(f"{what}: image must be (H, W) or (S, H, W) float32, got {tuple(image.shape)} {image.dtype}")
     return image.detach().contiguous()
@@ -274,10 +266,10 @@ def percentile_positive(image, percentile=90.0):
     pix = img.numel() // max(s, 1)
     lib = L.lib()
     nb = lib.prh_bev_select_workspace_bytes(s)
-    ws = _ws(nb, dev)
+    ws = G.workspace(nb, dev)
     out = torch.zeros((s, 4), dtype=torch.float64, device=dev)
-    L.check(lib.prh_bev_select(_ptr(img), s, pix, float(np.float32(percentile) / np.float32(100)), _ptr(out), _ptr(ws), nb, dev.index,
-                               _stream(dev)), "prh_bev_select")
+    L.check(lib.prh_bev_select(G.ptr(img), s, pix, float(np.float32(percentile) / np.float32(100)), G.ptr(out), G.ptr(ws), nb, dev.index,
+                               G.stream(dev)), "prh_bev_select")
     st = out.cpu().numpy()
     return [(_lerp(r[1], r[2], r[3]) if r[0] > 0 else None) for r in st], st
 
@@ -293,7 +285,7 @@ def tone_map(image, percentile=90.0, gamma=0.6):
     pix = img.numel() // max(s, 1)
     pt = torch.tensor([float(p) if p is not None else 0.0 for p in ps], dtype=torch.float32, device=dev)
     norm = torch.empty_like(img)
-    L.check(L.lib().prh_bev_tone(_ptr(img), s, pix, _ptr(pt), float(gamma), _ptr(norm), dev.index, _stream(dev)),
+    L.check(L.lib().prh_bev_tone(G.ptr(img), s, pix, G.ptr(pt), float(gamma), G.ptr(norm), dev.index, G.stream(dev)),
             "prh_bev_tone")
     return (norm, ps[0]) if img.dim() == 2 else (norm, ps)
 
@@ -310,8 +302,8 @@ def colorize(norm, image, cmap="jet"):
     dev = nrm.device
     table = torch.from_numpy((jet_table() if cmap == "jet" else gray_table()).view(np.uint32).reshape(-1).view(np.int32)).to(dev)
     out = torch.empty(tuple(nrm.shape) + (4,), dtype=torch.uint8, device=dev)
-    L.check(L.lib().prh_bev_colorize(_ptr(nrm), _ptr(img), nrm.numel(), _ptr(table), _ptr(out), dev.index,
-                                     _stream(dev)), "prh_bev_colorize")
+    L.check(L.lib().prh_bev_colorize(G.ptr(nrm), G.ptr(img), nrm.numel(), G.ptr(table), G.ptr(out), dev.index,
+                                     G.stream(dev)), "prh_bev_colorize")
     return out
 
 
@@ -346,8 +338,8 @@ def crop_views(rgba, extent, windows, resolution=RESOLUTION):
     if len(win):
         vt = torch.from_numpy(np.stack([u0, v0, h, w], 1).astype(np.int32)).to(dev)
         ot = torch.from_numpy(off).to(dev)
-        L.check(L.lib().prh_bev_crop(_ptr(src), src.shape[0], src.shape[1], _ptr(vt), _ptr(ot), len(win), int(off[-1]),
-                                     _ptr(data), dev.index, _stream(dev)), "prh_bev_crop")
+        L.check(L.lib().prh_bev_crop(G.ptr(src), src.shape[0], src.shape[1], G.ptr(vt), G.ptr(ot), len(win), int(off[-1]),
+                                     G.ptr(data), dev.index, G.stream(dev)), "prh_bev_crop")
     return Views(data, off, np.stack([h, w], 1).astype(np.int64).reshape(-1, 2), snapped.reshape(-1, 4), res)
 
 
@@ -435,18 +427,17 @@ def draw_lines(canvas, window, lines, line_view, styles, resolution=None):
     segs_t, seg_line_t, st_t, lv_t, dims_t, base_t, off_t, tv_t = (up(a) for a in (segs, seg_line, st, lv, dims, base[:-1],
                                                                                    off, tile_view))
     counts = torch.empty((n_tiles,), dtype=torch.int32, device=dev)
-    L.check(lib.prh_bev_draw_count(_ptr(segs_t), _ptr(seg_line_t), len(segs), _ptr(st_t), _ptr(lv_t), _ptr(dims_t),
-                                   _ptr(base_t), n_tiles, _ptr(counts), dev.index, _stream(dev)), "prh_bev_draw_count")
-    tile_off = torch.zeros((n_tiles + 1,), dtype=torch.int64, device=dev)
-    tile_off[1:] = torch.cumsum(counts, 0)
+    L.check(lib.prh_bev_draw_count(G.ptr(segs_t), G.ptr(seg_line_t), len(segs), G.ptr(st_t), G.ptr(lv_t), G.ptr(dims_t),
+                                   G.ptr(base_t), n_tiles, G.ptr(counts), dev.index, G.stream(dev)), "prh_bev_draw_count")
+    tile_off = G.exclusive_scan(counts)
     n_items = int(tile_off[-1].item())
     if n_items == 0:
         return canvas
     nb = lib.prh_bev_draw_workspace_bytes(n_tiles, n_items)
-    ws = _ws(nb, dev)
-    L.check(lib.prh_bev_draw(_ptr(segs_t), _ptr(seg_line_t), len(segs), _ptr(st_t), _ptr(lv_t), _ptr(dims_t), _ptr(base_t),
-                             _ptr(off_t), _ptr(tv_t), _ptr(tile_off), n_tiles, n_items, _ptr(data), _ptr(ws), nb,
-                             dev.index, _stream(dev)), "prh_bev_draw")
+    ws = G.workspace(nb, dev)
+    L.check(lib.prh_bev_draw(G.ptr(segs_t), G.ptr(seg_line_t), len(segs), G.ptr(st_t), G.ptr(lv_t), G.ptr(dims_t), G.ptr(base_t),
+                             G.ptr(off_t), G.ptr(tv_t), G.ptr(tile_off), n_tiles, n_items, G.ptr(data), G.ptr(ws), nb,
+                             dev.index, G.stream(dev)), "prh_bev_draw")
     return canvas
 
 
@@ -457,7 +448,7 @@ def chamfer_xy(gt_lines, pred_lines):
     from .predictions import line_costs
     if len(gt_lines) != len(pred_lines):
         raise ValueError("chamfer_xy: one prediction per GT line")
-    _device()
+    G.device("bev")
     out = np.full(len(gt_lines), -1.0)
     idx = [i for i, g in enumerate(gt_lines) if g is not None and len(g) > 0]
     if idx:

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _gpu as G
 from . import _lib as L
 
 DENSE_POINTS = 200          # src/dataset.py:214: tube continuity needs ~0.25 m spacing
@@ -100,16 +101,15 @@ def build_contexts_resampled(cloud, dense, line, num_context_points=1024, crop_r
         weights = torch.zeros((0, max_candidates), dtype=torch.float32, device=dev) if return_weights else None
         return (out, counts, weights) if return_weights else (out, counts)
     lib = L.lib()
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
+    p = G.ptr
     while True:
         weights = torch.zeros((n_lines, max_candidates), dtype=torch.float32, device=dev) if return_weights else None
         nb = lib.prh_context_workspace_bytes(npts, n_lines, max_candidates)
-        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ws = G.workspace(nb, dev)
         L.check(lib.prh_context_build(p(cloud), npts, p(dense), dense.shape[1], p(line), line.shape[1], n_lines,
                                       float(crop_radius), float(decay_scale), n, max_candidates,
                                       C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), p(out), p(counts), p(weights),
-                                      p(ws), nb, dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                "prh_context_build")
+                                      p(ws), nb, dev.index, G.stream(dev)), "prh_context_build")
         largest = int(counts.max().item())           # one small read-back per scene
         if largest <= max_candidates:
             break

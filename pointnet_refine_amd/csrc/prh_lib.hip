@@ -1209,12 +1209,8 @@ int prh_pos_hidden_backward(const float* xyz, long ld, const float* h, const flo
   float* part = a.f((size_t)nb * 4 * hidden);
   if (!a.ok) return fail(PRH_ERR_WORKSPACE, "pos_hidden_backward: workspace too small (%zu bytes)", workspace_bytes);
   hipStream_t st = (hipStream_t)stream;
-  if (dxyz != nullptr)
-    hipLaunchKernelGGL(pos_hidden_bwd_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, xyz, ld, h, dh, part,
-                       rows, hidden, w0, dxyz);
-  else
-    hipLaunchKernelGGL(pos_hidden_bwd_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, xyz, ld, h, dh, part,
-                       rows, hidden, w0, dxyz);
+  hipLaunchKernelGGL(dxyz != nullptr ? pos_hidden_bwd_kernel<true> : pos_hidden_bwd_kernel<false>, dim3((unsigned)nb),
+                     dim3(256), 0, st, xyz, ld, h, dh, part, rows, hidden, w0, dxyz);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(pos_hidden_final_kernel, dim3((unsigned)cdiv(4 * hidden, 16)), dim3(256), 0, st,
                      (const float*)part, nb, hidden, dw0, db0);
@@ -2156,12 +2152,8 @@ int prh_l1_loss(const float* pred, const float* target, int n_layers, long elems
   long blocks = cdiv(elems, 256L);
   blocks = blocks > L1_BLOCKS ? L1_BLOCKS : blocks;
   const float inv = (float)(1.0 / denom);
-  if (geometry != nullptr)
-    hipLaunchKernelGGL(l1_deep_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, pred, target, n_layers,
-                       elems, inv, d_pred, part);
-  else
-    hipLaunchKernelGGL(l1_deep_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pred, target, n_layers,
-                       elems, inv, d_pred, part);
+  hipLaunchKernelGGL(geometry != nullptr ? l1_deep_kernel<true> : l1_deep_kernel<false>, dim3((unsigned)blocks),
+                     dim3(256), 0, st, pred, target, n_layers, elems, inv, d_pred, part);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)blocks, inv, accumulate, loss);
   LAUNCH_CHECK();
@@ -2364,15 +2356,21 @@ size_t prh_drive_clip_workspace_bytes(int n_slices) {
   if (n_slices < 0) return 0;
   return align_up((size_t)n_slices * sizeof(DrvPose), 256) + 256;
 }
-static int drv_clip(bool write, const double* lines, const long long* line_offsets, int n_lines, const double* poses,
-                    int S, double segment_len, int* counts, const long long* out_offsets, double* out,
-                    void* workspace, size_t workspace_bytes, int device, void* stream) {
-  const char* what = write ? "drive_clip_write" : "drive_clip_count";
+// The two-pass polyline clip of the slicer and of the prediction scenes: one thread per (pose, line),
+// a count call and a write call over the same workspace.  kernel is the <WRITE> instantiation of the
+// tool's own rule (drv_clip_kernel, mt_clip_kernel), what the entry point's name, unit its word for a pose.
+using ClipKernel = void (*)(const double*, const long long*, int, const DrvPose*, int, double, int*,
+                            const long long*, double*);
+static int clip_lines(ClipKernel kernel, bool write, const char* what, const char* unit, const double* lines,
+                      const long long* line_offsets, int n_lines, const double* poses, int S, double segment_len,
+                      int* counts, const long long* out_offsets, double* out, void* workspace,
+                      size_t workspace_bytes, int device, void* stream) {
   if (n_lines < 0 || S < 0 || !(segment_len >= 0.0)) return fail(PRH_ERR_ARG, "%s: bad argument", what);
   if (n_lines == 0 || S == 0) return PRH_OK;
   if (!lines || !line_offsets || !poses || (write ? (!out_offsets || !out) : !counts))
     return fail(PRH_ERR_ARG, "%s: null pointer", what);
-  if ((long long)S * n_lines > 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "%s: too many (slice, line) pairs", what);
+  if ((long long)S * n_lines > 256ll * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "%s: too many (%s, line) pairs", what, unit);
   if (!workspace || workspace_bytes < prh_drive_clip_workspace_bytes(S))
     return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
   HIP_TRY(hipSetDevice(device));
@@ -2380,27 +2378,22 @@ static int drv_clip(bool write, const double* lines, const long long* line_offse
   DrvPose* pose = (DrvPose*)workspace;
   hipLaunchKernelGGL(drv_pose_kernel, dim3(cdiv(S, 256)), dim3(256), 0, st, poses, S, pose);
   LAUNCH_CHECK();
-  const int nblk = cdiv((long)S * n_lines, 256);
-  if (write)
-    hipLaunchKernelGGL((drv_clip_kernel<true>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, n_lines,
-                       (const DrvPose*)pose, S, segment_len / 2, (int*)nullptr, out_offsets, out);
-  else
-    hipLaunchKernelGGL((drv_clip_kernel<false>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, n_lines,
-                       (const DrvPose*)pose, S, segment_len / 2, counts, (const long long*)nullptr, (double*)nullptr);
+  hipLaunchKernelGGL(kernel, dim3(cdiv((long)S * n_lines, 256)), dim3(256), 0, st, lines, line_offsets, n_lines,
+                     (const DrvPose*)pose, S, segment_len / 2, counts, out_offsets, out);
   LAUNCH_CHECK();
   return PRH_OK;
 }
 int prh_drive_clip_count(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
                          int n_slices, double segment_len, int* counts, void* workspace, size_t workspace_bytes,
                          int device, void* stream) {
-  return drv_clip(false, lines, line_offsets, n_lines, poses, n_slices, segment_len, counts, nullptr, nullptr,
-                  workspace, workspace_bytes, device, stream);
+  return clip_lines(drv_clip_kernel<false>, false, "drive_clip_count", "slice", lines, line_offsets, n_lines, poses,
+                    n_slices, segment_len, counts, nullptr, nullptr, workspace, workspace_bytes, device, stream);
 }
 int prh_drive_clip_write(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
                          int n_slices, double segment_len, const long long* out_offsets, double* out,
                          void* workspace, size_t workspace_bytes, int device, void* stream) {
-  return drv_clip(true, lines, line_offsets, n_lines, poses, n_slices, segment_len, nullptr, out_offsets, out,
-                  workspace, workspace_bytes, device, stream);
+  return clip_lines(drv_clip_kernel<true>, true, "drive_clip_write", "slice", lines, line_offsets, n_lines, poses,
+                    n_slices, segment_len, nullptr, out_offsets, out, workspace, workspace_bytes, device, stream);
 }
 size_t prh_drive_noise_workspace_bytes(int n_lines) {
   if (n_lines < 0) return 0;
@@ -2427,14 +2420,9 @@ int prh_drive_noise(const double* lines, const long long* line_offsets, const in
                      n_lines, centroid);
   LAUNCH_CHECK();
   const int nblk = cdiv(n_verts * n_scales, 256);
-  if (draw)
-    hipLaunchKernelGGL((drv_noise_kernel<true>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, vertex_line,
-                       n_verts, n_lines, line_ids, sc, n_scales, (uint64_t)seed, (const double*)centroid, draws_u,
-                       draws_j, out);
-  else
-    hipLaunchKernelGGL((drv_noise_kernel<false>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, vertex_line,
-                       n_verts, n_lines, line_ids, sc, n_scales, (uint64_t)seed, (const double*)centroid, draws_u,
-                       draws_j, out);
+  hipLaunchKernelGGL(draw ? drv_noise_kernel<true> : drv_noise_kernel<false>, dim3(nblk), dim3(256), 0, st, lines,
+                     line_offsets, vertex_line, n_verts, n_lines, line_ids, sc, n_scales, (uint64_t)seed,
+                     (const double*)centroid, draws_u, draws_j, out);
   LAUNCH_CHECK();
   return PRH_OK;
 }
@@ -2570,43 +2558,17 @@ int prh_pcd_unpack14(const unsigned char* payload, long long n_points, float* ou
 
 // ------------------------------------------------------------------ prediction scenes
 size_t prh_match_clip_workspace_bytes(int n_frames) { return prh_drive_clip_workspace_bytes(n_frames); }
-static int mt_clip(bool write, const double* lines, const long long* line_offsets, int n_lines, const double* poses,
-                   int F, double segment_len, int* counts, const long long* out_offsets, double* out,
-                   void* workspace, size_t workspace_bytes, int device, void* stream) {
-  const char* what = write ? "match_clip_write" : "match_clip_count";
-  if (n_lines < 0 || F < 0 || !(segment_len >= 0.0)) return fail(PRH_ERR_ARG, "%s: bad argument", what);
-  if (n_lines == 0 || F == 0) return PRH_OK;
-  if (!lines || !line_offsets || !poses || (write ? (!out_offsets || !out) : !counts))
-    return fail(PRH_ERR_ARG, "%s: null pointer", what);
-  if ((long long)F * n_lines > 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "%s: too many (frame, line) pairs", what);
-  if (!workspace || workspace_bytes < prh_match_clip_workspace_bytes(F))
-    return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  DrvPose* pose = (DrvPose*)workspace;
-  hipLaunchKernelGGL(drv_pose_kernel, dim3(cdiv(F, 256)), dim3(256), 0, st, poses, F, pose);
-  LAUNCH_CHECK();
-  const int nblk = cdiv((long)F * n_lines, 256);
-  if (write)
-    hipLaunchKernelGGL((mt_clip_kernel<true>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, n_lines,
-                       (const DrvPose*)pose, F, segment_len / 2, (int*)nullptr, out_offsets, out);
-  else
-    hipLaunchKernelGGL((mt_clip_kernel<false>), dim3(nblk), dim3(256), 0, st, lines, line_offsets, n_lines,
-                       (const DrvPose*)pose, F, segment_len / 2, counts, (const long long*)nullptr, (double*)nullptr);
-  LAUNCH_CHECK();
-  return PRH_OK;
-}
 int prh_match_clip_count(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
                          int n_frames, double segment_len, int* counts, void* workspace, size_t workspace_bytes,
                          int device, void* stream) {
-  return mt_clip(false, lines, line_offsets, n_lines, poses, n_frames, segment_len, counts, nullptr, nullptr,
-                 workspace, workspace_bytes, device, stream);
+  return clip_lines(mt_clip_kernel<false>, false, "match_clip_count", "frame", lines, line_offsets, n_lines, poses,
+                    n_frames, segment_len, counts, nullptr, nullptr, workspace, workspace_bytes, device, stream);
 }
 int prh_match_clip_write(const double* lines, const long long* line_offsets, int n_lines, const double* poses,
                          int n_frames, double segment_len, const long long* out_offsets, double* out,
                          void* workspace, size_t workspace_bytes, int device, void* stream) {
-  return mt_clip(true, lines, line_offsets, n_lines, poses, n_frames, segment_len, nullptr, out_offsets, out,
-                 workspace, workspace_bytes, device, stream);
+  return clip_lines(mt_clip_kernel<true>, true, "match_clip_write", "frame", lines, line_offsets, n_lines, poses,
+                    n_frames, segment_len, nullptr, out_offsets, out, workspace, workspace_bytes, device, stream);
 }
 size_t prh_match_costs_workspace_bytes(long long n_pred_lines) {
   if (n_pred_lines < 0) return 0;

@@ -11,14 +11,16 @@ slice; here every slice of a drive comes out of two HIP passes over the cloud
   clip_lines                 HIP: every GT polyline transformed and clipped per slice (:145-182,263-273)
   apply_noise                HIP: the deterministic half of generate_noisy_line (augment :18-54)
   noisy_candidates           HIP: the same with the draws from a counter hash, fresh per seed
-  write_scene / slice_drive  host: the reference's two files (:184-209) and the whole pipeline
-                             (slice_drive's .pcd text is formatted on the device: pcd.write_pcds)
+  write_scene / slice_drive  host: the reference's two files (:184-209: pcd.write_pcd_host + this
+                             module's JSON) and the whole pipeline (slice_drive's .pcd text is
+                             formatted on the device: pcd.write_pcds)
 
     res = slice_drive("DRIVE_annotation_raw_data", "DRIVE.bag.json", "train_data")
     stream = SceneSampleStream("train_data", augment=(0.1, 0.25, 0.4), batch_size=32)
 
 slice_cloud, clip_lines, apply_noise and noisy_candidates have no CPU fallback: without a GPU they
-raise RuntimeError.
+raise RuntimeError.  The plumbing to the library (device, pointers, uploads, the count / scan /
+write clip driver shared with predictions.clip_lines_frames) is in _gpu.py.
 """
 import ctypes as C
 import glob
@@ -28,7 +30,9 @@ import os
 import numpy as np
 import torch
 
+from . import _gpu as G
 from . import _lib as L
+from .pcd import write_pcd_host, write_pcds
 
 SEGMENT_LEN = 50.0           # generate_train_data.py:11-12
 STRIDE = 25.0
@@ -106,19 +110,18 @@ def load_gt_items(json_path):
     return items
 
 
-def _xyz_dicts(points):
+def xyz_dicts(points):
+    """(n,3) -> the scene JSON's list of {'x', 'y', 'z'}."""
     return [{"x": float(p[0]), "y": float(p[1]), "z": float(p[2])} for p in points]
 
 
 def _write_scene_json(json_path, items, ref_ts):
-    """write_scene's JSON file on its own (slice_drive writes the .pcd files through pcd.write_pcds).
-    Keep identical to the JSON half of write_scene below; tests/test_pcd_gpu.py
-    (test_slice_drive_files_equal_write_scene) compares the two byte for byte."""
+    """write_scene's JSON file (slice_drive writes the .pcd files through pcd.write_pcds)."""
     output = {"timestamp": ref_ts, "items": []}
     for item in items:
-        entry = {"category": item["category"], "attributes": item["attributes"], "position": _xyz_dicts(item["points"])}
+        entry = {"category": item["category"], "attributes": item["attributes"], "position": xyz_dicts(item["points"])}
         if "noisy_candidates" in item:
-            entry["noisy_candidates"] = [_xyz_dicts(c) for c in item["noisy_candidates"]]
+            entry["noisy_candidates"] = [xyz_dicts(c) for c in item["noisy_candidates"]]
         output["items"].append(entry)
     with open(json_path, "w") as f:
         json.dump(output, f, indent=4)
@@ -130,52 +133,11 @@ def write_scene(pcd_path, json_path, points, items, ref_ts):
     items[].category / attributes / position, indent 4.  items: dicts with 'category',
     'attributes', 'points' (n,3); an item that carries 'noisy_candidates' (list of (n,3)) gets that
     key too, in the layout augment_train_data.py writes."""
-    points = np.asarray(torch.as_tensor(points).cpu() if torch.is_tensor(points) else points, dtype=np.float64)
-    points = points.reshape(-1, 4)
-    n = len(points)
-    with open(pcd_path, "w") as f:
-        f.write("VERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n")
-        f.write(f"WIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA ascii\n")
-        if n:
-            np.savetxt(f, points, fmt="%.4f %.4f %.4f %d", newline="\n")
-    output = {"timestamp": ref_ts, "items": []}
-    for item in items:
-        entry = {"category": item["category"], "attributes": item["attributes"], "position": _xyz_dicts(item["points"])}
-        if "noisy_candidates" in item:
-            entry["noisy_candidates"] = [_xyz_dicts(c) for c in item["noisy_candidates"]]
-        output["items"].append(entry)
-    with open(json_path, "w") as f:
-        json.dump(output, f, indent=4)
+    write_pcd_host(pcd_path, points)
+    _write_scene_json(json_path, items, ref_ts)
 
 
 # ------------------------------------------------------------------ GPU side
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("pointnet_refine_amd.drive needs a GPU (there is no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ws(nbytes, dev):
-    return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
-
-
-def _poses_t(poses, dev, what):
-    p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7) if not torch.is_tensor(poses) else poses
-    if torch.is_tensor(p):
-        if not p.is_cuda:
-            raise RuntimeError(f"{what}: tensors must be CUDA tensors (there is no CPU fallback)")
-        return p.detach().to(torch.float64).reshape(-1, 7).contiguous()
-    return torch.from_numpy(p).to(dev)
-
-
 def slice_cloud(cloud, poses_xyzq, segment_len=SEGMENT_LEN, radius=RADIUS):
     """Every slice of a drive in two passes over the cloud (:247-261).
 
@@ -184,42 +146,28 @@ def slice_cloud(cloud, poses_xyzq, segment_len=SEGMENT_LEN, radius=RADIUS):
     points[offsets[s]:offsets[s+1]] - local xyz and the untouched intensity of the points with
     float32 (x - f32(pose.x))^2 + (y - f32(pose.y))^2 < radius^2 and -segment_len/2 <= local x <=
     segment_len/2, in cloud order; source_index is the cloud row of each.  Bitwise reproducible."""
-    dev = _device()
-    if torch.is_tensor(cloud):
-        if not cloud.is_cuda:
-            raise RuntimeError("slice_cloud: tensors must be CUDA tensors (there is no CPU fallback)")
-        cl = cloud.detach()
-    else:
-        cl = torch.from_numpy(np.ascontiguousarray(cloud, dtype=np.float32)).to(dev)
+    dev = G.device("drive")
+    cl = G.as_cuda(cloud if torch.is_tensor(cloud) else np.asarray(cloud, dtype=np.float32), dev, "slice_cloud")
     if cl.dtype != torch.float32 or cl.dim() != 2 or cl.shape[1] != 4:
         raise ValueError(f"slice_cloud: cloud must be (P,4) float32, got {tuple(cl.shape)} {cl.dtype}")
-    cl = cl.contiguous()
     dev = cl.device
-    ps = _poses_t(poses_xyzq, dev, "slice_cloud")
+    ps = G.poses(poses_xyzq, dev, "slice_cloud")
     npts, n_s = cl.shape[0], ps.shape[0]
     if npts >= 2 ** 31:
         raise ValueError("slice_cloud: at most 2^31 - 1 points per call")
     lib = L.lib()
     nb = lib.prh_drive_slice_workspace_bytes(npts, n_s)
-    ws = _ws(nb, dev)
+    ws = G.workspace(nb, dev)
     offsets = torch.empty((n_s + 1,), dtype=torch.int64, device=dev)
-    L.check(lib.prh_drive_slice_count(_ptr(cl), npts, _ptr(ps), n_s, float(segment_len), float(radius), _ptr(offsets),
-                                      _ptr(ws), nb, dev.index, _stream(dev)), "prh_drive_slice_count")
+    L.check(lib.prh_drive_slice_count(G.ptr(cl), npts, G.ptr(ps), n_s, float(segment_len), float(radius), G.ptr(offsets),
+                                      G.ptr(ws), nb, dev.index, G.stream(dev)), "prh_drive_slice_count")
     total = int(offsets[-1].item())
     points = torch.empty((total, 4), dtype=torch.float64, device=dev)
     index = torch.empty((total,), dtype=torch.int64, device=dev)
-    L.check(lib.prh_drive_slice_write(_ptr(cl), npts, _ptr(ps), n_s, float(segment_len), float(radius), _ptr(offsets),
-                                      _ptr(points), _ptr(index), total, _ptr(ws), nb, dev.index, _stream(dev)),
+    L.check(lib.prh_drive_slice_write(G.ptr(cl), npts, G.ptr(ps), n_s, float(segment_len), float(radius), G.ptr(offsets),
+                                      G.ptr(points), G.ptr(index), total, G.ptr(ws), nb, dev.index, G.stream(dev)),
             "prh_drive_slice_write")
     return points, offsets, index
-
-
-def _csr(lines, dev):
-    arrs = [np.zeros((0, 3)) if l is None else np.asarray(l, dtype=np.float64).reshape(-1, 3) for l in lines]
-    off = np.zeros(len(arrs) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([len(a) for a in arrs])
-    verts = np.concatenate(arrs) if off[-1] > 0 else np.zeros((0, 3))
-    return torch.from_numpy(np.ascontiguousarray(verts)).to(dev), torch.from_numpy(off).to(dev), off
 
 
 def clip_lines(lines, poses_xyzq, segment_len=SEGMENT_LEN, return_counts=False):
@@ -227,34 +175,14 @@ def clip_lines(lines, poses_xyzq, segment_len=SEGMENT_LEN, return_counts=False):
     with clip_polyline_by_x (:145-182).  Returns, per slice, the list of (line index, (k,3) float64)
     the reference keeps (k > 1, :267-273), in line order.  return_counts=True also returns the
     (S, n_lines) int array of output vertex counts before that rule."""
-    dev = _device()
-    ps = _poses_t(poses_xyzq, dev, "clip_lines")
-    n_s, n_l = ps.shape[0], len(lines)
-    verts, off_t, _ = _csr(lines, dev)
-    counts = torch.zeros((n_s * n_l,), dtype=torch.int32, device=dev)
-    lib = L.lib()
-    nb = lib.prh_drive_clip_workspace_bytes(n_s)
-    ws = _ws(nb, dev)
-    L.check(lib.prh_drive_clip_count(_ptr(verts), _ptr(off_t), n_l, _ptr(ps), n_s, float(segment_len), _ptr(counts),
-                                     _ptr(ws), nb, dev.index, _stream(dev)), "prh_drive_clip_count")
-    out_off = torch.zeros((n_s * n_l + 1,), dtype=torch.int64, device=dev)
-    out_off[1:] = torch.cumsum(counts, 0)
-    total = int(out_off[-1].item())
-    out = torch.empty((total, 3), dtype=torch.float64, device=dev)
-    if total:
-        L.check(lib.prh_drive_clip_write(_ptr(verts), _ptr(off_t), n_l, _ptr(ps), n_s, float(segment_len),
-                                         _ptr(out_off), _ptr(out), _ptr(ws), nb, dev.index, _stream(dev)),
-                "prh_drive_clip_write")
-    out, oo = out.cpu().numpy(), out_off.cpu().numpy()
-    cnt = np.diff(oo).reshape(n_s, n_l)
-    per_slice = [[(l, out[oo[s * n_l + l]:oo[s * n_l + l + 1]].copy()) for l in range(n_l) if cnt[s, l] > 1]
-                 for s in range(n_s)]
-    return (per_slice, cnt) if return_counts else per_slice
+    ps = G.poses(poses_xyzq, G.device("drive"), "clip_lines")
+    return G.clip_two_pass(("prh_drive_clip_workspace_bytes", "prh_drive_clip_count", "prh_drive_clip_write"), lines, ps,
+                           segment_len, return_counts)
 
 
 def _noise(lines, scales, seed, line_ids, draws, dev):
     """(out (K,V,3), draws_u (L,K,4), draws_j (K,V,3)) CUDA float64 and the host CSR offsets."""
-    verts, off_t, off = _csr(lines, dev)
+    verts, off_t, off = G.lines_csr(lines, dev)
     n_l, n_v = len(lines), int(off[-1])
     k = len(scales) if draws is None else int(draws[0].shape[1])
     if not 1 <= k <= MAX_SCALES:
@@ -270,10 +198,10 @@ def _noise(lines, scales, seed, line_ids, draws, dev):
     sc = (C.c_double * MAX_SCALES)(*([float(s) for s in scales] if draws is None else []))
     lib = L.lib()
     nb = lib.prh_drive_noise_workspace_bytes(n_l)
-    ws = _ws(nb, dev)
-    L.check(lib.prh_drive_noise(_ptr(verts), _ptr(off_t), _ptr(vline), n_v, n_l, _ptr(ids), sc, k,
-                                C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), 1 if draws is None else 0, _ptr(du),
-                                _ptr(dj), _ptr(out), _ptr(ws), nb, dev.index, _stream(dev)), "prh_drive_noise")
+    ws = G.workspace(nb, dev)
+    L.check(lib.prh_drive_noise(G.ptr(verts), G.ptr(off_t), G.ptr(vline), n_v, n_l, G.ptr(ids), sc, k,
+                                C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), 1 if draws is None else 0, G.ptr(du),
+                                G.ptr(dj), G.ptr(out), G.ptr(ws), nb, dev.index, G.stream(dev)), "prh_drive_noise")
     return out, du, dj, off
 
 
@@ -281,7 +209,7 @@ def apply_noise(gt, yaw_rad, shift, jitter):
     """The deterministic half of generate_noisy_line (augment_train_data.py:18-54), fp64 on the GPU:
     (gt - centroid) @ R(yaw).T + centroid + shift + jitter with R = [[c,-s,0],[s,c,0],[0,0,1]].
     gt, jitter (n,3); shift (3,).  Returns (n,3) numpy."""
-    dev = _device()
+    dev = G.device("drive")
     gt = np.asarray(gt, dtype=np.float64).reshape(-1, 3)
     jitter = np.asarray(jitter, dtype=np.float64).reshape(-1, 3)
     if len(jitter) != len(gt):
@@ -301,7 +229,7 @@ def noisy_candidates(gt_lines, noise_scales=NOISE_SCALES, seed=0, return_draws=F
     of (n,3) numpy arrays; the same seed gives the same bits.  return_draws=True also returns
     {'yaw' (L,K) rad, 'shift' (L,K,3), 'jitter' [per line (K,n,3)]}.  Same distribution as the
     reference's numpy draws, not the same numbers."""
-    dev = _device()
+    dev = G.device("drive")
     out, du, dj, off = _noise(gt_lines, tuple(noise_scales), seed, None, None, dev)
     out, du, dj = out.cpu().numpy(), du.cpu().numpy(), dj.cpu().numpy()
     k = len(noise_scales)
@@ -316,11 +244,7 @@ def noisy_candidates(gt_lines, noise_scales=NOISE_SCALES, seed=0, return_draws=F
 def stream_candidates(gt_lines, item_ids, noise_scales, seed, device):
     """SceneSampleStream's per-epoch draw: candidates of gt_lines hashed under their item numbers.
     Returns out[k][l] as a list (per scale) of lists (per line) of (n,3) numpy arrays."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("pointnet_refine_amd.drive needs a GPU (there is no CPU fallback)")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = G.device("drive", device)
     out, _, _, off = _noise(gt_lines, tuple(noise_scales), seed, item_ids, None, dev)
     out = out.cpu().numpy()
     return [[out[c, off[l]:off[l + 1]] for l in range(len(gt_lines))] for c in range(len(noise_scales))]
@@ -337,7 +261,6 @@ def slice_drive(drive_dir, gt_json, out_dir=None, candidates=False, noise_scales
     'points' (T,4) CUDA, 'offsets', 'source_index', 'items' [per slice list of item dicts],
     'written' [names]}."""
     from .io import load_pcd_data
-    from .pcd import write_pcds
     poses = load_poses(os.path.join(drive_dir, "pose"))
     res = {"pose_index": [], "names": [], "points": None, "offsets": None, "source_index": None, "items": [],
            "written": []}

@@ -15,37 +15,14 @@ candidate) line of a scene at once:
 
 There is no CPU fallback: without a GPU every function raises RuntimeError.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
+from . import _gpu as G
 from . import _lib as L
 
 BAD_MATCH_LAT = 1.0          # :341: a candidate whose initial Lat exceeds 1 m is matched to the wrong GT
 _METRICS = ("ade_noisy", "ade_refined", "cd_noisy", "cd_refined", "lat_noisy", "lat_refined")
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("pointnet_refine_amd.metrics needs a GPU (there is no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _f64(x, dev, what):
-    if torch.is_tensor(x):
-        if not x.is_cuda:
-            raise RuntimeError(f"{what}: tensors must be CUDA tensors (there is no CPU fallback)")
-        return x.detach().to(torch.float64).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def line_metrics(noisy, refined, gt_lines, gt_index=None):
@@ -58,9 +35,9 @@ def line_metrics(noisy, refined, gt_lines, gt_index=None):
     into the GT polyline, -1 when not valid), reversed, valid, resampled_gt (L,M,3), ade_noisy,
     ade_refined, cd_noisy, cd_refined, lat_noisy, lat_refined (NaN when not valid) and
     bad_match = valid & (lat_noisy > 1.0)."""
-    dev = _device()
-    nz = _f64(noisy, dev, "line_metrics")
-    rf = _f64(refined, dev, "line_metrics")
+    dev = G.device("metrics")
+    nz = G.as_cuda(noisy, dev, "line_metrics", torch.float64)
+    rf = G.as_cuda(refined, dev, "line_metrics", torch.float64)
     if nz.dim() != 3 or nz.shape[2] != 3 or rf.shape != nz.shape:
         raise ValueError(f"line_metrics: noisy and refined must both be (L,M,3), got {tuple(nz.shape)} and {tuple(rf.shape)}")
     n_lines, m = nz.shape[0], nz.shape[1]
@@ -84,8 +61,8 @@ def line_metrics(noisy, refined, gt_lines, gt_index=None):
     res = torch.empty((n_lines, m, 3), dtype=torch.float64, device=dev)
     met = torch.empty((n_lines, 6), dtype=torch.float64, device=dev)
     lib = L.lib()
-    L.check(lib.prh_line_metrics(_ptr(nz), _ptr(rf), n_lines, m, _ptr(gt_t), _ptr(off_t), len(gts), _ptr(idx_t),
-                                 _ptr(info), _ptr(res), _ptr(met), dev.index, _stream(dev)), "prh_line_metrics")
+    L.check(lib.prh_line_metrics(G.ptr(nz), G.ptr(rf), n_lines, m, G.ptr(gt_t), G.ptr(off_t), len(gts), G.ptr(idx_t),
+                                 G.ptr(info), G.ptr(res), G.ptr(met), dev.index, G.stream(dev)), "prh_line_metrics")
     info, met = info.cpu().numpy(), met.cpu().numpy()
     out = {"crop_start": info[:, 0].astype(np.int64), "crop_end": info[:, 1].astype(np.int64),
            "reversed": info[:, 2].astype(bool), "valid": info[:, 3].astype(bool), "resampled_gt": res.cpu().numpy()}
@@ -101,9 +78,9 @@ def _sweep(pred_t, gt_t, shifts, dev):
     out = torch.empty((n_s,), dtype=torch.float64, device=dev)
     lib = L.lib()
     nb = lib.prh_shift_sweep_workspace_bytes(pred_t.shape[0], gt_t.shape[0], n_s)
-    ws = torch.empty((max(int(nb), 1),), dtype=torch.uint8, device=dev)
-    L.check(lib.prh_shift_sweep(_ptr(pred_t), pred_t.shape[0], _ptr(gt_t), gt_t.shape[0], _ptr(sh), n_s, _ptr(out),
-                                _ptr(ws), nb, dev.index, _stream(dev)), "prh_shift_sweep")
+    ws = G.workspace(nb, dev)
+    L.check(lib.prh_shift_sweep(G.ptr(pred_t), pred_t.shape[0], G.ptr(gt_t), gt_t.shape[0], G.ptr(sh), n_s, G.ptr(out),
+                                G.ptr(ws), nb, dev.index, G.stream(dev)), "prh_shift_sweep")
     return out.cpu().numpy()
 
 
@@ -111,9 +88,9 @@ def shift_sweep(pred_points, gt_points, shifts):
     """(S,) float64: for every shift (dx, dy) of shifts (S,2), the mean over pred_points (P,3) of the
     distance from pred + (dx, dy, 0) to the nearest of gt_points (G,3) - calibrate_alignment's
     inner loop (:170-193) for all shifts in one launch.  Bitwise reproducible."""
-    dev = _device()
-    pred_t = _f64(pred_points, dev, "shift_sweep").reshape(-1, 3)
-    gt_t = _f64(gt_points, dev, "shift_sweep").reshape(-1, 3)
+    dev = G.device("metrics")
+    pred_t = G.as_cuda(pred_points, dev, "shift_sweep", torch.float64).reshape(-1, 3)
+    gt_t = G.as_cuda(gt_points, dev, "shift_sweep", torch.float64).reshape(-1, 3)
     if pred_t.shape[0] == 0 or gt_t.shape[0] == 0 or np.asarray(shifts).size == 0:
         raise ValueError("shift_sweep: needs at least one pred point, one GT point and one shift")
     return _sweep(pred_t, gt_t, shifts, dev)
@@ -131,9 +108,9 @@ def calibrate_alignment(pred_lines, gt_lines, return_tables=False):
     shift_sweep launch.  return_tables=True also returns {"coarse": (shifts, means), "fine": ...}."""
     if len(pred_lines) == 0 or len(gt_lines) == 0:
         return ((0, 0), 999.0, {}) if return_tables else ((0, 0), 999.0)
-    dev = _device()
-    pred_t = _f64(np.vstack(pred_lines), dev, "calibrate_alignment")
-    gt_t = _f64(np.vstack(gt_lines), dev, "calibrate_alignment")
+    dev = G.device("metrics")
+    pred_t = G.as_cuda(np.vstack(pred_lines), dev, "calibrate_alignment", torch.float64)
+    gt_t = G.as_cuda(np.vstack(gt_lines), dev, "calibrate_alignment", torch.float64)
     best_offset, best_dist = (0, 0), float("inf")
     tables = {}
     coarse = _grid(np.arange(-20, 20, 2.0), np.arange(-10, 10, 1.0))
@@ -188,7 +165,7 @@ def evaluate_scene(model, pcd_points, items, num_line_points=32, num_context_poi
     """
     from .context import resample_polylines_device
     from .io import scene_offsets
-    dev = _device()
+    dev = G.device("metrics")
     rows, raw, gts, cal_gt = scene_rows(items)
     m = int(num_line_points)
     out = {"item_index": np.array([r[0] for r in rows], dtype=np.int64),

@@ -6,6 +6,7 @@ cloud that is already on the device meets the disk as one byte copy.
                   Python's % operator (np.savetxt) writes, with the byte span of every slice
   parse_rows      HIP: the payload of an ASCII PCD -> (P, ncols) float32 with np.loadtxt's bits
   write_pcds / write_pcd   the ten header lines + one slice of that text per file
+  write_pcd_host  the same file from np.savetxt: the package's one host writer and header text
   read_pcd        io.load_pcd_data's result as a CUDA tensor: ASCII through parse_rows, 14-byte
                   binary records through an unpack kernel, 16-byte records as a view
 
@@ -13,15 +14,14 @@ The device paths are strict: a row they cannot serve exactly (a value outside th
 domain - finite |x|,|y|,|z| < 2^40, finite |intensity| < 2^53; a token outside the parser's exact
 fast path, a blank or comment line, a ragged row) raises HostFallback naming the row, and
 write_pcd(s) / read_pcd(strict=False) then redo that call through the host functions
-(np.savetxt as drive.write_scene uses it, io.load_pcd_data), so bytes, values and exceptions are the
+(write_pcd_host, the np.savetxt writer drive.write_scene is built on; io.load_pcd_data), so bytes, values and exceptions are the
 host's.  format_rows, parse_rows and read_pcd have no CPU fallback: without a GPU they raise
 RuntimeError.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
+from . import _gpu as G
 from . import _lib as L
 
 FIELDS = ("x", "y", "z", "intensity")
@@ -37,7 +37,7 @@ class HostFallback(ValueError):
 
 # ------------------------------------------------------------------ host side: the header
 def header_bytes(n):
-    """The ten header lines drive.write_scene writes for n points."""
+    """The ten header lines of the reference's scene files for n points (the package's one copy)."""
     return (f"VERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n"
             f"WIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA ascii\n").encode()
 
@@ -65,9 +65,13 @@ def parse_header(buf):
             return info
 
 
-def _host_write(path, rows):
-    """drive.write_scene's .pcd half on the host."""
-    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
+def write_pcd_host(path, points):
+    """The reference's save_pcd on the host, byte for byte: the header and np.savetxt's '%.4f %.4f
+    %.4f %d' rows (intensity truncated as int() does).  points: (n,4) rows, numpy or tensor.  The
+    .pcd half of drive.write_scene and predictions.write_prediction_scene, and what write_pcds
+    falls back to."""
+    rows = np.asarray(torch.as_tensor(points).cpu() if torch.is_tensor(points) else points, dtype=np.float64)
+    rows = rows.reshape(-1, 4)
     with open(path, "w") as f:
         f.write(header_bytes(len(rows)).decode())
         if len(rows):
@@ -75,38 +79,8 @@ def _host_write(path, rows):
 
 
 # ------------------------------------------------------------------ GPU side
-def _device(device=None):
-    if not torch.cuda.is_available():
-        raise RuntimeError("pointnet_refine_amd.pcd needs a GPU (there is no CPU fallback)")
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise RuntimeError("pointnet_refine_amd.pcd needs a GPU (there is no CPU fallback)")
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _exclusive(counts):
-    out = torch.zeros((counts.numel() + 1,), dtype=torch.int64, device=counts.device)
-    if counts.numel():
-        out[1:] = torch.cumsum(counts, 0)
-    return out
-
-
 def _rows_t(points, what):
-    dev = _device()
-    if torch.is_tensor(points):
-        if not points.is_cuda:
-            raise RuntimeError(f"{what}: tensors must be CUDA tensors (there is no CPU fallback)")
-        pts = points.detach()
-    else:
-        pts = torch.from_numpy(np.ascontiguousarray(points)).to(dev)
+    pts = G.as_cuda(points, G.device("pcd"), what)
     if pts.dtype not in (torch.float64, torch.float32):
         pts = pts.to(torch.float64)
     if pts.dim() != 2 or pts.shape[1] != 4:
@@ -140,18 +114,18 @@ def format_rows(points, offsets=None):
     group_bytes = torch.empty((n_g,), dtype=torch.int32, device=dev)
     status = torch.empty((1,), dtype=torch.int64, device=dev)
     nb = lib.prh_pcd_format_workspace_bytes(n)
-    ws = torch.empty((max(int(nb), 1),), dtype=torch.uint8, device=dev)
+    ws = G.workspace(nb, dev)
     is64 = 1 if pts.dtype == torch.float64 else 0
-    L.check(lib.prh_pcd_format_count(_ptr(pts), is64, n, _ptr(row_bytes), _ptr(group_bytes), _ptr(status), _ptr(ws),
-                                     nb, dev.index, _stream(dev)), "prh_pcd_format_count")
-    group_off = _exclusive(group_bytes)
+    L.check(lib.prh_pcd_format_count(G.ptr(pts), is64, n, G.ptr(row_bytes), G.ptr(group_bytes), G.ptr(status), G.ptr(ws),
+                                     nb, dev.index, G.stream(dev)), "prh_pcd_format_count")
+    group_off = G.exclusive_scan(group_bytes)
     bad, total = torch.stack((status[0], group_off[-1])).tolist()
     if bad >= 0:
         raise HostFallback("format_rows", bad)
     text = torch.empty((total,), dtype=torch.uint8, device=dev)
     byte_off = torch.empty((n_s + 1,), dtype=torch.int64, device=dev)
-    L.check(lib.prh_pcd_format_write(_ptr(pts), is64, n, _ptr(row_bytes), _ptr(group_off), _ptr(off), n_s, _ptr(text),
-                                     total, _ptr(byte_off), dev.index, _stream(dev)), "prh_pcd_format_write")
+    L.check(lib.prh_pcd_format_write(G.ptr(pts), is64, n, G.ptr(row_bytes), G.ptr(group_off), G.ptr(off), n_s, G.ptr(text),
+                                     total, G.ptr(byte_off), dev.index, G.stream(dev)), "prh_pcd_format_write")
     return text, byte_off
 
 
@@ -163,12 +137,12 @@ def parse_rows(payload, ncols):
     if torch.is_tensor(payload):
         if not payload.is_cuda:
             raise RuntimeError("parse_rows: tensors must be CUDA tensors (there is no CPU fallback)")
-        _device()
+        G.device("pcd")
         if payload.dtype != torch.uint8 or payload.dim() != 1:
             raise ValueError("parse_rows: payload must be a 1-D uint8 tensor")
         pay = payload.detach().contiguous()
     else:
-        dev = _device()
+        dev = G.device("pcd")
         pay = (torch.frombuffer(bytearray(payload), dtype=torch.uint8).to(dev) if len(payload)
                else torch.empty((0,), dtype=torch.uint8, device=dev))
     ncols = int(ncols)
@@ -179,21 +153,21 @@ def parse_rows(payload, ncols):
     if n == 0:
         return torch.empty((0, ncols), dtype=torch.float32, device=dev)
     lib = L.lib()
-    n_b = lib.prh_pcd_index_blocks(_ptr(pay), n)
+    n_b = lib.prh_pcd_index_blocks(G.ptr(pay), n)
     block_lines = torch.empty((n_b,), dtype=torch.int32, device=dev)
-    L.check(lib.prh_pcd_index_count(_ptr(pay), n, _ptr(block_lines), dev.index, _stream(dev)), "prh_pcd_index_count")
-    block_off = _exclusive(block_lines)
+    L.check(lib.prh_pcd_index_count(G.ptr(pay), n, G.ptr(block_lines), dev.index, G.stream(dev)), "prh_pcd_index_count")
+    block_off = G.exclusive_scan(block_lines)
     lines, last = torch.stack((block_off[-1], pay[-1].to(torch.int64))).tolist()
     rows = lines + (0 if last == 10 else 1)
     row_start = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
-    L.check(lib.prh_pcd_index_write(_ptr(pay), n, _ptr(block_off), _ptr(row_start), rows, dev.index, _stream(dev)),
+    L.check(lib.prh_pcd_index_write(G.ptr(pay), n, G.ptr(block_off), G.ptr(row_start), rows, dev.index, G.stream(dev)),
             "prh_pcd_index_write")
     out = torch.empty((rows, ncols), dtype=torch.float32, device=dev)
     status = torch.empty((1,), dtype=torch.int64, device=dev)
     nb = lib.prh_pcd_parse_workspace_bytes(rows)
-    ws = torch.empty((max(int(nb), 1),), dtype=torch.uint8, device=dev)
-    L.check(lib.prh_pcd_parse(_ptr(pay), n, _ptr(row_start), rows, ncols, _ptr(out), _ptr(status), _ptr(ws), nb,
-                              dev.index, _stream(dev)), "prh_pcd_parse")
+    ws = G.workspace(nb, dev)
+    L.check(lib.prh_pcd_parse(G.ptr(pay), n, G.ptr(row_start), rows, ncols, G.ptr(out), G.ptr(status), G.ptr(ws), nb,
+                              dev.index, G.stream(dev)), "prh_pcd_parse")
     bad = int(status.item())
     if bad >= 0:
         raise HostFallback("parse_rows", bad)
@@ -210,7 +184,7 @@ def unpack_records14(payload, n_points):
     payload = payload.detach().contiguous()
     dev = payload.device
     out = torch.empty((n_points, 4), dtype=torch.float32, device=dev)
-    L.check(L.lib().prh_pcd_unpack14(_ptr(payload), n_points, _ptr(out), dev.index, _stream(dev)), "prh_pcd_unpack14")
+    L.check(L.lib().prh_pcd_unpack14(G.ptr(payload), n_points, G.ptr(out), dev.index, G.stream(dev)), "prh_pcd_unpack14")
     return out
 
 
@@ -231,7 +205,7 @@ def write_pcds(paths, points, offsets, strict=False):
         host = points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)
         for s, path in enumerate(paths):
             if path is not None:
-                _host_write(path, host[off[s]:off[s + 1]])
+                write_pcd_host(path, host[off[s]:off[s + 1]])
         return
     text, boff = memoryview(text.cpu().numpy()), byte_off.cpu().numpy()
     for s, path in enumerate(paths):
@@ -259,7 +233,7 @@ def read_pcd(path, device=None, strict=False):
     through io.load_pcd_data, which never raises: a missing file, a bad header or a ragged file
     give an empty (0,4) tensor and its printed message."""
     from .io import load_pcd_data
-    dev = _device(device)
+    dev = G.device("pcd", device)
 
     def host():
         arr = load_pcd_data(path)

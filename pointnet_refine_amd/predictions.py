@@ -8,7 +8,8 @@ reference loops over frames in Python (a numpy pass over the cloud, one numpy ca
 
   pixel_to_ego / load_results / load_frame_poses / match_poses   host: the detector JSON, the poses
                                                   and the nearest-pose rule (:101-124,248-262,338-359)
-  clip_lines_frames      HIP: GT polylines per frame, this tool's clip rule (:265-315,400-402)
+  clip_lines_frames      HIP: GT polylines per frame, this tool's clip rule (:265-315,400-402),
+                         through the driver drive.clip_lines uses (_gpu.clip_two_pass)
   line_costs             HIP: the (P_f, G_f) one-way xy Chamfer matrices of all frames (:434-448)
   assign                 HIP: minimum-cost assignment of every frame's matrix (:451-459)
   match_predictions      line_costs + assign
@@ -17,7 +18,6 @@ reference loops over frames in Python (a numpy pass over the cloud, one numpy ca
 clip_lines_frames, line_costs, assign, match_predictions and predictions_to_scenes have no CPU
 fallback: without a GPU they raise RuntimeError.
 """
-import ctypes as C
 import glob
 import json
 import os
@@ -25,9 +25,10 @@ import os
 import numpy as np
 import torch
 
+from . import _gpu as G
 from . import _lib as L
 from . import drive as D
-from .drive import _csr, _poses_t, _ptr, _stream, _ws, _xyz_dicts
+from .pcd import write_pcd_host, write_pcds
 
 SEGMENT_LEN = 50.0               # generate_inference_data_vma.py:18
 RADIUS = 60.0                    # :366
@@ -110,33 +111,17 @@ def write_prediction_scene(pcd_path, json_path, points, items, pose_ts, result_t
     ASCII PCD drive.write_scene writes, and a JSON of timestamp (the pose's), result_timestamp and
     the items as given (dicts of 'category', 'attributes', 'position', 'noisy_candidates',
     'context_lines' with lists of {'x','y','z'}), indent 4."""
-    points = np.asarray(torch.as_tensor(points).cpu() if torch.is_tensor(points) else points, dtype=np.float64)
-    points = points.reshape(-1, 4)
-    n = len(points)
-    with open(pcd_path, "w") as f:
-        f.write("VERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n")
-        f.write(f"WIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA ascii\n")
-        if n:
-            np.savetxt(f, points, fmt="%.4f %.4f %.4f %d", newline="\n")
-    with open(json_path, "w") as f:
-        json.dump({"timestamp": str(pose_ts), "result_timestamp": str(result_ts), "items": items}, f, indent=4)
+    write_pcd_host(pcd_path, points)
+    _write_prediction_json(json_path, items, pose_ts, result_ts)
 
 
 def _write_prediction_json(json_path, items, pose_ts, result_ts):
-    """write_prediction_scene's JSON file on its own (the .pcd files go through pcd.write_pcds).
-    Keep identical to the JSON half of write_prediction_scene above; tests/test_pcd_gpu.py
-    (test_predictions_to_scenes_files_equal_write_prediction_scene) compares the two byte for byte."""
+    """write_prediction_scene's JSON file (predictions_to_scenes writes the .pcd files through pcd.write_pcds)."""
     with open(json_path, "w") as f:
         json.dump({"timestamp": str(pose_ts), "result_timestamp": str(result_ts), "items": items}, f, indent=4)
 
 
 # ------------------------------------------------------------------ GPU side
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("pointnet_refine_amd.predictions needs a GPU (there is no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _check_unit(poses, what):
     p = poses.detach().cpu().numpy() if torch.is_tensor(poses) else np.asarray(poses, dtype=np.float64)
     p = p.reshape(-1, 7)
@@ -156,30 +141,11 @@ def clip_lines_frames(lines, poses_xyzq, segment_len=SEGMENT_LEN, return_counts=
     of (line index, (k,3) float64) kept, in line order; return_counts=True also returns the (F,
     n_lines) int array of vertex counts before the keep rule (0 for a line the gate drops).
     Poses whose quaternion norm differs from 1 by more than 1e-6 raise ValueError."""
-    dev = _device()
+    dev = G.device("predictions")
     _check_unit(poses_xyzq, "clip_lines_frames")
-    ps = _poses_t(poses_xyzq, dev, "clip_lines_frames")
-    n_f, n_l = ps.shape[0], len(lines)
-    verts, off_t, _ = _csr(lines, dev)
-    counts = torch.zeros((n_f * n_l,), dtype=torch.int32, device=dev)
-    lib = L.lib()
-    nb = lib.prh_match_clip_workspace_bytes(n_f)
-    ws = _ws(nb, dev)
-    L.check(lib.prh_match_clip_count(_ptr(verts), _ptr(off_t), n_l, _ptr(ps), n_f, float(segment_len), _ptr(counts),
-                                     _ptr(ws), nb, dev.index, _stream(dev)), "prh_match_clip_count")
-    out_off = torch.zeros((n_f * n_l + 1,), dtype=torch.int64, device=dev)
-    out_off[1:] = torch.cumsum(counts, 0)
-    total = int(out_off[-1].item())
-    out = torch.empty((total, 3), dtype=torch.float64, device=dev)
-    if total:
-        L.check(lib.prh_match_clip_write(_ptr(verts), _ptr(off_t), n_l, _ptr(ps), n_f, float(segment_len),
-                                         _ptr(out_off), _ptr(out), _ptr(ws), nb, dev.index, _stream(dev)),
-                "prh_match_clip_write")
-    out, oo = out.cpu().numpy(), out_off.cpu().numpy()
-    cnt = np.diff(oo).reshape(n_f, n_l)
-    per_frame = [[(l, out[oo[f * n_l + l]:oo[f * n_l + l + 1]].copy()) for l in range(n_l) if cnt[f, l] > 1]
-                 for f in range(n_f)]
-    return (per_frame, cnt) if return_counts else per_frame
+    ps = G.poses(poses_xyzq, dev, "clip_lines_frames")
+    return G.clip_two_pass(("prh_match_clip_workspace_bytes", "prh_match_clip_count", "prh_match_clip_write"), lines, ps,
+                           segment_len, return_counts)
 
 
 def _xy_csr(lines, dev):
@@ -211,7 +177,7 @@ def line_costs(pred_lines, pred_offsets, gt_lines, gt_offsets):
 
 def _pack_lines(pred_lines, pred_offsets, gt_lines, gt_offsets):
     """line_costs' arguments as device CSR arrays (the host half of the call)."""
-    dev = _device()
+    dev = G.device("predictions")
     p_off = _frame_offsets(pred_offsets, len(pred_lines), "line_costs")
     g_off = _frame_offsets(gt_offsets, len(gt_lines), "line_costs")
     if len(p_off) != len(g_off):
@@ -232,9 +198,9 @@ def _costs_packed(packed):
     if c_off[-1] > 0:
         lib = L.lib()
         nb = lib.prh_match_costs_workspace_bytes(n_pred)
-        ws = _ws(nb, dev)
-        L.check(lib.prh_match_costs(_ptr(pxy), _ptr(pl_off), _ptr(pf), n_pred, _ptr(gxy), _ptr(gl_off), _ptr(gf), n_f,
-                                    _ptr(cf), _ptr(costs), _ptr(ws), nb, dev.index, _stream(dev)), "prh_match_costs")
+        ws = G.workspace(nb, dev)
+        L.check(lib.prh_match_costs(G.ptr(pxy), G.ptr(pl_off), G.ptr(pf), n_pred, G.ptr(gxy), G.ptr(gl_off), G.ptr(gf), n_f,
+                                    G.ptr(cf), G.ptr(costs), G.ptr(ws), nb, dev.index, G.stream(dev)), "prh_match_costs")
     return costs, c_off, shapes
 
 
@@ -249,7 +215,7 @@ def assign(costs, cost_offsets, shapes, threshold=None, return_duals=False):
     and = 0 on assigned pairs.  When several assignments are optimal any one of them may be
     returned; the same input gives the same bits every run.  At most MAX_LINES (128) lines per side
     per frame: more raise ValueError, and so does a frame with a NaN or infinite cost."""
-    dev = _device()
+    dev = G.device("predictions")
     shapes = np.ascontiguousarray(shapes, dtype=np.int32).reshape(-1, 2)
     n_f = len(shapes)
     c_off = np.ascontiguousarray(cost_offsets, dtype=np.int64).reshape(-1)
@@ -259,12 +225,7 @@ def assign(costs, cost_offsets, shapes, threshold=None, return_duals=False):
     if n_f and shapes.max() > MAX_LINES:
         f = int(np.argmax(shapes.max(1)))
         raise ValueError(f"assign: frame {f} is {shapes[f, 0]} x {shapes[f, 1]}; at most {MAX_LINES} lines per side")
-    if torch.is_tensor(costs):
-        if not costs.is_cuda:
-            raise RuntimeError("assign: tensors must be CUDA tensors (there is no CPU fallback)")
-        ct = costs.detach().to(torch.float64).reshape(-1).contiguous()
-    else:
-        ct = torch.from_numpy(np.ascontiguousarray(costs, dtype=np.float64).reshape(-1)).to(dev)
+    ct = G.as_cuda(costs, dev, "assign", torch.float64).reshape(-1)
     if ct.numel() != (int(c_off[-1]) if n_f else 0):
         raise ValueError(f"assign: {ct.numel()} costs for offsets that end at {int(c_off[-1]) if n_f else 0}")
     r_off = np.zeros(n_f + 1, dtype=np.int64)
@@ -279,10 +240,10 @@ def assign(costs, cost_offsets, shapes, threshold=None, return_duals=False):
     if n_f:
         cf, rf, gf = (torch.from_numpy(a).to(dev) for a in (c_off, r_off, g_off))
         sh = torch.from_numpy(shapes).to(dev)
-        L.check(L.lib().prh_match_assign(_ptr(ct), _ptr(cf), _ptr(sh), _ptr(rf), _ptr(gf), n_f, int(cells.max()),
+        L.check(L.lib().prh_match_assign(G.ptr(ct), G.ptr(cf), G.ptr(sh), G.ptr(rf), G.ptr(gf), n_f, int(cells.max()),
                                          float(threshold) if threshold is not None else 0.0,
-                                         1 if threshold is not None else 0, _ptr(match), _ptr(total), _ptr(status),
-                                         _ptr(u), _ptr(v), dev.index, _stream(dev)), "prh_match_assign")
+                                         1 if threshold is not None else 0, G.ptr(match), G.ptr(total), G.ptr(status),
+                                         G.ptr(u), G.ptr(v), dev.index, G.stream(dev)), "prh_match_assign")
     st = status.cpu().numpy()
     if np.any(st != STATUS_OK):
         f = int(np.flatnonzero(st != STATUS_OK)[0])
@@ -297,7 +258,7 @@ def match_predictions(pred_lines_per_frame, gt_lines_per_frame, threshold=MATCH_
     frame of (match (P_f,) int32: GT index of each prediction or -1, cost (P_f, G_f) float64)."""
     if len(pred_lines_per_frame) != len(gt_lines_per_frame):
         raise ValueError("match_predictions: one list of predictions and one of GT lines per frame")
-    _device()
+    G.device("predictions")
     p_off = np.concatenate([[0], np.cumsum([len(p) for p in pred_lines_per_frame])]).astype(np.int64)
     g_off = np.concatenate([[0], np.cumsum([len(g) for g in gt_lines_per_frame])]).astype(np.int64)
     costs, c_off, shapes = line_costs([l for p in pred_lines_per_frame for l in p], p_off,
@@ -322,8 +283,7 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
     'items' [per frame list of item dicts, [] for a skipped frame], 'matches', 'costs', 'gt_index'
     [per frame the GT item of each context line], 'written' [result ts]}."""
     from .io import load_pcd_data
-    from .pcd import write_pcds
-    _device()
+    G.device("predictions")
     poses = load_frame_poses(os.path.join(drive_dir, "pose"))
     res = {"frames": [], "pose_index": [], "pose_ts": [], "points": None, "offsets": None, "slice": [], "items": [],
            "matches": [], "costs": [], "gt_index": [], "written": []}
@@ -355,11 +315,11 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
         res["slice"].append(s)
         items = []
         if s >= 0 and off[s + 1] > off[s]:
-            context = [_xyz_dicts(v) for _, v in clipped[s]]
+            context = [D.xyz_dicts(v) for _, v in clipped[s]]
             for i, line in enumerate(preds[s]):
                 g = int(matched[s][0][i])
                 items.append({"category": "lane_line", "attributes": {"score": fr["scores"][i]},
-                              "position": context[g] if g >= 0 else [], "noisy_candidates": [_xyz_dicts(line)],
+                              "position": context[g] if g >= 0 else [], "noisy_candidates": [D.xyz_dicts(line)],
                               "context_lines": context})
         res["items"].append(items)
         res["matches"].append(matched[s][0] if s >= 0 else np.zeros(0, dtype=np.int32))

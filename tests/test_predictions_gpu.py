@@ -79,6 +79,35 @@ def test_clip_lines_frames_generated_pairs_match_restatement():
             assert np.abs(v - want[f][l]).max() < TOL
 
 
+def test_each_clip_entry_point_runs_its_own_rule():
+    """drive.clip_lines and clip_lines_frames share one driver on each side of the C ABI; two lines
+    on which the two rules differ show that each entry point still launches its own kernel.  One
+    identity pose (the frame transform is exact), segment_len 50.  Line A ends on the slab's two
+    faces: the slicer keeps both end points (x_min <= x <= x_max), this tool's gate finds no vertex
+    strictly inside and drops it.  Line B crosses both faces and is cut at +-25 by either rule.
+    Every value is exact in fp64, so counts and vertices are compared with ==."""
+    from pointnet_refine_amd import drive
+    PR = _pr()
+    pose = np.array([[0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]])
+    a = np.array([(-25.0, 0.0, 0.0), (25.0, 0.0, 0.0)])
+    b = np.array([(-30.0, 1.0, 0.0), (0.0, 1.0, 0.0), (30.0, 1.0, 0.0)])
+    b_cut = np.array([(-25.0, 1.0, 0.0), (0.0, 1.0, 0.0), (25.0, 1.0, 0.0)])
+    want = {drive.clip_lines: ([2, 3], [(0, a), (1, b_cut)], R.RD.clip_lines_ref),
+            PR.clip_lines_frames: ([0, 3], [(1, b_cut)], R.clip_lines_frames_ref)}
+    for fn, (counts, kept, restatement) in want.items():
+        ref_counts, ref = restatement([a, b], pose)                 # the hand-derived table, on the CPU
+        assert ref_counts.tolist() == [counts] and all(np.array_equal(ref[0][l], v) for l, v in kept)
+        per_pose, got_counts = fn([a, b], pose, segment_len=50.0, return_counts=True)
+        assert got_counts.tolist() == [counts]
+        assert len(per_pose) == 1 and [l for l, _ in per_pose[0]] == [l for l, _ in kept]
+        for (_, v), (_, w) in zip(per_pose[0], kept):
+            assert v.dtype == np.float64 and np.array_equal(v, w)
+        per_pose, got_counts = fn([], pose, return_counts=True)
+        assert per_pose == [[]] and got_counts.shape == (1, 0)
+        per_pose, got_counts = fn([a, b], np.zeros((0, 7)), return_counts=True)
+        assert per_pose == [] and got_counts.shape == (0, 2)
+
+
 def test_costs_and_matches_on_reference_frames(golden_dir):
     PR = _pr()
     z = R.load_g12(golden_dir)
