@@ -670,6 +670,16 @@ int prh_test_gemm_nt(const float* a, const float* w, float* c, int m, int n, int
 size_t prh_test_gemm_tn_workspace_bytes(int p, int mo, int ni);
 int prh_test_gemm_tn(const float* a, const float* b, float* c, float* colsum, int p, int mo,
                      int ni, void* workspace, size_t workspace_bytes, int device, void* stream);
+/* The tn core with a BatchNorm-backward apply pass, dy[rows,cols] <- ka*dy + kb*z + kc in place:
+ * side != 0 carried inside the wgrad launch (split-fp16 mode, transposed-read core; an error
+ * elsewhere), side == 0 as the stand-alone pass ahead of the plain wgrad.  amax_out (device
+ * float): largest |dz|.  cols, lddy, ldz multiples of 4. */
+size_t prh_test_gemm_tn_side_workspace_bytes(int p, int mo, int ni);
+int prh_test_gemm_tn_side(const float* a, const float* b, float* c, float* colsum, int p, int mo,
+                          int ni, float* dy, long lddy, const float* z, long ldz, const float* ka,
+                          const float* kb, const float* kc, long rows, int cols, int side,
+                          float* amax_out, void* workspace, size_t workspace_bytes, int device,
+                          void* stream);
 
 /* Diagnostic: which XCD (XCC_ID) and CU (HW_ID) each workgroup of a `blocks` x 512-thread
  * launch with `lds_bytes` of dynamic LDS lands on; out[2*b] = XCC_ID, out[2*b+1] = HW_ID.

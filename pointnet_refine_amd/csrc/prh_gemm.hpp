@@ -950,6 +950,16 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const NTParams p) {
 // ---------------------------------------------------------------------------------------
 // wgrad core: C[Mo,Ni] (+)= sum over rows p in this split of proA(A)[p,Mo] * proB(B)[p,Ni]
 // ---------------------------------------------------------------------------------------
+// Side job of the transposed-read wgrad core (gemm_tn_tr_kernel<PROB, true>): the BatchNorm-backward
+// apply pass of ANOTHER layer, dy <- ka*dy + kb*z + kc over [rows, cols] in place, carried by the
+// wgrad's workgroups between their MFMA batches.  part[workgroup] receives the workgroup's max|dz|;
+// amax (host side only) is where launch_tn has absmax_final_kernel reduce them to.  dy null: none.
+struct TNSide {
+  float* dy; long lddy; const float* z; long ldz;
+  const float* ka; const float* kb; const float* kc;
+  long rows; int cols;
+  float* part; float* amax;
+};
 struct TNParams {
   const float* A;  long lda;     // [P,Mo]  (dy)
   const float* A2; long lda2;    // PRO_BNBWD: z
@@ -964,6 +974,7 @@ struct TNParams {
   const float* amaxA;            // fp16-plane core: largest |proA(A)|, |proB(B)| (device; null:
   const float* amaxB;            //   the launch measures them)
   int* pace;                     // transposed-read core: per-split progress counters (zeroed), or null
+  TNSide side;                   // transposed-read core: optional side job
 };
 
 // NARROW: Ni <= 64 (one column tile): 64 x 32 wave tiles, as in gemm_nt_kernel

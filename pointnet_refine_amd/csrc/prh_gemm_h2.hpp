@@ -439,7 +439,26 @@ __device__ __forceinline__ f16x8 tr_fragment(const char* plane, int col0, int la
 // co-resident cost a fraction of a millisecond once, never a hang.
 constexpr int TR_PACE = 8;            // k-tiles (128 rows) between progress reports
 constexpr int TR_PACE_SPINS = 256;    // x (s_sleep 16 + one L2 load): ~0.3 ms at most, once
-template <int PROB>
+//
+// SIDE: the workgroups also carry p.side, the BatchNorm-backward apply pass of another layer
+// (bn_bwd_apply_kernel's job: dy <- ka*dy + kb*z + kc in place, max|dz| per workgroup into
+// side.part[blockIdx.x]).  The GEMM is matrix-bound and leaves most of the HBM bandwidth idle; the
+// apply pass is pure bandwidth.  Every element is owned by one thread of one workgroup, so there
+// is nothing to synchronise: the same row-strided walk as the stand-alone kernel with the grid as
+// block count, a wave per row (cols >= 256: 256-column chunks of it; narrow layers: 64 / lanes-
+// per-row rows per wave item), one float4 item per thread and k-tile.  The item's two loads are
+// issued ahead of the k-tile's own and consumed after its store_tile, where the staging set just
+// written is dead (+16 registers, no scratch); whatever the k-loop did not reach is drained behind
+// it.  Rows and pad columns are fenced by the buffer descriptors (a descriptor per item over the
+// item's valid rows, lanes past the width get an offset beyond any descriptor), so the walk has
+// no branches.  The coefficients live in LDS behind the stages (3 x cols rounded up to 256).
+// Same pro_apply expression, same 16-B granularity as bn_bwd_apply_kernel: dz and its maximum are
+// bit-identical to the stand-alone pass.
+constexpr int TR_SIDE_MAX_COLS = 4096;
+inline size_t tr_side_lds(int cols) { return (size_t)3 * ((cols + 255) / 256 * 256) * 4 + 64; }
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+template <int PROB, bool SIDE = false>
 __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
   static_assert(PROB == PRO_NONE || PROB == PRO_BNRELU, "prologue not supported");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -541,6 +560,70 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
       }
     }
   };
+  // ---- side job state (SIDE only): group = rpw consecutive rows, item = (group, 256-column chunk)
+  [[maybe_unused]] float4 sdy = zero4(), sz = zero4();
+  [[maybe_unused]] float smax = 0.f;
+  [[maybe_unused]] long sg = 0, sgstep = 0;            // this wave's row group, stride (wave-uniform)
+  [[maybe_unused]] int sch = 0, snchunk = 1, srpw = 1, svo_d = 0, svo_z = 0, ssub = 0, scv = 0;
+  [[maybe_unused]] const float* scoef = reinterpret_cast<const float*>(smem + TR_LDS);
+  [[maybe_unused]] int scpad = 0;
+  if constexpr (SIDE) {
+    const TNSide& s = p.side;
+    const int c4s = s.cols >> 2;
+    int lpr = 64;                                      // lanes per row
+    while (lpr > 1 && (lpr >> 1) >= c4s) lpr >>= 1;
+    srpw = 64 / lpr;
+    snchunk = (c4s + 63) >> 6;
+    ssub = lane / lpr; scv = lane % lpr;
+    const bool colok = snchunk > 1 || scv < c4s;       // (the last chunk's width is fenced by the descriptor)
+    svo_d = colok ? (int)(ssub * s.lddy + scv * 4) * 4 : 0x40000000;
+    svo_z = colok ? (int)(ssub * s.ldz + scv * 4) * 4 : 0x40000000;
+    sg = (long)blockIdx.x * 8 + __builtin_amdgcn_readfirstlane(wave);
+    sgstep = (long)gridDim.x * 8;
+    scpad = (s.cols + 255) / 256 * 256;
+    float* cw = reinterpret_cast<float*>(smem + TR_LDS);
+    for (int i = tid; i < scpad; i += 512) {           // visible after the barrier that opens the k-loop
+      const bool in = i < s.cols;
+      cw[i] = in ? s.ka[i] : 0.f; cw[scpad + i] = in ? s.kb[i] : 0.f; cw[2 * scpad + i] = in ? s.kc[i] : 0.f;
+    }
+  }
+  // rows of this wave's current group that exist, and its chunk's columns
+  [[maybe_unused]] auto side_rows = [&]() -> int {
+    const long rem = p.side.rows - sg * srpw;
+    return rem <= 0 ? 0 : (rem > srpw ? srpw : (int)rem);
+  };
+  [[maybe_unused]] auto side_cols = [&]() -> int {
+    const int c = p.side.cols - sch * 256;
+    return c > 256 ? 256 : c;
+  };
+  // bytes a descriptor over nv rows x cc columns spans (selects, no branches: the k-loop body stays one block)
+  [[maybe_unused]] auto side_span = [&](int nv, int cc, long ld) -> int {
+    const int full = (int)(((long)(nv > 0 ? nv - 1 : 0) * ld + cc) * 4);
+    return nv > 0 ? full : 0;
+  };
+  [[maybe_unused]] auto side_issue = [&](float4& xd, float4& xz) {
+    const int nv = side_rows(), cc = side_cols();
+    const size_t e0 = (size_t)(sg * srpw);
+    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(p.side.dy + e0 * p.side.lddy + sch * 256), 0, side_span(nv, cc, p.side.lddy), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(p.side.z + e0 * p.side.ldz + sch * 256), 0, side_span(nv, cc, p.side.ldz), 0x00020000);
+    xd = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, svo_d, 0, 0));
+    xz = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rz, svo_z, 0, 0));
+  };
+  [[maybe_unused]] auto side_finish = [&](const float4& xd, const float4& xz) {      // apply, store, maximum; next item
+    const int nv = side_rows(), cc = side_cols();
+    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(p.side.dy + (size_t)(sg * srpw) * p.side.lddy + sch * 256), 0, side_span(nv, cc, p.side.lddy), 0x00020000);
+    const float* kq = scoef + sch * 256 + scv * 4;
+    const float4 v = pro_apply<PRO_BNBWD>(xd, xz, ldg4(kq), ldg4(kq + scpad), ldg4(kq + 2 * scpad));
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rd, svo_d, 0, 0);
+    const bool mine = ssub < nv && scv * 4 < cc;
+    const float vm = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+    smax = fmaxf(smax, mine ? vm : 0.f);
+    const bool wrap = sch + 1 == snchunk;
+    sch = wrap ? 0 : sch + 1; sg += wrap ? sgstep : 0;
+  };
   if (KT > 0) {
     load_tile(0, va[0], vb[0]);
     load_tile(1, va[1], vb[1]);
@@ -551,12 +634,14 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
     constexpr int CS = decltype(cs_)::value;
     char* cur = smem + (kt & 1) * TR_STAGE;
     char* nxt = smem + ((kt + 1) & 1) * TR_STAGE;
+    if constexpr (SIDE) side_issue(sdy, sz);
     load_tile(kt + 2, va[CS ^ 1], vb[CS ^ 1]);
     __builtin_amdgcn_sched_barrier(0);
     compute(cur, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
     __builtin_amdgcn_sched_barrier(0);
     compute(cur, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
     store_tile(nxt, va[CS], vb[CS]);
+    if constexpr (SIDE) side_finish(sdy, sz);
 #pragma unroll
     for (int g = 0; g < 12; ++g) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -583,6 +668,33 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
     iter(kt + 1, std::integral_constant<int, 0>{});
   }
   if (kt < KT) iter(kt, std::integral_constant<int, 1>{});
+
+  if constexpr (SIDE) {      // the rest of this workgroup's slice, four items in flight per thread
+    const long ngroups = (p.side.rows + srpw - 1) / srpw;
+    while (sg < ngroups) {   // (wave-uniform; items past the end are fenced like any other)
+      float4 xd[4], xz[4];
+      const long g0 = sg; const int c0 = sch;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        side_issue(xd[i], xz[i]);
+        if (++sch == snchunk) { sch = 0; sg += sgstep; }
+      }
+      sg = g0; sch = c0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) side_finish(xd[i], xz[i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) smax = fmaxf(smax, __shfl_xor(smax, o));
+    float* red = reinterpret_cast<float*>(smem + TR_LDS) + 3 * scpad;
+    if (lane == 0) red[wave] = smax;
+    __syncthreads();
+    if (tid == 0) {
+      float m = red[0];
+#pragma unroll
+      for (int i = 1; i < 8; ++i) m = fmaxf(m, red[i]);
+      p.side.part[blockIdx.x] = m;
+    }
+  }
 
   const float unscale = 1.f / (sA * sB);
   const int half = lane >> 5, l31 = lane & 31;

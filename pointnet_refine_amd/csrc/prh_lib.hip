@@ -558,10 +558,27 @@ inline size_t tn_splits_bound(Cores cores, int P, int Mo, int Ni) {   // over bo
 inline size_t tn_slab_floats(Cores c, int P, int Mo, int Ni) { return tn_splits_bound(c, P, Mo, Ni) * Mo * Ni + TN_HDR; }
 inline size_t tn_colsum_floats(Cores c, int P, int Mo, int Ni) { return tn_splits_bound(c, P, Mo, Ni) * Mo; }
 
+// Can the wgrad p (plain A, B plain or BN+ReLU) carry the side job s?  True exactly when launch_tn
+// serves p on the transposed-read core and the job fits it: one partial maximum per workgroup,
+// 16-B accesses, coefficients within the LDS image, 32-bit offsets within a row group.
+inline bool tn_side_ok(Cores c, const TNParams& p, const TNSide& s) {
+  if (c.core != 3 || p.Mo <= 0 || p.Ni <= 0) return false;
+  if (p.lda > TN_S3_MAX_LD || p.ldb > TN_S3_MAX_LD || p.lda2 > TN_S3_MAX_LD) return false;
+  const TNPlan pl = tn_plan(c, p.P, p.Mo, p.Ni, true, p.lda > p.ldb ? p.lda : p.ldb);
+  if (!pl.s3 || ((p.Mo | p.Ni | (int)p.lda | (int)p.ldb) & 3) != 0) return false;
+  if ((long)pl.tiles_m * pl.tiles_n * pl.splits > ABSMAX_MAX_BLOCKS) return false;
+  return s.dy != nullptr && s.z != nullptr && s.part != nullptr && s.amax != nullptr && s.rows > 0 && s.cols > 0 &&
+         s.cols <= TR_SIDE_MAX_COLS && ((s.cols | (int)s.lddy | (int)s.ldz) & 3) == 0 && s.lddy <= 65536 &&
+         s.ldz <= 65536 && al16(s.dy) && al16(s.z);
+}
+
 // C[Mo,Ni] (ld ldc) = proA(A)^T proB(B); colsum_out[Mo] = column sums of proA(A) (optional)
 template <int PROA, int PROB>
 int launch_tn(Cores c, TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, float* colsum_out,
               hipStream_t st) {   // p.amaxA / p.amaxB are filled in when the fp16-plane core measured them
+  const bool side = p.side.dy != nullptr;     // a missing carrier is an error, never a skipped pass
+  if (side && !((PROA == PRO_NONE && (PROB == PRO_NONE || PROB == PRO_BNRELU)) && tn_side_ok(c, p, p.side)))
+    return fail(PRH_ERR_ARG, "gemm_tn: this launch cannot carry a side job (Mo=%d Ni=%d P=%d)", p.Mo, p.Ni, p.P);
   if (p.Mo <= 0 || p.Ni <= 0) return PRH_OK;
   const bool ld_ok = p.lda <= TN_S3_MAX_LD && p.ldb <= TN_S3_MAX_LD && p.lda2 <= TN_S3_MAX_LD;
   long maxld = p.lda > p.ldb ? p.lda : p.ldb;
@@ -609,15 +626,25 @@ int launch_tn(Cores c, TNParams& p, float* slab, float* colsum_slab, float* C, l
           if (hipMemsetAsync(p.pace, 0, sizeof(int) * pl.splits, st) != hipSuccess)
             return fail(PRH_ERR_HIP, "gemm_tn: memset of the pacing counters failed");
         }
-        snprintf(nm, sizeof(nm), "gemm_tn_%s<%d,%d> Mo=%d Ni=%d", tr ? "h2tr" : c.tag(), PROA, PROB, p.Mo, p.Ni);
+        snprintf(nm, sizeof(nm), "gemm_tn_%s<%d,%d>%s Mo=%d Ni=%d", tr ? "h2tr" : c.tag(), PROA, PROB,
+                 side ? "+apply" : "", p.Mo, p.Ni);
         ProfScope ps(nm, 2.0 * p.P * (double)p.Mo * p.Ni, by, st);
         if constexpr (PROA == PRO_NONE && (PROB == PRO_NONE || PROB == PRO_BNRELU)) {
-          if (tr) {
+          if (tr && side) {
+            static const int attr_sd = allow_big_lds(gemm_tn_tr_kernel<PROB, true>);
+            if (attr_sd != PRH_OK) return attr_sd;
+            hipLaunchKernelGGL((gemm_tn_tr_kernel<PROB, true>), dim3((unsigned)blocks), dim3(512),
+                               TR_LDS + tr_side_lds(p.side.cols), st, p);
+            LAUNCH_CHECK();
+            hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, (const float*)p.side.part, (int)blocks,
+                               p.side.amax);
+          } else if (tr) {
             static const int attr_tr = allow_big_lds(gemm_tn_tr_kernel<PROB>);
             if (attr_tr != PRH_OK) return attr_tr;
             hipLaunchKernelGGL((gemm_tn_tr_kernel<PROB>), dim3((unsigned)blocks), dim3(512), TR_LDS, st, p);
           }
         }
+        if (side && !tr) return fail(PRH_ERR_ARG, "gemm_tn: side job without the transposed-read core");
         if (!tr) switch (c.core) {
           case 2: launch_tn_s3<PROA, PROB, 1>(p, blocks, st); break;
           case 3: launch_tn_s3<PROA, PROB, 2>(p, blocks, st); break;
@@ -848,15 +875,48 @@ int stack_forward(Cores c, const prh_bn_layer* ly, int L, const float* x, int P,
 //   complete masked gradient for l = L-1.  stats_ready: BN-backward partials of layer L-1
 //   are already in w.ws_a/ws_b.
 // Scratch: coef [3*maxc], wT [max cin*cout], slab, colslab.
-struct StackBwdScratch { float* ca; float* cb; float* cc; float* wT; float* slab; float* colslab; float* dxpad; float* hdr; };
+// hdr[2]: two headers (largest |dz| in [0], per-block maxima from [64]) - while a held wgrad still
+// reads its own layer's maximum from one, the apply pass it carries fills the other
+struct StackBwdScratch { float* ca; float* cb; float* cc; float* wT; float* slab; float* colslab; float* dxpad; float* hdr[2]; };
+
+// A wgrad <PRO_NONE, PRO_BNRELU> of materialised dz whose launch is held back until the layer below
+// has its BN-backward coefficients, so that this layer's apply pass can ride in it (TNSide)
+struct HeldWgrad { bool on = false; TNParams t; float* slab; float* colslab; float* out; long ldc; };
+int launch_held(Cores c, HeldWgrad& h, hipStream_t st) {
+  h.on = false;
+  return launch_tn<PRO_NONE, PRO_BNRELU>(c, h.t, h.slab, h.colslab, h.out, h.ldc, nullptr, st);
+}
+inline TNSide side_job(float* dy, long lddy, const float* z, long ldz, const StackBwdScratch& sc, long rows, int cols,
+                       float* hdr) {
+  TNSide s;
+  s.dy = dy; s.lddy = lddy; s.z = z; s.ldz = ldz; s.ka = sc.ca; s.kb = sc.cb; s.kc = sc.cc;
+  s.rows = rows; s.cols = cols; s.part = hdr + 64; s.amax = hdr;
+  return s;
+}
 
 int stack_backward(Cores c, const prh_bn_layer* ly, int L, const float* x, int P, int training,
                    float* dy_cat, long lddy, const float* z_cat, long ldz, const float* scale,
                    const float* shift, const float* mean, const float* rstd,
                    const prh_bn_layer_grad* gr, float* dx, StackWS& w, StackBwdScratch& sc,
-                   StatInfo si, hipStream_t st, const float* op_amax = nullptr) {
+                   StatInfo si, hipStream_t st, const float* op_amax = nullptr, const HeldWgrad* held = nullptr) {
   if (!training || c.mode != 3) op_amax = nullptr;   // slots as filled by stack_forward
   StackDims d = stack_dims(ly, L);
+  // Split-fp16 mode: the apply pass of layer l rides in the wgrad of layer l+1 (the caller's held
+  // wgrad for l = L-1), so each layer runs  finalize(l); wgrad(l+1) + apply(l); dgrad(l)  and its own
+  // wgrad waits for layer l-1.  What that moves across the other launches:
+  //  * the held wgrad reads dz_{l+1} (materialised, untouched by dgrad(l+1), which only reads it and
+  //    writes block l), its layer's maximum in sc.hdr[cur] - the apply it carries writes
+  //    sc.hdr[cur ^ 1] - and the saved activations; it reads none of ca/cb/cc, which finalize(l) has
+  //    by then overwritten with layer l's, exactly what the carried apply needs;
+  //  * its slab (sc.slab, the caller's for the held fusion wgrad) is written and reduced inside
+  //    launch_tn, back to back, so no slab is live across another wgrad; its pacing counters and, when
+  //    op_amax is absent, its measured B maximum sit behind that same slab;
+  //  * ws_a / ws_b / stat2 are produced by dgrad(l+1) and consumed by finalize(l) before the held
+  //    wgrad starts, and no wgrad touches them, wprep or wT (layer 0, whose padded wgrad borrows wT,
+  //    is never held).
+  HeldWgrad hw;
+  if (held != nullptr) hw = *held;
+  int cur = 0;                        // sc.hdr[cur]: where the newest dz maximum is (the caller's: 0)
   const float* x0 = x; long ldx = d.cin0; int k0 = d.cin0;
   if (d.cin0p != d.cin0) { x0 = w.xpad; ldx = d.cin0p; k0 = d.cin0p; }   // xpad filled by caller
   for (int l = L - 1; l >= 0; --l) {
@@ -874,9 +934,18 @@ int stack_backward(Cores c, const prh_bn_layer* ly, int L, const float* x, int P
     // 1b. split-fp16 mode: dy_l <- dz_l in place, so wgrad and dgrad read one plain operand
     const bool mat = dz_in_place(c, co, lddy, ldz);
     const float* dz_amax = nullptr;     // largest |dz_l| once known
-    if (mat) {
-      TRY(materialize_dz(dy_cat + o, lddy, z_cat + o, ldz, sc.ca, sc.cb, sc.cc, P, co, sc.hdr, st));
-      dz_amax = sc.hdr;
+    if (hw.on) {
+      const TNSide s = side_job(dy_cat + o, lddy, z_cat + o, ldz, sc, P, co, sc.hdr[cur ^ 1]);
+      if (mat && tn_side_ok(c, hw.t, s)) {
+        hw.t.side = s;
+        cur ^= 1;
+        dz_amax = sc.hdr[cur];
+      }
+      TRY(launch_held(c, hw, st));
+    }
+    if (mat && dz_amax == nullptr) {
+      TRY(materialize_dz(dy_cat + o, lddy, z_cat + o, ldz, sc.ca, sc.cb, sc.cc, P, co, sc.hdr[cur], st));
+      dz_amax = sc.hdr[cur];
     }
     // 2. wgrad: dW_l = dz_l^T h_{l-1}
     if (gr && gr[l].dw) {
@@ -895,7 +964,11 @@ int stack_backward(Cores c, const prh_bn_layer* ly, int L, const float* x, int P
         t.B = z_cat + d.off[l - 1]; t.ldb = ldz; t.Ni = ly[l].cin;
         t.qa = scale + d.off[l - 1]; t.qb = shift + d.off[l - 1];
         if (op_amax != nullptr) t.amaxB = op_amax + (l - 1);
-        if (mat) TRY((launch_tn<PRO_NONE, PRO_BNRELU>(c, t, sc.slab, sc.colslab, gr[l].dw, (long)ly[l].cin, nullptr, st)));
+        // hold it for apply(l-1) if that pass can ride (decided again, with the real job, at launch)
+        if (mat && dz_in_place(c, ly[l - 1].cout, lddy, ldz) &&
+            tn_side_ok(c, t, side_job(dy_cat + d.off[l - 1], lddy, z_cat + d.off[l - 1], ldz, sc, P, ly[l - 1].cout, sc.hdr[cur ^ 1]))) {
+          hw.on = true; hw.t = t; hw.slab = sc.slab; hw.colslab = sc.colslab; hw.out = gr[l].dw; hw.ldc = (long)ly[l].cin;
+        } else if (mat) TRY((launch_tn<PRO_NONE, PRO_BNRELU>(c, t, sc.slab, sc.colslab, gr[l].dw, (long)ly[l].cin, nullptr, st)));
         else TRY((launch_tn<PRO_BNBWD, PRO_BNRELU>(c, t, sc.slab, sc.colslab, gr[l].dw, (long)ly[l].cin, nullptr, st)));
       }
       dz_amax = t.amaxA;
@@ -932,6 +1005,7 @@ int stack_backward(Cores c, const prh_bn_layer* ly, int L, const float* x, int P
       else TRY((launch_nt<PRO_BNBWD, EPI_DGRAD>(c, p, st)));
     }
   }
+  if (hw.on) TRY(launch_held(c, hw, st));     // (layer 0 is never held: nothing below it to carry)
   return PRH_OK;
 }
 
@@ -953,7 +1027,7 @@ void stack_bwd_scratch_carve(Cores c, Arena& a, StackBwdScratch& sc, int P, cons
   int mc = max_cout(ly, L); if (extra_c > mc) mc = extra_c;
   size_t mw = max_w(ly, L); if (extra_w > mw) mw = extra_w;
   sc.ca = a.f(mc); sc.cb = a.f(mc); sc.cc = a.f(mc);
-  sc.hdr = a.f(S3_HDR_FLOATS);
+  sc.hdr[0] = a.f(S3_HDR_FLOATS); sc.hdr[1] = a.f(S3_HDR_FLOATS);
   sc.wT = a.f(mw);
   size_t slab = 0, cs = 0;
   for (int l = 0; l < L; ++l) {
@@ -1579,9 +1653,10 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
   const float* dzf_amax = nullptr;
   const bool matf = dz_in_place(c, od, (long)od, (long)od);
   if (matf) {       // split-fp16 mode: dyf <- dz_f in place
-    TRY(materialize_dz(dyf, (long)od, sv->z_fus, (long)od, sc.ca, sc.cb, sc.cc, P, od, sc.hdr, st));
-    dzf_amax = sc.hdr;
+    TRY(materialize_dz(dyf, (long)od, sv->z_fus, (long)od, sc.ca, sc.cb, sc.cc, P, od, sc.hdr[0], st));
+    dzf_amax = sc.hdr[0];
   }
+  HeldWgrad hf;       // the fusion wgrad waits for conv5's coefficients and carries its apply pass (stack_backward)
   if (gr->fusion.dw) {
     TNParams t; memset(&t, 0, sizeof(t));
     t.A = dyf; t.lda = od; t.A2 = sv->z_fus; t.lda2 = od; t.pa = sc.ca; t.pb = sc.cb; t.pc = sc.cc;
@@ -1589,7 +1664,10 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
     t.P = P; t.Mo = od; t.Ni = cat;
     t.amaxA = dzf_amax;
     if (training && c.mode == 3 && sv->op_amax != nullptr) t.amaxB = sv->op_amax + 5;
-    if (matf) TRY((launch_tn<PRO_NONE, PRO_BNRELU>(c, t, fslab, fcslab, gr->fusion.dw, (long)cat, nullptr, st)));
+    if (matf && dz_in_place(c, od, (long)cat, (long)cat) &&
+        tn_side_ok(c, t, side_job(dy_cat + d.off[4], (long)cat, sv->z_cat + d.off[4], (long)cat, sc, P, od, sc.hdr[1]))) {
+      hf.on = true; hf.t = t; hf.slab = fslab; hf.colslab = fcslab; hf.out = gr->fusion.dw; hf.ldc = (long)cat;
+    } else if (matf) TRY((launch_tn<PRO_NONE, PRO_BNRELU>(c, t, fslab, fcslab, gr->fusion.dw, (long)cat, nullptr, st)));
     else TRY((launch_tn<PRO_BNBWD, PRO_BNRELU>(c, t, fslab, fcslab, gr->fusion.dw, (long)cat, nullptr, st)));
     dzf_amax = t.amaxA;
   }
@@ -1614,7 +1692,7 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
   float* dx = d_ctx;
   TRY(stack_backward(c, prm->conv, 5, ctx, P, training, dy_cat, (long)cat, sv->z_cat, (long)cat,
                      sv->bn_scale, sv->bn_shift, sv->bn_mean, sv->bn_rstd, gr->conv, dx, w, sc, si5,
-                     st, sv->op_amax));
+                     st, sv->op_amax, &hf));
 
   // (4) intensity gate: dW2 = dG^T u, db2 = colsum dG; dU = dG W2 masked by u>0 with
   //     column sums (db1) and intensity-weighted column sums (dw1)
@@ -3067,6 +3145,39 @@ int prh_test_gemm_tn(const float* a, const float* b, float* c, float* colsum, in
   TNParams t; memset(&t, 0, sizeof(t));
   t.A = a; t.lda = mo; t.B = b; t.ldb = ni; t.P = p; t.Mo = mo; t.Ni = ni;
   return launch_tn<PRO_NONE, PRO_NONE>(cores, t, slab, cs, c, (long)ni, colsum, (hipStream_t)stream);
+}
+// The same raw wgrad with a BatchNorm-backward apply pass over dy [rows, cols]: side != 0, carried by
+// the wgrad launch (an error where the transposed-read core does not serve it); side == 0, the
+// stand-alone pass (materialize_dz) followed by the plain wgrad.  amax_out (device): max|dz|.
+size_t prh_test_gemm_tn_side_workspace_bytes(int p, int mo, int ni) {
+  return prh_test_gemm_tn_workspace_bytes(p, mo, ni) + (size_t)S3_HDR_FLOATS * sizeof(float) + 256;
+}
+int prh_test_gemm_tn_side(const float* a, const float* b, float* c, float* colsum, int p, int mo, int ni,
+                          float* dy, long lddy, const float* z, long ldz, const float* ka, const float* kb,
+                          const float* kc, long rows, int cols, int side, float* amax_out, void* workspace,
+                          size_t workspace_bytes, int device, void* stream) {
+  HIP_TRY(hipSetDevice(device));
+  if (!dy || !z || !ka || !kb || !kc || !amax_out || rows <= 0 || cols <= 0 || (cols & 3) || (lddy & 3) || (ldz & 3) ||
+      lddy < cols || ldz < cols)
+    return fail(PRH_ERR_ARG, "test_gemm_tn_side: bad side matrix");
+  const Cores cores = cores_of(gemm_mode());
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(workspace, workspace_bytes);
+  float* slab = ar.f(tn_slab_floats(cores, p, mo, ni));
+  float* cs = ar.f(tn_colsum_floats(cores, p, mo, ni));
+  float* hdr = ar.f(S3_HDR_FLOATS);
+  if (!ar.ok) return fail(PRH_ERR_WORKSPACE, "test_gemm_tn_side: workspace too small");
+  TNParams t; memset(&t, 0, sizeof(t));
+  t.A = a; t.lda = mo; t.B = b; t.ldb = ni; t.P = p; t.Mo = mo; t.Ni = ni;
+  if (side) {
+    t.side.dy = dy; t.side.lddy = lddy; t.side.z = z; t.side.ldz = ldz; t.side.ka = ka; t.side.kb = kb; t.side.kc = kc;
+    t.side.rows = rows; t.side.cols = cols; t.side.part = hdr + 64; t.side.amax = hdr;
+  } else {
+    TRY(materialize_dz(dy, lddy, z, ldz, ka, kb, kc, rows, cols, hdr, st));
+  }
+  TRY((launch_tn<PRO_NONE, PRO_NONE>(cores, t, slab, cs, c, (long)ni, colsum, st)));
+  HIP_TRY(hipMemcpyAsync(amax_out, hdr, sizeof(float), hipMemcpyDeviceToDevice, st));
+  return PRH_OK;
 }
 
 }  // extern "C"
