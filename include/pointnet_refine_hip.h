@@ -592,6 +592,71 @@ int prh_bev_draw(const double* segments, const int* segment_line, int n_segments
                  long long n_tiles, long long n_items, unsigned* canvas, void* workspace, size_t workspace_bytes,
                  int device, void* stream);
 
+/* ---- 3-D scene views (inference_whole_scene.py:242-404, tools/visualize_data.py,
+ * check_global_align.py and visualize_sampled_pointcloud.py of the reference) ------------------
+ * Depth-buffered point splats and polylines under orbit cameras; every point of the cloud is drawn.
+ *
+ * 3-D views - the rule.
+ * Camera.  A camera is an fp64 row of 16 values: eye[3], r[3], u[3], f[3], s, near, ortho, 0.  An
+ * orbit camera about a target c at elevation e, azimuth a (matplotlib's view_init convention) and
+ * distance D has eye = c + D * (cos e cos a, cos e sin a, sin e), right r = (-sin a, cos a, 0), up
+ * u = (-sin e cos a, -sin e sin a, cos e), forward f = -(cos e cos a, cos e sin a, sin e); nothing
+ * is singular at e = +-90 degrees.  Perspective (ortho = 0): s = (H / 2) / tan(fov / 2) pixels.
+ * Orthographic (ortho != 0): s = pixels per metre.  The host builds the rows; the device evaluates
+ * no trigonometric function and no square root.
+ * Projection of a point p, all in fp64, no contraction, one rounding per operation, in this order:
+ * q = p - eye; xr = (q0 * r0 + q1 * r1) + q2 * r2, yu and d likewise with u and f; the point is
+ * dropped unless d >= near; k = ortho ? s : s / d; X = W / 2 + xr * k, Y = H / 2 - yu * k; the
+ * pixel is (row floor(Y), column floor(X)), pixel centres at (+0.5, +0.5).  float32 inputs are
+ * promoted exactly.
+ * Depth word.  A pixel holds one 64-bit word (bits(float32(depth)) << 32) | payload; the empty
+ * word is all ones; every write is a 64-bit unsigned atomic minimum, so the buffer does not depend
+ * on arrival order.  A depth below zero (possible only through a line's bias) counts as +0.  Point
+ * payload: 0x01000000 | lut, lut = clamp(floor((I - cmin) / (cmax - cmin) * 256), 0, 255), clamped
+ * before the integer conversion.  Line payload: the line's index (< 2^24).  At equal depth a line
+ * beats a point, a lower line index a higher one, a lower colour index a higher one.
+ * Splat.  A point covers the size x size pixels at offsets i - size / 2 (integer division), i = 0 ..
+ * size - 1, on both axes, size 1..9, all with the point's depth word; pixels outside the image are
+ * skipped.  A NaN or infinite x, y, z or intensity sets *bad and is skipped.
+ * Lines.  The host cuts every segment of a (polyline, view) pair to d >= near by linear
+ * interpolation in view space and projects it without the floor.  A segment is ax ay bx by
+ * (pixels), arc_a (screen arc length at a from the line's first drawn vertex), L (its screen
+ * length), wa, wb (1 / d in a perspective view, d in an orthographic one), with its line and view.
+ * A style is r g b, width, marker, dash_on, dash_off (pixels) and bias (metres).  For a pixel
+ * centre c: t = clamp(((c - a).(b - a)) / |b - a|^2, 0, 1), t = 0 for a zero-length segment.  With
+ * width > 0 the segment covers the pixel when |c - (a + t (b - a))|^2 <= (width / 2)^2 and
+ * (dash_off == 0 or fmod(arc_a + t * L, dash_on + dash_off) < dash_on), at depth 1 / ((1 - t) * wa
+ * + t * wb) (perspective-correct) or (1 - t) * wa + t * wb (orthographic).  With marker > 0 vertex a
+ * covers it when |c - a|^2 <= (marker / 2)^2, at a's depth (1 / wa or wa), and b likewise.  The
+ * smallest of these depths, minus bias, forms the word.  Edges are hard: no blending, no
+ * transparency; order-independent transparency is out of scope.
+ * Resolve.  Empty -> the background colour; a point word -> table[lut]; a line word -> the line's
+ * colour; alpha 255.  The depth image is float32, +inf where the pixel is empty.
+ *
+ * points [n,4] x y z intensity, fp32 or fp64 (is_double), contiguous.  prh_view_bounds: info [7]
+ * fp64 = x_min x_max y_min y_max z_min z_max (exact) and 1.0 when a value is NaN or infinite.
+ * zbuf [n_views,height,width] 64-bit words.  prh_view_splat: cameras [n_views,16], at most
+ * prh_view_max_views() per call; offsets NULL: every point into every view; else point i of slice
+ * s (offsets [n_slices+1]) goes into view v when slice_mask[s * n_views + v] != 0.  One pass over
+ * the points.  prh_view_lines: segments [n_segments,8], segment_ids [n_segments,2] int32 = line,
+ * view; styles [n_lines,8]; one workgroup per segment walks its bounding box grown by max(width,
+ * marker) / 2.  prh_view_resolve: table [256] and line_colours [n_lines] packed RGBA (R in the low
+ * byte), background likewise; rgba [pixels], depth [pixels].  Bitwise reproducible. */
+size_t prh_view_bounds_workspace_bytes(void);
+int prh_view_bounds(const void* points, long long n, int is_double, double* info, void* workspace,
+                    size_t workspace_bytes, int device, void* stream);
+int prh_view_clear(unsigned long long* zbuf, int n_views, int height, int width, int device, void* stream);
+int prh_view_max_views(void);
+int prh_view_splat(const void* points, long long n, int is_double, const double* cameras, int n_views,
+                   const long long* offsets, int n_slices, const unsigned char* slice_mask, int size, double cmin,
+                   double cmax, int height, int width, unsigned long long* zbuf, int* bad, int device, void* stream);
+int prh_view_lines(const double* segments, const int* segment_ids, int n_segments, const double* styles,
+                   int n_lines, const double* cameras, int n_views, int height, int width, unsigned long long* zbuf,
+                   int device, void* stream);
+int prh_view_resolve(const unsigned long long* zbuf, long long pixels, const unsigned* table,
+                     const unsigned* line_colours, int n_lines, unsigned background, unsigned* rgba, float* depth,
+                     int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

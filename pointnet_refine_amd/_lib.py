@@ -86,6 +86,8 @@ EXPORTS = [
     "prh_bev_bounds_workspace_bytes", "prh_bev_bounds", "prh_bev_raster", "prh_bev_select_workspace_bytes",
     "prh_bev_select", "prh_bev_tone", "prh_bev_colorize", "prh_bev_crop", "prh_bev_tile", "prh_bev_draw_count",
     "prh_bev_draw_workspace_bytes", "prh_bev_draw",
+    "prh_view_bounds_workspace_bytes", "prh_view_bounds", "prh_view_clear", "prh_view_max_views", "prh_view_splat",
+    "prh_view_lines", "prh_view_resolve",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -279,6 +281,20 @@ def _bind(lib):
     lib.prh_bev_draw_workspace_bytes.argtypes = [ll, ll]
     lib.prh_bev_draw.restype = i
     lib.prh_bev_draw.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, ll, ll, vp, vp, sz, i, vp]
+    lib.prh_view_bounds_workspace_bytes.restype = sz
+    lib.prh_view_bounds_workspace_bytes.argtypes = []
+    lib.prh_view_bounds.restype = i
+    lib.prh_view_bounds.argtypes = [vp, ll, i, vp, vp, sz, i, vp]
+    lib.prh_view_clear.restype = i
+    lib.prh_view_clear.argtypes = [vp, i, i, i, i, vp]
+    lib.prh_view_max_views.restype = i
+    lib.prh_view_max_views.argtypes = []
+    lib.prh_view_splat.restype = i
+    lib.prh_view_splat.argtypes = [vp, ll, i, vp, i, vp, i, vp, i, dbl, dbl, i, i, vp, vp, i, vp]
+    lib.prh_view_lines.restype = i
+    lib.prh_view_lines.argtypes = [vp, vp, i, vp, i, vp, i, i, i, vp, i, vp]
+    lib.prh_view_resolve.restype = i
+    lib.prh_view_resolve.argtypes = [vp, ll, vp, vp, i, C.c_uint, vp, vp, i, vp]
     lib.prh_pcd_group_rows.restype = i
     lib.prh_pcd_group_rows.argtypes = []
     lib.prh_pcd_format_workspace_bytes.restype = sz

@@ -28,6 +28,7 @@
 #include "prh_drive.hpp"
 #include "prh_match.hpp"
 #include "prh_bev.hpp"
+#include "prh_view.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
@@ -2867,6 +2868,102 @@ int prh_bev_draw(const double* segments, const int* segment_line, int n_segments
   LAUNCH_CHECK();
   hipLaunchKernelGGL(bev_draw_kernel, dim3((unsigned)n_tiles), dim3(BEV_THREADS), 0, st, segments, segment_line, styles,
                      view_dims, tile_base, pixel_offsets, tile_view, tile_offsets, (const int*)items, sorted, canvas);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ 3-D views
+size_t prh_view_bounds_workspace_bytes(void) {
+  return align_up((size_t)VIEW_BOUNDS_BLOCKS * 6 * sizeof(double), 256) + align_up((size_t)VIEW_BOUNDS_BLOCKS * sizeof(int), 256);
+}
+int prh_view_bounds(const void* points, long long n, int is_double, double* info, void* workspace,
+                    size_t workspace_bytes, int device, void* stream) {
+  if (n <= 0 || !points || !info) return fail(PRH_ERR_ARG, "view_bounds: bad argument");
+  if (!workspace || workspace_bytes < prh_view_bounds_workspace_bytes())
+    return fail(PRH_ERR_WORKSPACE, "view_bounds: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* bad = (int*)((char*)workspace + align_up((size_t)VIEW_BOUNDS_BLOCKS * 6 * sizeof(double), 256));
+  const long long want = (n + VIEW_THREADS - 1) / VIEW_THREADS;
+  const int nblk = (int)(want < VIEW_BOUNDS_BLOCKS ? want : VIEW_BOUNDS_BLOCKS);
+  if (is_double) {
+    hipLaunchKernelGGL(view_bounds_kernel<double>, dim3(nblk), dim3(VIEW_THREADS), 0, st, (const double*)points, n,
+                       (double*)workspace, bad);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(view_bounds_final<double>, dim3(1), dim3(VIEW_THREADS), 0, st, (const double*)workspace,
+                       (const int*)bad, nblk, info);
+  } else {
+    hipLaunchKernelGGL(view_bounds_kernel<float>, dim3(nblk), dim3(VIEW_THREADS), 0, st, (const float*)points, n,
+                       (float*)workspace, bad);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(view_bounds_final<float>, dim3(1), dim3(VIEW_THREADS), 0, st, (const float*)workspace,
+                       (const int*)bad, nblk, info);
+  }
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+static bool view_image_ok(int n_views, int height, int width) {
+  return n_views >= 0 && height >= 0 && width >= 0 && height < (1 << 24) && width < (1 << 24) &&
+         (long long)n_views * height * width < 256ll * 0x7fffffff;
+}
+int prh_view_clear(unsigned long long* zbuf, int n_views, int height, int width, int device, void* stream) {
+  if (!view_image_ok(n_views, height, width)) return fail(PRH_ERR_ARG, "view_clear: bad argument");
+  const long long cells = (long long)n_views * height * width;
+  if (cells == 0) return PRH_OK;
+  if (!zbuf) return fail(PRH_ERR_ARG, "view_clear: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(view_clear_kernel, dim3((unsigned)((cells + VIEW_THREADS - 1) / VIEW_THREADS)), dim3(VIEW_THREADS),
+                     0, (hipStream_t)stream, zbuf, cells);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_view_max_views(void) { return VIEW_MAX_VIEWS; }
+int prh_view_splat(const void* points, long long n, int is_double, const double* cameras, int n_views,
+                   const long long* offsets, int n_slices, const unsigned char* slice_mask, int size, double cmin,
+                   double cmax, int height, int width, unsigned long long* zbuf, int* bad, int device, void* stream) {
+  if (n < 0 || !view_image_ok(n_views, height, width) || n_views > VIEW_MAX_VIEWS || size < 1 || size > VIEW_MAX_SPLAT ||
+      n_slices < 0 || !bad || n >= 256ll * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "view_splat: bad argument");
+  if ((offsets != nullptr) != (slice_mask != nullptr) || (offsets && n_slices < 1))
+    return fail(PRH_ERR_ARG, "view_splat: offsets and slice_mask go together");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
+  if (n == 0 || (long long)n_views * height * width == 0) return PRH_OK;
+  if (!points || !cameras || !zbuf) return fail(PRH_ERR_ARG, "view_splat: null pointer");
+  const long long per_block = (long long)VIEW_THREADS * VIEW_POINTS_PER_THREAD;
+  const unsigned nblk = (unsigned)((n + per_block - 1) / per_block);
+  if (is_double)
+    hipLaunchKernelGGL(view_splat_kernel<double>, dim3(nblk), dim3(VIEW_THREADS), 0, st, (const double*)points, n, cameras,
+                       n_views, offsets, n_slices, slice_mask, size, cmin, cmax, height, width, zbuf, bad);
+  else
+    hipLaunchKernelGGL(view_splat_kernel<float>, dim3(nblk), dim3(VIEW_THREADS), 0, st, (const float*)points, n, cameras,
+                       n_views, offsets, n_slices, slice_mask, size, cmin, cmax, height, width, zbuf, bad);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_view_lines(const double* segments, const int* segment_ids, int n_segments, const double* styles,
+                   int n_lines, const double* cameras, int n_views, int height, int width, unsigned long long* zbuf,
+                   int device, void* stream) {
+  if (n_segments < 0 || n_lines < 0 || n_lines > (1 << 24) || !view_image_ok(n_views, height, width)) return fail(PRH_ERR_ARG, "view_lines: bad argument");
+  if (n_segments == 0 || (long long)n_views * height * width == 0) return PRH_OK;
+  if (!segments || !segment_ids || !styles || !cameras || !zbuf) return fail(PRH_ERR_ARG, "view_lines: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(view_lines_kernel, dim3((unsigned)n_segments), dim3(VIEW_THREADS), 0, (hipStream_t)stream, segments,
+                     segment_ids, styles, n_lines, cameras, n_views, height, width, zbuf);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_view_resolve(const unsigned long long* zbuf, long long pixels, const unsigned* table,
+                     const unsigned* line_colours, int n_lines, unsigned background, unsigned* rgba, float* depth,
+                     int device, void* stream) {
+  if (pixels < 0 || pixels >= 256ll * 0x7fffffff || n_lines < 0) return fail(PRH_ERR_ARG, "view_resolve: bad argument");
+  if (pixels == 0) return PRH_OK;
+  if (!zbuf || !table || !rgba || !depth || (n_lines > 0 && !line_colours))
+    return fail(PRH_ERR_ARG, "view_resolve: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(view_resolve_kernel, dim3((unsigned)((pixels + VIEW_THREADS - 1) / VIEW_THREADS)), dim3(VIEW_THREADS),
+                     0, (hipStream_t)stream, zbuf, pixels, table, line_colours, n_lines, background, rgba, depth);
   LAUNCH_CHECK();
   return PRH_OK;
 }
