@@ -657,6 +657,70 @@ int prh_view_resolve(const unsigned long long* zbuf, long long pixels, const uns
                      const unsigned* line_colours, int n_lines, unsigned background, unsigned* rgba, float* depth,
                      int device, void* stream);
 
+/* ---- map fusion: the refined pieces of a drive merged into one map in the drive frame --------
+ * The reference stops at per-slice arrays in per-slice ego frames; it has no counterpart of this
+ * stage, so the rule below is the specification (tests/_fuse_oracle.py restates it in numpy).
+ *
+ * Map fusion - the rule.
+ * All arithmetic is fp64, one rounding per operation, no contraction; a dot product of two
+ * 3-vectors is (p0 * q0 + p1 * q1) + p2 * q2, |p|^2 = p.p.  The host subtracts an origin from every
+ * carrier vertex and every pose translation before the upload and adds it back to the fused
+ * vertices; the default origin is the first pose's translation with each component rounded down
+ * to a multiple of 1000 m, so device coordinates stay within a few km of zero.
+ * Inputs.  n_lines carrier polylines in CSR form (line_offsets [n_lines+1]) with the cumulative
+ * 3-D arc length cum of each, computed on the host from the shifted vertices: cum[0] = 0, cum[k+1]
+ * = cum[k] + sqrt(|V[k+1] - V[k]|^2), sequentially; the same bits go to the device and to the
+ * oracle.  n_pieces pieces of M points each (2 <= M <= prh_fuse_max_points() = 64) in ego
+ * coordinates, each with a line and a pose index; poses [S,7] = x y z qx qy qz qw.  Pieces are
+ * grouped by line in ascending line order, and the caller's order within a line is kept.
+ * 1. To the drive frame.  w = R(q) p + t, each component ((R0 p0 + R1 p1) + R2 p2) + t, with R the
+ *    rotation matrix of the normalised quaternion: the transpose of the matrix the drive slicer
+ *    applies (local = R^T (p - t)), built by the same code.
+ * 2. Projection of w onto its carrier.  For every segment k = (a, b) = (V[k], V[k+1]) with e = b - a
+ *    and L2 = e.e > 0: u = clamp(((w - a).e) / L2, 0, 1), c = a + u e, d2 = |w - c|^2.  The first k
+ *    with the strictly smallest d2 wins (seg = k); s = cum[k] + u (cum[k+1] - cum[k]), d = sqrt(d2).
+ *    A carrier without such a segment gives seg = -1, s = 0 and d = sqrt(|w - V[0]|^2).
+ * 3. Taper.  Point i of a piece weighs t_i = min(i + 1, M - i): piece ends sit at slice edges,
+ *    where the context tube is cut off, so they count least.
+ * 4. Nodes.  A line with at least one vertex has the nodes j = 0 .. floor(cum_total / ds) at arc
+ *    position (double)j * ds (a line without vertices has none).  Piece segment i = (point i, point
+ *    i + 1) is used only if s[i+1] > s[i]; it contributes to every node with s[i] <= j ds < s[i+1]:
+ *    u = (j ds - s[i]) / (s[i+1] - s[i]), weight om = t_i + u (t_{i+1} - t_i), position x = w_i + u
+ *    (w_{i+1} - w_i).  A piece that runs against its carrier contributes nothing and one that
+ *    doubles back contributes more than once; both follow from the rule and are kept.
+ * 5. Node result.  C = number of contributions, W = sum om, X = (sum om x) / W, spread = sqrt((sum
+ *    om |x - X|^2) / W), the last taken in a second sweep once X is known; every sum starts at 0
+ *    and runs over the line's pieces in the caller's order, then ascending i, so the output is
+ *    bitwise reproducible and independent of the launch shape.  A node with C = 0 gets X = 0, W =
+ *    0, spread = 0.
+ * 6. Polylines (host).  The fused polylines of a line are its nodes with C >= min_count (default
+ *    1) in node order; two consecutive used nodes j < j' with (j' - j) ds > max_gap (default 5.0
+ *    m) belong to different polylines; polylines of fewer than 2 nodes are dropped.
+ *
+ * prh_fuse_project: one thread per piece point, steps 1-2.  pieces [n_pieces*M,3]; piece_pose NULL:
+ * the points are in the drive frame already (M >= 1 is enough here); piece_line NULL: step 1 only,
+ * s / d / seg are not written.  world [n_pieces*M,3], s, d [n_pieces*M] fp64, seg [n_pieces*M]
+ * int32.  Carrier vertices and cum go through LDS prh_fuse_tile() segments at a time, so a carrier
+ * may be of any length.  A piece whose line index is outside 0..n_lines-1 gets seg = -1, s = d = 0;
+ * one whose pose index is outside 0..n_poses-1 gets NaN.
+ * prh_fuse_gather: one thread per node, steps 3-5 as a gather over the line's pieces: no atomics,
+ * no sort.  line_piece_offsets [n_lines+1]: line l owns pieces line_piece_offsets[l] ..
+ * line_piece_offsets[l+1]; node_offsets [n_lines+1] likewise for the nodes, node j of line l at
+ * (double)j * ds.  node_x [n_nodes,3], node_w, node_spread [n_nodes] fp64, node_count [n_nodes]
+ * int32. */
+int prh_fuse_max_points(void);
+int prh_fuse_tile(void);
+size_t prh_fuse_project_workspace_bytes(int n_poses);
+int prh_fuse_project(const double* pieces, long long n_pieces, int points_per_piece, const int* piece_line,
+                     const int* piece_pose, const double* poses, int n_poses, const double* line_vertices,
+                     const long long* line_offsets, const double* line_cum, int n_lines, double* world, double* s,
+                     double* d, int* seg, void* workspace, size_t workspace_bytes, int device, void* stream);
+size_t prh_fuse_gather_workspace_bytes(long long n_pieces);
+int prh_fuse_gather(const double* world, const double* s, long long n_pieces, int points_per_piece,
+                    const long long* line_piece_offsets, int n_lines, const long long* node_offsets,
+                    long long n_nodes, double ds, double* node_x, double* node_w, int* node_count,
+                    double* node_spread, void* workspace, size_t workspace_bytes, int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

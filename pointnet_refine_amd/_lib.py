@@ -88,6 +88,8 @@ EXPORTS = [
     "prh_bev_draw_workspace_bytes", "prh_bev_draw",
     "prh_view_bounds_workspace_bytes", "prh_view_bounds", "prh_view_clear", "prh_view_max_views", "prh_view_splat",
     "prh_view_lines", "prh_view_resolve",
+    "prh_fuse_max_points", "prh_fuse_tile", "prh_fuse_project_workspace_bytes", "prh_fuse_project",
+    "prh_fuse_gather_workspace_bytes", "prh_fuse_gather",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -295,6 +297,18 @@ def _bind(lib):
     lib.prh_view_lines.argtypes = [vp, vp, i, vp, i, vp, i, i, i, vp, i, vp]
     lib.prh_view_resolve.restype = i
     lib.prh_view_resolve.argtypes = [vp, ll, vp, vp, i, C.c_uint, vp, vp, i, vp]
+    lib.prh_fuse_max_points.restype = i
+    lib.prh_fuse_max_points.argtypes = []
+    lib.prh_fuse_tile.restype = i
+    lib.prh_fuse_tile.argtypes = []
+    lib.prh_fuse_project_workspace_bytes.restype = sz
+    lib.prh_fuse_project_workspace_bytes.argtypes = [i]
+    lib.prh_fuse_project.restype = i
+    lib.prh_fuse_project.argtypes = [vp, ll, i, vp, vp, vp, i, vp, vp, vp, i, vp, vp, vp, vp, vp, sz, i, vp]
+    lib.prh_fuse_gather_workspace_bytes.restype = sz
+    lib.prh_fuse_gather_workspace_bytes.argtypes = [ll]
+    lib.prh_fuse_gather.restype = i
+    lib.prh_fuse_gather.argtypes = [vp, vp, ll, i, vp, i, vp, ll, dbl, vp, vp, vp, vp, vp, sz, i, vp]
     lib.prh_pcd_group_rows.restype = i
     lib.prh_pcd_group_rows.argtypes = []
     lib.prh_pcd_format_workspace_bytes.restype = sz

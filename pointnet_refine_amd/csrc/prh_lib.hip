@@ -29,6 +29,7 @@
 #include "prh_match.hpp"
 #include "prh_bev.hpp"
 #include "prh_view.hpp"
+#include "prh_fuse.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
@@ -2964,6 +2965,75 @@ int prh_view_resolve(const unsigned long long* zbuf, long long pixels, const uns
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(view_resolve_kernel, dim3((unsigned)((pixels + VIEW_THREADS - 1) / VIEW_THREADS)), dim3(VIEW_THREADS),
                      0, (hipStream_t)stream, zbuf, pixels, table, line_colours, n_lines, background, rgba, depth);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ map fusion
+int prh_fuse_max_points(void) { return FUSE_MAX_POINTS; }
+int prh_fuse_tile(void) { return FUSE_TILE; }
+size_t prh_fuse_project_workspace_bytes(int n_poses) {
+  if (n_poses < 0) return 0;
+  return align_up((size_t)n_poses * sizeof(DrvPose), 256) + 256;
+}
+int prh_fuse_project(const double* pieces, long long n_pieces, int points_per_piece, const int* piece_line,
+                     const int* piece_pose, const double* poses, int n_poses, const double* line_vertices,
+                     const long long* line_offsets, const double* line_cum, int n_lines, double* world, double* s,
+                     double* d, int* seg, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const int M = points_per_piece;
+  if (n_pieces < 0 || M < 1 || n_poses < 0 || n_lines < 0) return fail(PRH_ERR_ARG, "fuse_project: bad argument");
+  if (n_pieces > (long long)FUSE_THREADS * 0x7fffffff / M) return fail(PRH_ERR_ARG, "fuse_project: too many points");
+  if (n_pieces == 0) return PRH_OK;
+  if (!pieces || !world) return fail(PRH_ERR_ARG, "fuse_project: null pointer");
+  if (piece_pose && (!poses || n_poses == 0)) return fail(PRH_ERR_ARG, "fuse_project: piece_pose without poses");
+  if (piece_line && (!s || !d || !seg || (n_lines > 0 && (!line_offsets || !line_vertices || !line_cum))))
+    return fail(PRH_ERR_ARG, "fuse_project: null pointer");
+  if (piece_pose && (!workspace || workspace_bytes < prh_fuse_project_workspace_bytes(n_poses)))
+    return fail(PRH_ERR_WORKSPACE, "fuse_project: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  DrvPose* pose = (DrvPose*)workspace;
+  if (piece_pose) {
+    hipLaunchKernelGGL(drv_pose_kernel, dim3(cdiv(n_poses, 256)), dim3(256), 0, st, poses, n_poses, pose);
+    LAUNCH_CHECK();
+  }
+  const long long n_points = n_pieces * M;
+  hipLaunchKernelGGL(fuse_project_kernel, dim3((unsigned)((n_points + FUSE_THREADS - 1) / FUSE_THREADS)),
+                     dim3(FUSE_THREADS), 0, st, pieces, n_points, M, piece_line, piece_pose, (const DrvPose*)pose,
+                     n_poses, line_vertices, line_offsets, line_cum, n_lines, world, s, d, seg);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+size_t prh_fuse_gather_workspace_bytes(long long n_pieces) {
+  if (n_pieces < 0) return 0;
+  return align_up((size_t)n_pieces * 2 * sizeof(double), 256) + 256;
+}
+int prh_fuse_gather(const double* world, const double* s, long long n_pieces, int points_per_piece,
+                    const long long* line_piece_offsets, int n_lines, const long long* node_offsets,
+                    long long n_nodes, double ds, double* node_x, double* node_w, int* node_count,
+                    double* node_spread, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const int M = points_per_piece;
+  if (n_pieces < 0 || n_lines < 0 || n_nodes < 0 || M < 2 || M > FUSE_MAX_POINTS || !(ds > 0.0))
+    return fail(PRH_ERR_ARG, "fuse_gather: bad argument (2..%d points per piece, ds > 0)", FUSE_MAX_POINTS);
+  if (n_nodes >= (long long)FUSE_THREADS * 0x7fffffff || n_pieces >= (long long)FUSE_THREADS * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "fuse_gather: too many nodes or pieces");
+  if (n_nodes == 0) return PRH_OK;
+  if (n_lines == 0 || !line_piece_offsets || !node_offsets || !node_x || !node_w || !node_count || !node_spread ||
+      (n_pieces > 0 && (!world || !s)))
+    return fail(PRH_ERR_ARG, "fuse_gather: null pointer");
+  if (!workspace || workspace_bytes < prh_fuse_gather_workspace_bytes(n_pieces))
+    return fail(PRH_ERR_WORKSPACE, "fuse_gather: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  double* range = (double*)workspace;
+  if (n_pieces > 0) {
+    hipLaunchKernelGGL(fuse_range_kernel, dim3((unsigned)((n_pieces + FUSE_THREADS - 1) / FUSE_THREADS)),
+                       dim3(FUSE_THREADS), 0, st, s, n_pieces, M, range);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(fuse_gather_kernel, dim3((unsigned)((n_nodes + FUSE_THREADS - 1) / FUSE_THREADS)),
+                     dim3(FUSE_THREADS), 0, st, world, s, (const double*)range, M, line_piece_offsets, n_lines,
+                     node_offsets, n_nodes, ds, node_x, node_w, node_count, node_spread);
   LAUNCH_CHECK();
   return PRH_OK;
 }

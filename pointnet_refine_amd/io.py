@@ -94,11 +94,12 @@ def refine_scene(model, pcd_points, raw_lines, num_line_points=32, num_context_p
 
 @torch.no_grad()
 def scene_offsets(model, pcd_points, raw_lines, num_line_points=32, num_context_points=1024,
-                  crop_radius=0.3, decay_scale=2.0, batch_lines=2048, seed=0, precision=None):
+                  crop_radius=0.3, decay_scale=2.0, batch_lines=2048, seed=0, precision=None, return_counts=False):
     """The model side of refine_scene for a non-empty list of lines: contexts from the GPU builder
     and the batched eval forward.  Returns CUDA float32 tensors (offset (L,M,3) = last-layer
     output, noisy_c (L,M,3) = resampled line centred on centres (L,3)); the refined line is
-    noisy_c + centres + offset."""
+    noisy_c + centres + offset.  return_counts=True adds build_contexts' counts (L,) int32: the
+    cloud points each line's tube held."""
     dev = next(model.parameters()).device
     cloud = pcd_points if torch.is_tensor(pcd_points) else torch.from_numpy(np.ascontiguousarray(pcd_points, dtype=np.float32))
     cloud = cloud.to(dev, torch.float32)
@@ -119,12 +120,13 @@ def scene_offsets(model, pcd_points, raw_lines, num_line_points=32, num_context_
         with mode_scope:
             if precision is not None and enc is not None:
                 enc.inference_precision = None if precision == "layers" else precision
-            ctx, noisy_c, centres, _ = build_contexts(cloud, raw_lines, num_line_points, num_context_points,
-                                                      crop_radius, decay_scale, seed)
+            ctx, noisy_c, centres, counts = build_contexts(cloud, raw_lines, num_line_points, num_context_points,
+                                                           crop_radius, decay_scale, seed)
             outs = []
             for s in range(0, ctx.shape[0], batch_lines):
                 outs.append(model(ctx[s:s + batch_lines], noisy_c[s:s + batch_lines])[-1])   # last layer, :139-141
-            return torch.cat(outs), noisy_c, centres
+            offset = torch.cat(outs)
+            return (offset, noisy_c, centres, counts) if return_counts else (offset, noisy_c, centres)
     finally:
         model.train(was_training)
         if enc is not None:
