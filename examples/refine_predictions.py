@@ -1,0 +1,110 @@
+"""A detector run in, one refined lane map out, with no ground truth in between: every camera
+frame's BEV-pixel polylines are refined in their ego frame, the refined pieces are linked across
+frames into lanes and fused into one polyline per lane in the drive frame
+(pointnet_refine_amd/link.py).
+
+    python examples/refine_predictions.py DRIVE_DIR RESULTS_JSON --checkpoint CKPT --out MAP.json
+                                          [--gt GT_JSON] [--png DIR]
+
+DRIVE_DIR holds pose/*.json and merged.pcd; RESULTS_JSON is the detector's output
+(predictions.load_results); MAP.json gets the fused map in the drive file layout
+(items[].category / attributes / position), one item per polyline with its cluster as 'source_line'.
+With --gt every fused cluster is attributed to the ground-truth line of smallest mean distance
+(fuse.project_to_lines) and the map's distance to those lines is printed (fuse.map_error).
+--png DIR draws the fused map over a BEV intensity map of the merged cloud (bev.py).
+
+Without --checkpoint the model carries deterministic procedural weights (the run then exercises the
+path and says nothing about accuracy).
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PNG_RESOLUTION = 0.1         # metres per pixel of the --png picture
+
+
+def load_model(checkpoint):
+    from pointnet_refine_amd.model import LineRefineNet
+    model = LineRefineNet()
+    if checkpoint:
+        model.load_state_dict(torch.load(checkpoint, map_location="cpu"))
+        print(f"Loaded model from {checkpoint}")
+    else:
+        from oracle import procedural as P
+        model.load_state_dict(P.linerefine_state_dict(0))
+        print("No checkpoint: procedural weights")
+    return model.cuda().eval()
+
+
+def attribute(fused, gt):
+    """Per fused cluster the GT line of smallest mean distance over the cluster's vertices."""
+    from pointnet_refine_amd import fuse
+    owner = []
+    for parts in fused:
+        pts = np.concatenate(parts) if parts else np.zeros((0, 3))
+        if len(pts) == 0 or not gt:
+            owner.append(-1)
+            continue
+        means = [float(fuse.project_to_lines(pts, np.full(len(pts), l), gt)[1].mean()) if len(gt[l]) else np.inf
+                 for l in range(len(gt))]
+        owner.append(int(np.argmin(means)))
+    return owner
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("drive_dir")
+    ap.add_argument("results_json")
+    ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--gt", default=None)
+    ap.add_argument("--png", default=None)
+    ap.add_argument("--step", type=float, default=0.5)
+    ap.add_argument("--gate", type=float, default=1.0)
+    ap.add_argument("--min-pieces", type=int, default=2)
+    args = ap.parse_args()
+
+    from pointnet_refine_amd import drive, fuse, link
+    res = link.refine_predictions(load_model(args.checkpoint), args.drive_dir, args.results_json, seed=args.seed,
+                                  step=args.step, gate=args.gate, min_pieces=args.min_pieces)
+    rep = res["report"]
+    print(f"{rep['slices']} frames, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
+          f"{rep['candidates']} candidate pairs, {rep['edges']} edges, {rep['clusters']} clusters, "
+          f"{rep['clusters_kept']} kept ({rep['pieces_unlinked']} pieces unlinked), "
+          f"{rep['nodes_used']} of {rep['nodes']} nodes used, {rep['fused_polylines']} polylines")
+    fused = res["fused"]
+    n = fuse.write_map_json(args.out, fused, categories=["lane_line"] * len(fused))
+    print(f"Wrote {n} polylines to {args.out}")
+    if args.gt is not None:
+        gt = [it["points"] for it in drive.load_gt_items(args.gt)]
+        owner = attribute(fused, gt)
+        by_line = [[p for c, parts in enumerate(fused) if owner[c] == l for p in parts] for l in range(len(gt))]
+        e = fuse.map_error(by_line, gt)
+        print(f"Distance to {args.gt} (clusters attributed to lines {owner}):")
+        print(f"  fused map        mean {e['mean']:.4f} m   max {e['max']:.4f} m   coverage {100.0 * e['coverage']:.1f} %   "
+              f"({e['vertices']} vertices)")
+    if args.png is not None:
+        from pointnet_refine_amd import bev
+        from pointnet_refine_amd.io import load_pcd_data
+        cloud = np.atleast_2d(load_pcd_data(os.path.join(args.drive_dir, "merged.pcd")))[:, :4].astype(np.float32)
+        image, extent = bev.bev_map(cloud, resolution=PNG_RESOLUTION)
+        norm, _ = bev.tone_map(image)
+        rgba = bev.colorize(norm, image).contiguous()
+        parts = [p for f in fused for p in f]
+        bev.draw_lines(rgba, np.array([float(v) for v in extent]), parts, np.zeros(len(parts), dtype=np.int64),
+                       [bev.STYLE_REFINED] * len(parts), resolution=PNG_RESOLUTION)
+        os.makedirs(args.png, exist_ok=True)
+        path = os.path.join(args.png, os.path.basename(os.path.normpath(args.drive_dir)) + "_map.png")
+        bev.write_png(path, rgba)
+        print(f"Saved {path}")
+
+
+if __name__ == "__main__":
+    main()

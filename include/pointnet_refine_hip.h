@@ -721,6 +721,80 @@ int prh_fuse_gather(const double* world, const double* s, long long n_pieces, in
                     long long n_nodes, double ds, double* node_x, double* node_w, int* node_count,
                     double* node_spread, void* workspace, size_t workspace_bytes, int device, void* stream);
 
+/* Piece linking - the rule.
+ * Which refined pieces of a drive are the same lane, when no carrier says so (detector output).
+ * The conventions are those of "Map fusion - the rule": fp64, one rounding per operation, no
+ * contraction, a 3-vector dot is (p0 * q0 + p1 * q1) + p2 * q2, the origin is shifted on the host.
+ * Inputs.  P pieces of M points each (2 <= M <= 64) in the shifted drive frame: the world output of
+ * prh_fuse_project with piece_line NULL.  A frame index per piece.  Per piece cum[M], the
+ * cumulative arc length of its points computed on the host (cum[0] = 0, cum[k+1] = cum[k] +
+ * sqrt(|A[k+1] - A[k]|^2), sequentially); the same bits go to the device and to the oracle.
+ * Parameters gate (metres, default 1.0), min_in (default 4), out_ratio (default 4).
+ * 1. Boxes.  Per piece, lo[c] and hi[c] are the min and max over its points, per axis.
+ * 2. Candidates.  A candidate is a pair (i, j) with i < j, frame[i] != frame[j] and, for every
+ *    axis, lo_i[c] - gate <= hi_j[c] and lo_j[c] - gate <= hi_i[c].  Candidates are listed by
+ *    ascending i, then ascending j; that order is part of the rule.  Pieces of one frame are never
+ *    linked directly: two detections in one frame are two objects, or two fragments that do not
+ *    overlap.
+ * 3. Directed statistics of a -> b.  Every point k of a, in ascending k, is projected onto the
+ *    polyline b exactly as in fusion step 2 (segments with L2 > 0, clamped u, the first strictly
+ *    smallest d2), which gives seg, u, d = sqrt(d2) and s_b = cum_b[seg] + u (cum_b[seg+1] -
+ *    cum_b[seg]).  The point is end-clamped if b has no usable segment, or seg is b's first usable
+ *    segment and u == 0, or seg is b's last usable segment and u == 1: it lies beyond b, outside
+ *    the overlap, and counts nowhere.  An interior point with d <= gate is in: n_in += 1, sum_d +=
+ *    d, sum_a += cum_a[k], sum_b += s_b, sum_dot += e_a . e_b with e_a = A[q+1] - A[q], q = min(k,
+ *    M - 2), and e_b the winning segment's vector.  An interior point with d > gate is out:
+ *    n_out += 1.
+ * 4. Pair statistics.  n_in, n_out, sum_d and sum_dot of the pair (i, j) are the totals of i -> j
+ *    and then j -> i; sum_self, the coordinate along i, is sum_a of i -> j plus sum_b of j -> i;
+ *    sum_other, the coordinate along j, is sum_b of i -> j plus sum_a of j -> i.  Every sum starts
+ *    at 0 and runs over i -> j in ascending k, then j -> i in ascending k, so the result is bitwise
+ *    reproducible and independent of the launch shape.
+ * 5. Edges (host).  A candidate is an edge iff n_in >= min_in and out_ratio * n_out <= n_in, in
+ *    integers.  rho = +1 if sum_dot >= 0, else -1; delta = (sum_self - rho * sum_other) / n_in: the
+ *    arc coordinate along i of a point is delta + rho times its coordinate along j.
+ * 6. Clusters and arc synchronisation (host).  Clusters are the connected components of the edge
+ *    graph, numbered by ascending smallest member.  That member is the root: level 0, sigma = +1,
+ *    o = 0.  A piece at level n + 1 takes as parent, among its neighbours at level n, the one with
+ *    the largest n_in; ties go to the smallest index.  For child b, parent a and their edge (i, j):
+ *    sigma_b = rho * sigma_a; if a == i, o_b = o_a + sigma_a * delta, otherwise o_b = o_a - sigma_b *
+ *    delta.  Point k of piece p gets g = o_p + sigma_p * cum_p[k].  A piece with sigma_p < 0 has its
+ *    points and its g reversed, so g ascends along every piece (detector polylines come in either
+ *    direction).  Per cluster, the smallest g is subtracted.
+ * 7. Draft carriers.  The clusters with at least min_pieces pieces (default 2) are kept: a lane
+ *    seen once is not evidence.  prh_fuse_gather runs on them with s := g, every cluster a line with
+ *    the nodes 0 .. floor(max g / step).  A cluster's draft carrier is its nodes with C >= 1 in node
+ *    order, as one polyline (gaps are bridged); a cluster with fewer than 2 such nodes is dropped
+ *    like a small one.
+ * 8. Map.  The standard fusion (steps 1-6 of "Map fusion - the rule") of the kept pieces, the
+ *    reversed ones reversed, with the draft carriers as lines and the cluster as piece_line.  The
+ *    second pass removes what arc drift the spanning tree left.
+ *
+ * prh_link_pairs_count / prh_link_pairs_write: steps 1-2 in two calls over the same inputs.  world
+ * [n_pieces*M,3] fp64, piece_frame [n_pieces] int32.  Count fills pair_offsets [n_pieces+1]: the
+ * exclusive scan, taken on the device, of the number of candidates (i, j > i) per i.  The caller
+ * reads pair_offsets[n_pieces], sizes pair_j (int32) by it, and write fills pair_j with the
+ * ascending j of every i from pair_offsets[i] on.  The boxes of the j side go through LDS
+ * prh_link_tile() at a time and a row is compacted with ballot / popcount: no sort, no atomic.
+ * O(n_pieces^2) box tests; at most 2^24 pieces.
+ * prh_link_stats: steps 3-4 for every candidate, one wave per pair, prh_link_pairs_per_block()
+ * pairs per block.  cum [n_pieces*M].  pair_count [n_pairs,2] int32 = n_in n_out; pair_sum
+ * [n_pairs,4] fp64 = sum_d sum_self sum_other sum_dot.  Pair p belongs to the i with
+ * pair_offsets[i] <= p < pair_offsets[i+1]; a pair_j[p] outside 0..n_pieces-1 gives counts of -1
+ * and NaN sums. */
+int prh_link_tile(void);
+int prh_link_pairs_per_block(void);
+size_t prh_link_pairs_workspace_bytes(long long n_pieces);
+int prh_link_pairs_count(const double* world, long long n_pieces, int points_per_piece, const int* piece_frame,
+                         double gate, long long* pair_offsets, void* workspace, size_t workspace_bytes, int device,
+                         void* stream);
+int prh_link_pairs_write(const double* world, long long n_pieces, int points_per_piece, const int* piece_frame,
+                         double gate, const long long* pair_offsets, int* pair_j, void* workspace,
+                         size_t workspace_bytes, int device, void* stream);
+int prh_link_stats(const double* world, const double* cum, long long n_pieces, int points_per_piece,
+                   const long long* pair_offsets, const int* pair_j, long long n_pairs, double gate, int* pair_count,
+                   double* pair_sum, int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

@@ -90,6 +90,8 @@ EXPORTS = [
     "prh_view_lines", "prh_view_resolve",
     "prh_fuse_max_points", "prh_fuse_tile", "prh_fuse_project_workspace_bytes", "prh_fuse_project",
     "prh_fuse_gather_workspace_bytes", "prh_fuse_gather",
+    "prh_link_tile", "prh_link_pairs_per_block", "prh_link_pairs_workspace_bytes", "prh_link_pairs_count",
+    "prh_link_pairs_write", "prh_link_stats",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -309,6 +311,18 @@ def _bind(lib):
     lib.prh_fuse_gather_workspace_bytes.argtypes = [ll]
     lib.prh_fuse_gather.restype = i
     lib.prh_fuse_gather.argtypes = [vp, vp, ll, i, vp, i, vp, ll, dbl, vp, vp, vp, vp, vp, sz, i, vp]
+    lib.prh_link_tile.restype = i
+    lib.prh_link_tile.argtypes = []
+    lib.prh_link_pairs_per_block.restype = i
+    lib.prh_link_pairs_per_block.argtypes = []
+    lib.prh_link_pairs_workspace_bytes.restype = sz
+    lib.prh_link_pairs_workspace_bytes.argtypes = [ll]
+    lib.prh_link_pairs_count.restype = i
+    lib.prh_link_pairs_count.argtypes = [vp, ll, i, vp, dbl, vp, vp, sz, i, vp]
+    lib.prh_link_pairs_write.restype = i
+    lib.prh_link_pairs_write.argtypes = [vp, ll, i, vp, dbl, vp, vp, vp, sz, i, vp]
+    lib.prh_link_stats.restype = i
+    lib.prh_link_stats.argtypes = [vp, vp, ll, i, vp, vp, ll, dbl, vp, vp, i, vp]
     lib.prh_pcd_group_rows.restype = i
     lib.prh_pcd_group_rows.argtypes = []
     lib.prh_pcd_format_workspace_bytes.restype = sz

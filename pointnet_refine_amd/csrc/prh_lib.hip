@@ -30,6 +30,7 @@
 #include "prh_bev.hpp"
 #include "prh_view.hpp"
 #include "prh_fuse.hpp"
+#include "prh_link.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
@@ -3034,6 +3035,74 @@ int prh_fuse_gather(const double* world, const double* s, long long n_pieces, in
   hipLaunchKernelGGL(fuse_gather_kernel, dim3((unsigned)((n_nodes + FUSE_THREADS - 1) / FUSE_THREADS)),
                      dim3(FUSE_THREADS), 0, st, world, s, (const double*)range, M, line_piece_offsets, n_lines,
                      node_offsets, n_nodes, ds, node_x, node_w, node_count, node_spread);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ piece linking
+int prh_link_tile(void) { return LINK_TILE; }
+int prh_link_pairs_per_block(void) { return LINK_PAIRS; }
+size_t prh_link_pairs_workspace_bytes(long long n_pieces) {
+  if (n_pieces < 0) return 0;
+  return align_up((size_t)n_pieces * 6 * sizeof(double), 256) + align_up((size_t)n_pieces * sizeof(long long), 256) + 256;
+}
+// boxes, then <WRITE> of link_pairs_kernel; the count call also scans the row counts on the device
+static int link_pairs(bool write, const char* what, const double* world, long long n_pieces, int M,
+                      const int* piece_frame, double gate, long long* pair_offsets, int* pair_j, void* workspace,
+                      size_t workspace_bytes, int device, void* stream) {
+  if (n_pieces < 0 || n_pieces > (1ll << 24) || M < 2 || M > FUSE_MAX_POINTS || !(gate >= 0.0))
+    return fail(PRH_ERR_ARG, "%s: bad argument (at most 2^24 pieces of 2..%d points, gate >= 0)", what, FUSE_MAX_POINTS);
+  if (!pair_offsets) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if (n_pieces > 0 && (!world || !piece_frame || (write && !pair_j))) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if (!workspace || workspace_bytes < prh_link_pairs_workspace_bytes(n_pieces))
+    return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  const int P = (int)n_pieces;
+  double* box = (double*)workspace;
+  long long* row_count = (long long*)((char*)workspace + align_up((size_t)n_pieces * 6 * sizeof(double), 256));
+  if (P > 0) {
+    hipLaunchKernelGGL(link_box_kernel, dim3(cdiv(P, LINK_THREADS)), dim3(LINK_THREADS), 0, st, world, P, M, box);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(write ? link_pairs_kernel<true> : link_pairs_kernel<false>, dim3(cdiv(P, LINK_ROWS)),
+                       dim3(LINK_THREADS), 0, st, (const double*)box, piece_frame, P, gate, row_count,
+                       (const long long*)pair_offsets, pair_j);
+    LAUNCH_CHECK();
+  }
+  if (!write) {
+    hipLaunchKernelGGL(link_scan_kernel, dim3(1), dim3(LINK_SCAN_THREADS), 0, st, (const long long*)row_count, P,
+                       pair_offsets);
+    LAUNCH_CHECK();
+  }
+  return PRH_OK;
+}
+int prh_link_pairs_count(const double* world, long long n_pieces, int points_per_piece, const int* piece_frame,
+                         double gate, long long* pair_offsets, void* workspace, size_t workspace_bytes, int device,
+                         void* stream) {
+  return link_pairs(false, "link_pairs_count", world, n_pieces, points_per_piece, piece_frame, gate, pair_offsets,
+                    nullptr, workspace, workspace_bytes, device, stream);
+}
+int prh_link_pairs_write(const double* world, long long n_pieces, int points_per_piece, const int* piece_frame,
+                         double gate, const long long* pair_offsets, int* pair_j, void* workspace,
+                         size_t workspace_bytes, int device, void* stream) {
+  return link_pairs(true, "link_pairs_write", world, n_pieces, points_per_piece, piece_frame, gate,
+                    (long long*)pair_offsets, pair_j, workspace, workspace_bytes, device, stream);
+}
+int prh_link_stats(const double* world, const double* cum, long long n_pieces, int points_per_piece,
+                   const long long* pair_offsets, const int* pair_j, long long n_pairs, double gate, int* pair_count,
+                   double* pair_sum, int device, void* stream) {
+  const int M = points_per_piece;
+  if (n_pieces < 0 || n_pieces > (1ll << 24) || n_pairs < 0 || M < 2 || M > FUSE_MAX_POINTS || !(gate >= 0.0))
+    return fail(PRH_ERR_ARG, "link_stats: bad argument (at most 2^24 pieces of 2..%d points, gate >= 0)", FUSE_MAX_POINTS);
+  if (n_pairs >= (long long)LINK_PAIRS * 0x7fffffff) return fail(PRH_ERR_ARG, "link_stats: too many pairs");
+  if (n_pairs == 0) return PRH_OK;
+  if (n_pieces == 0) return fail(PRH_ERR_ARG, "link_stats: pairs without pieces");
+  if (!world || !cum || !pair_offsets || !pair_j || !pair_count || !pair_sum)
+    return fail(PRH_ERR_ARG, "link_stats: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(link_stats_kernel, dim3((unsigned)((n_pairs + LINK_PAIRS - 1) / LINK_PAIRS)), dim3(LINK_THREADS), 0,
+                     (hipStream_t)stream, world, cum, (int)n_pieces, M, pair_offsets, pair_j, n_pairs, gate, pair_count,
+                     pair_sum);
   LAUNCH_CHECK();
   return PRH_OK;
 }
