@@ -3,7 +3,7 @@ slice's lines are refined by the model, and the refined pieces are fused into on
 input line in the drive frame (pointnet_refine_amd/fuse.py).
 
     python examples/refine_drive.py DRIVE_DIR LINES_JSON --checkpoint CKPT --out MAP.json
-                                    [--noise S] [--seed N] [--gt GT_JSON] [--png DIR]
+                                    [--noise S] [--seed N] [--gt GT_JSON] [--png DIR] [--batched]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; LINES_JSON the lines to refine in the drive file layout
 (items[].category / attributes / position); MAP.json gets the fused map in the same layout.
@@ -56,6 +56,7 @@ def main():
     ap.add_argument("--gt", default=None)
     ap.add_argument("--png", default=None)
     ap.add_argument("--step", type=float, default=0.5)
+    ap.add_argument("--batched", action="store_true", help="contexts of all slices in one ragged GPU pass")
     args = ap.parse_args()
 
     from pointnet_refine_amd import drive, fuse
@@ -65,7 +66,8 @@ def main():
     if args.noise is not None:
         lines = [c[0] for c in drive.noisy_candidates(lines, (args.noise,), seed=args.seed)]
         print(f"Perturbed {len(lines)} lines at scale {args.noise} (seed {args.seed})")
-    res = fuse.refine_drive(load_model(args.checkpoint), args.drive_dir, None, lines, seed=args.seed, step=args.step)
+    res = fuse.refine_drive(load_model(args.checkpoint), args.drive_dir, None, lines, seed=args.seed, step=args.step,
+                            batched=args.batched)
     rep = res["report"]
     print(f"{rep['slices']} slices, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['nodes_used']} of {rep['nodes']} nodes used, {rep['fused_polylines']} polylines")

@@ -4,7 +4,7 @@ frames into lanes and fused into one polyline per lane in the drive frame
 (pointnet_refine_amd/link.py).
 
     python examples/refine_predictions.py DRIVE_DIR RESULTS_JSON --checkpoint CKPT --out MAP.json
-                                          [--gt GT_JSON] [--png DIR]
+                                          [--gt GT_JSON] [--png DIR] [--batched]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; RESULTS_JSON is the detector's output
 (predictions.load_results); MAP.json gets the fused map in the drive file layout
@@ -69,11 +69,12 @@ def main():
     ap.add_argument("--step", type=float, default=0.5)
     ap.add_argument("--gate", type=float, default=1.0)
     ap.add_argument("--min-pieces", type=int, default=2)
+    ap.add_argument("--batched", action="store_true", help="contexts of all frames in one ragged GPU pass")
     args = ap.parse_args()
 
     from pointnet_refine_amd import drive, fuse, link
     res = link.refine_predictions(load_model(args.checkpoint), args.drive_dir, args.results_json, seed=args.seed,
-                                  step=args.step, gate=args.gate, min_pieces=args.min_pieces)
+                                  step=args.step, gate=args.gate, min_pieces=args.min_pieces, batched=args.batched)
     rep = res["report"]
     print(f"{rep['slices']} frames, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['candidates']} candidate pairs, {rep['edges']} edges, {rep['clusters']} clusters, "

@@ -359,6 +359,47 @@ int prh_context_build(const float* cloud, int npts, const float* dense, int n_de
                       float* dbg_weights, void* workspace, size_t workspace_bytes, int device,
                       void* stream);
 
+/* Ragged context builder: the contexts of the lines of MANY slices (a drive's slices, a detector
+ * run's frames) in one pass.  Every line is cropped from its own slice; per line the arithmetic and
+ * its order are those of prh_context_build, so the bytes of out and counts equal a
+ * prh_context_build call per slice (with that slice's seed and a candidate buffer large enough).
+ *   points        [T,4] device: the slices back to back, T < 2^31
+ *   slice_offsets [n_slices+1] HOST: slice s is rows slice_offsets[s] .. slice_offsets[s+1]; starts at
+ *                 0 and never decreases (a slice may be empty: its lines get counts 0, zero contexts)
+ *   dense [n_lines,n_dense,3], line [n_lines,m,3] device, as in prh_context_build
+ *   line_slice    [n_lines] HOST: the slice of each line, never decreasing (lines grouped by slice)
+ *   slice_seed    [n_slices] HOST: one seed per slice
+ * Index convention of the hash: a line's index is its position among the lines of its own slice
+ * (the first line of every slice is line 0), a point's index is its row relative to
+ * slice_offsets[s] - what a per-slice prh_context_build call uses, so the draws coincide.
+ * Work items are (line, 256-point block of the line's slice) on a flat 1-D grid: their number, the
+ * sum over the lines of ceil(slice points / 256), must stay below 2^31; n_lines itself is only
+ * bounded by that.
+ * prh_context_ragged_count: counts [n_lines] points inside each tube and cand_offsets [n_lines+1]
+ *   (device, int64) their exclusive scan; the caller reads cand_offsets[n_lines] (or the whole
+ *   array) and sizes the candidate buffers.  It also leaves the per-line tables and per-block
+ *   counts in the workspace: prh_context_ragged_select must get the same workspace, untouched, and
+ *   the same host arrays.
+ * prh_context_ragged_select: fills and draws the lines line0 .. line1-1 (any run; the runs of a
+ *   call sequence may reuse cand / keys).  cand (int32, slice-local rows in cloud order) and keys
+ *   (uint32; the weights share it) hold cand_capacity entries each, at least
+ *   cand_offsets[line1] - cand_offsets[line0]: no cap, no truncation (a shorter buffer is never
+ *   written past its end: the lines that do not fit are drawn from what fits).  Writes
+ *   out [n_lines,n_samples,4] rows of the run.
+ * prh_context_ragged_workspace_bytes: n_items is that number of work items; 0 for n_lines <= 0 or
+ *   n_items outside 0 .. 2^31 - 1.  The entry points recompute n_items from the host arrays and
+ *   refuse a workspace that is too small. */
+size_t prh_context_ragged_workspace_bytes(int n_lines, long long n_items);
+int prh_context_ragged_count(const float* points, const long long* slice_offsets, int n_slices, const float* dense,
+                             int n_dense, const int* line_slice, const unsigned long long* slice_seed, int n_lines,
+                             float radius, int32_t* counts, long long* cand_offsets, void* workspace,
+                             size_t workspace_bytes, int device, void* stream);
+int prh_context_ragged_select(const float* points, const long long* slice_offsets, int n_slices, const float* dense,
+                              int n_dense, const float* line, int m, const int* line_slice, int n_lines, float radius,
+                              float decay_scale, int n_samples, const int32_t* counts, const long long* cand_offsets,
+                              int line0, int line1, int* cand, unsigned* keys, long long cand_capacity, float* out,
+                              void* workspace, size_t workspace_bytes, int device, void* stream);
+
 /* Scene evaluation (inference_whole_scene.py:26-92,299-365), fp64 throughout, FMA contraction off,
  * distances as sqrt((dx*dx + dy*dy) + dz*dz) - the numpy order - so results match the
  * reference's float64 numpy / scipy code to rounding even at UTM-sized coordinates.

@@ -77,6 +77,7 @@ EXPORTS = [
     "prh_profile_enable", "prh_profile_count", "prh_profile_reset", "prh_profile_read",
     "prh_attn_forward", "prh_attn_backward", "prh_attn_backward_ex",
     "prh_context_workspace_bytes", "prh_context_build",
+    "prh_context_ragged_workspace_bytes", "prh_context_ragged_count", "prh_context_ragged_select",
     "prh_line_metrics", "prh_shift_sweep_workspace_bytes", "prh_shift_sweep",
     "prh_drive_slice_workspace_bytes", "prh_drive_slice_count", "prh_drive_slice_write",
     "prh_drive_clip_workspace_bytes", "prh_drive_clip_count", "prh_drive_clip_write",
@@ -223,6 +224,13 @@ def _bind(lib):
     lib.prh_context_build.restype = i
     lib.prh_context_build.argtypes = [vp, i, vp, i, vp, i, i, f, f, i, i, C.c_ulonglong, vp, vp, vp, vp,
                                       C.c_size_t, i, vp]
+    lib.prh_context_ragged_workspace_bytes.restype = sz
+    lib.prh_context_ragged_workspace_bytes.argtypes = [i, C.c_longlong]
+    lib.prh_context_ragged_count.restype = i
+    lib.prh_context_ragged_count.argtypes = [vp, vp, i, vp, i, vp, vp, i, f, vp, vp, vp, sz, i, vp]
+    lib.prh_context_ragged_select.restype = i
+    lib.prh_context_ragged_select.argtypes = [vp, vp, i, vp, i, vp, i, vp, i, f, f, i, vp, vp, i, i, vp, vp,
+                                              C.c_longlong, vp, vp, sz, i, vp]
     lib.prh_line_metrics.restype = i
     lib.prh_line_metrics.argtypes = [vp, vp, i, i, vp, vp, i, vp, vp, vp, vp, i, vp]
     lib.prh_shift_sweep_workspace_bytes.restype = sz

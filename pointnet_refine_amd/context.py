@@ -18,6 +18,8 @@ from . import _gpu as G
 from . import _lib as L
 
 DENSE_POINTS = 200          # src/dataset.py:214: tube continuity needs ~0.25 m spacing
+CROP_BLOCK = 256            # points per work item of the crop passes (csrc/prh_context.hpp)
+CANDIDATE_BYTES = 8         # per candidate of the ragged builder: int32 row + uint32 key
 
 
 def resample_polyline(points, num_points=32):
@@ -133,5 +135,129 @@ def build_contexts(cloud, raw_lines, num_line_points=32, num_context_points=1024
     line_t = resample_polylines_device(raw_lines, num_line_points, dev).float()
     ctx, counts = build_contexts_resampled(cloud, dense_t, line_t, num_context_points, crop_radius, decay_scale,
                                            seed, max_candidates)
+    centres = line_t.mean(dim=1)
+    return ctx, line_t - centres[:, None, :], centres, counts
+
+
+# ------------------------------------------------------------------ ragged: many slices, one pass
+def ragged_block_offsets(slice_offsets, line_slice):
+    """Host plan of the ragged crop passes: (L+1,) int64, the exclusive scan over the lines of
+    ceil(points of the line's slice / CROP_BLOCK).  Work item i belongs to the line l with
+    out[l] <= i < out[l+1]; a line of an empty slice has none; out[-1] is the grid size.
+    slice_offsets (S+1,) starts at 0 and never decreases; line_slice (L,) never decreases (lines are
+    grouped by slice) and names slices 0..S-1 - RuntimeError otherwise, as the library says too."""
+    so = np.asarray(slice_offsets, dtype=np.int64).reshape(-1)
+    ls = np.asarray(line_slice, dtype=np.int64).reshape(-1)
+    if len(so) < 2 or so[0] != 0 or (np.diff(so) < 0).any():
+        raise RuntimeError("build_contexts_ragged: slice_offsets must start at 0 and never decrease")
+    if len(ls) and (ls.min() < 0 or ls.max() >= len(so) - 1):
+        raise RuntimeError(f"build_contexts_ragged: line_slice names a slice outside 0..{len(so) - 2}")
+    if (np.diff(ls) < 0).any():
+        raise RuntimeError("build_contexts_ragged: line_slice must never decrease (lines are grouped by slice)")
+    blocks = (np.diff(so) + (CROP_BLOCK - 1)) // CROP_BLOCK
+    out = np.zeros(len(ls) + 1, dtype=np.int64)
+    out[1:] = np.cumsum(blocks[ls])
+    return out
+
+
+def ragged_runs(cand_offsets, max_candidate_bytes=None):
+    """Runs of consecutive lines [(l0, l1), ...] covering 0..L whose candidates fit the byte budget
+    (CANDIDATE_BYTES each; None: one run).  Greedy from the left; a line that alone exceeds the
+    budget runs alone - the budget bounds the buffers of every other run."""
+    co = np.asarray(cand_offsets, dtype=np.int64).reshape(-1)
+    n = len(co) - 1
+    if max_candidate_bytes is None:
+        return [(0, n)] if n > 0 else []
+    room = max(int(max_candidate_bytes), 0) // CANDIDATE_BYTES
+    runs, l0 = [], 0
+    while l0 < n:
+        # the last l1 with co[l1] - co[l0] <= room, at least l0 + 1
+        l1 = max(int(np.searchsorted(co, co[l0] + room, side="right")) - 1, l0 + 1)
+        runs.append((l0, min(l1, n)))
+        l0 = min(l1, n)
+    return runs
+
+
+def build_contexts_ragged_resampled(points, slice_offsets, dense, line, line_slice, slice_seeds,
+                                    num_context_points=1024, crop_radius=0.3, decay_scale=2.0,
+                                    max_candidate_bytes=None):
+    """build_contexts_resampled for the lines of many slices at once (prh_context_ragged_count /
+    _select): points (T,4) float32 CUDA holds the slices back to back, slice_offsets (S+1,) int64
+    (host array, or a tensor that is read back) cuts it, line l of dense (L,D,3) / line (L,M,3) is
+    cropped from slice line_slice[l] (never decreasing) and drawn with slice_seeds[line_slice[l]].
+    Returns context (L,N,4), counts (L,) int32 - the bytes build_contexts_resampled gives per slice
+    for that slice's points, lines and seed (a line's index in the hash is its position among its
+    slice's lines, a point's its row within the slice).
+
+    The candidates live in one CSR buffer sized from the true counts after one read-back: no
+    max_candidates, no repeat.  max_candidate_bytes bounds that buffer (8 bytes per candidate): over
+    it, the fill and draw pass runs over consecutive runs of lines (ragged_runs) that reuse the
+    buffer; the result does not depend on the budget."""
+    for t, name in ((points, "points"), (dense, "dense"), (line, "line")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise RuntimeError(f"build_contexts_ragged: {name} must be a float32 CUDA tensor (there is no CPU fallback)")
+    points, dense, line = points.contiguous(), dense.contiguous(), line.contiguous()
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise RuntimeError(f"build_contexts_ragged: points must be (T,4), got {tuple(points.shape)}")
+    if dense.dim() != 3 or line.dim() != 3 or dense.shape[0] != line.shape[0] or dense.shape[2] != 3 or line.shape[2] != 3:
+        raise RuntimeError("build_contexts_ragged: dense (L,D,3) and line (L,M,3) expected")
+    if torch.is_tensor(slice_offsets):
+        slice_offsets = slice_offsets.cpu().numpy()
+    so = np.ascontiguousarray(slice_offsets, dtype=np.int64).reshape(-1)
+    ls = np.ascontiguousarray(line_slice, dtype=np.int32).reshape(-1)
+    seeds = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in slice_seeds], dtype=np.uint64)
+    n_lines, n, n_slices = dense.shape[0], int(num_context_points), len(so) - 1
+    if len(ls) != n_lines or len(seeds) != n_slices:
+        raise RuntimeError("build_contexts_ragged: one line_slice entry per line and one seed per slice expected")
+    blk = ragged_block_offsets(so, ls)
+    if so[-1] != points.shape[0]:
+        raise RuntimeError(f"build_contexts_ragged: slice_offsets end at {so[-1]}, points has {points.shape[0]} rows")
+    dev = points.device
+    out = torch.empty((n_lines, n, 4), dtype=torch.float32, device=dev)
+    counts = torch.empty((n_lines,), dtype=torch.int32, device=dev)
+    if n_lines == 0:
+        return out, counts
+    lib = L.lib()
+    p = G.ptr
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    cand_offsets = torch.empty((n_lines + 1,), dtype=torch.int64, device=dev)
+    nb = lib.prh_context_ragged_workspace_bytes(n_lines, int(blk[-1]))
+    if nb == 0:
+        raise RuntimeError(f"build_contexts_ragged: {int(blk[-1])} (line, block) work items do not fit one call")
+    ws = G.workspace(nb, dev)
+    L.check(lib.prh_context_ragged_count(p(points), hp(so), n_slices, p(dense), dense.shape[1], hp(ls), hp(seeds),
+                                         n_lines, float(crop_radius), p(counts), p(cand_offsets), p(ws), nb,
+                                         dev.index, G.stream(dev)), "prh_context_ragged_count")
+    total = int(cand_offsets[-1].item())                 # the one read-back of the call
+    if max_candidate_bytes is None or total * CANDIDATE_BYTES <= int(max_candidate_bytes):
+        runs, sizes = [(0, n_lines)], [total]
+    else:
+        co = cand_offsets.cpu().numpy()
+        runs = ragged_runs(co, max_candidate_bytes)
+        sizes = [int(co[l1] - co[l0]) for l0, l1 in runs]
+    cap = max(sizes)
+    cand = torch.empty((cap,), dtype=torch.int32, device=dev)
+    keys = torch.empty((cap,), dtype=torch.int32, device=dev)          # uint32 keys, float weights before them
+    for l0, l1 in runs:
+        L.check(lib.prh_context_ragged_select(p(points), hp(so), n_slices, p(dense), dense.shape[1], p(line),
+                                              line.shape[1], hp(ls), n_lines, float(crop_radius), float(decay_scale),
+                                              n, p(counts), p(cand_offsets), l0, l1, p(cand), p(keys), cap, p(out),
+                                              p(ws), nb, dev.index, G.stream(dev)), "prh_context_ragged_select")
+    return out, counts
+
+
+def build_contexts_ragged(points, slice_offsets, raw_lines, line_slice, slice_seeds, num_line_points=32,
+                          num_context_points=1024, crop_radius=0.3, decay_scale=2.0, max_candidate_bytes=None):
+    """build_contexts for the lines of many slices in one pass: raw_lines is the flat list of (n_i,3)
+    polylines, each in the frame of its slice line_slice[i] (never decreasing).  Returns context
+    (L,N,4), noisy_line (L,M,3) centred, centres (L,3), counts (L,); see
+    build_contexts_ragged_resampled for points, slice_offsets, slice_seeds and the memory budget."""
+    if not (torch.is_tensor(points) and points.is_cuda):
+        raise RuntimeError("build_contexts_ragged: points must be a float32 CUDA tensor (there is no CPU fallback)")
+    dev = points.device
+    dense_t = resample_polylines_device(raw_lines, DENSE_POINTS, dev).float()
+    line_t = resample_polylines_device(raw_lines, num_line_points, dev).float()
+    ctx, counts = build_contexts_ragged_resampled(points, slice_offsets, dense_t, line_t, line_slice, slice_seeds,
+                                                  num_context_points, crop_radius, decay_scale, max_candidate_bytes)
     centres = line_t.mean(dim=1)
     return ctx, line_t - centres[:, None, :], centres, counts

@@ -2322,6 +2322,144 @@ int prh_context_build(const float* cloud, int npts, const float* dense, int n_de
   return PRH_OK;
 }
 
+// ragged builder: every line cropped from its own slice of one point buffer, candidates in CSR
+struct CtxRaggedWS {
+  int* line_base; int* line_npts; int* line_local; uint64_t* line_seed; long long* blk_offsets;
+  float* box; int* blkcnt; int* blkoff;
+};
+void ctx_ragged_carve(Arena& a, CtxRaggedWS& w, int L, long long n_items) {
+  w.line_base = (int*)a.f((size_t)L);
+  w.line_npts = (int*)a.f((size_t)L);
+  w.line_local = (int*)a.f((size_t)L);
+  w.line_seed = (uint64_t*)a.f(2 * (size_t)L);
+  w.blk_offsets = (long long*)a.f(2 * ((size_t)L + 1));
+  w.box = a.f((size_t)L * 6);
+  w.blkcnt = (int*)a.f((size_t)n_items);
+  w.blkoff = (int*)a.f((size_t)n_items);
+}
+// Host arrays checked; blk_offsets (n_lines + 1) = exclusive scan of the 256-point blocks of each
+// line's slice.  Returns PRH_OK or the error of the first rule broken.
+static int ctx_ragged_plan(const char* what, const long long* slice_offsets, int n_slices, const int* line_slice,
+                           int n_lines, std::vector<long long>& blk_offsets) {
+  if (!slice_offsets || !line_slice || n_slices <= 0 || n_lines <= 0)
+    return fail(PRH_ERR_ARG, "%s: bad argument (slice_offsets, line_slice, at least one slice and one line)", what);
+  if (slice_offsets[0] != 0) return fail(PRH_ERR_ARG, "%s: slice_offsets must start at 0", what);
+  for (int s = 0; s < n_slices; ++s)
+    if (slice_offsets[s + 1] < slice_offsets[s])
+      return fail(PRH_ERR_ARG, "%s: slice_offsets must not decrease (slice %d)", what, s);
+  if (slice_offsets[n_slices] >= (1ll << 31)) return fail(PRH_ERR_ARG, "%s: at most 2^31 - 1 points per call", what);
+  blk_offsets.assign((size_t)n_lines + 1, 0);
+  for (int l = 0; l < n_lines; ++l) {
+    const int s = line_slice[l];
+    if (s < 0 || s >= n_slices) return fail(PRH_ERR_ARG, "%s: line %d names slice %d of %d", what, l, s, n_slices);
+    if (l > 0 && s < line_slice[l - 1])
+      return fail(PRH_ERR_ARG, "%s: line_slice must not decrease (line %d): lines are grouped by slice", what, l);
+    blk_offsets[l + 1] = blk_offsets[l] + (slice_offsets[s + 1] - slice_offsets[s] + 255) / 256;
+  }
+  if (blk_offsets[n_lines] > 0x7fffffffll)
+    return fail(PRH_ERR_ARG, "%s: %lld (line, block) work items do not fit one grid", what, blk_offsets[n_lines]);
+  return PRH_OK;
+}
+size_t prh_context_ragged_workspace_bytes(int n_lines, long long n_items) {
+  if (n_lines <= 0 || n_items < 0 || n_items > 0x7fffffffll) return 0;
+  Arena a; CtxRaggedWS w;
+  ctx_ragged_carve(a, w, n_lines, n_items);
+  return a.off + 256;
+}
+static int ctx_ragged_shapes(const char* what, int n_dense, int m, float radius) {
+  if (n_dense < 1 || n_dense > CTX_MAX_DENSE || m < 1 || m > CTX_MAX_LINE)
+    return fail(PRH_ERR_ARG, "%s: n_dense must be 1..%d and m 1..%d", what, CTX_MAX_DENSE, CTX_MAX_LINE);
+  if (!(radius >= 0.f)) return fail(PRH_ERR_ARG, "%s: radius", what);
+  return PRH_OK;
+}
+int prh_context_ragged_count(const float* points, const long long* slice_offsets, int n_slices, const float* dense,
+                             int n_dense, const int* line_slice, const unsigned long long* slice_seed, int n_lines,
+                             float radius, int32_t* counts, long long* cand_offsets, void* workspace,
+                             size_t workspace_bytes, int device, void* stream) {
+  const char* what = "context_ragged_count";
+  std::vector<long long> blk;
+  TRY(ctx_ragged_plan(what, slice_offsets, n_slices, line_slice, n_lines, blk));
+  TRY(ctx_ragged_shapes(what, n_dense, 1, radius));
+  if (!dense || !slice_seed || !counts || !cand_offsets || (slice_offsets[n_slices] > 0 && !points))
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  const long long n_items = blk[n_lines];
+  Arena a(workspace, workspace_bytes);
+  CtxRaggedWS w;
+  ctx_ragged_carve(a, w, n_lines, n_items);
+  if (!workspace || !a.ok) return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  // per-line tables: first row and rows of the line's slice, the line's position among its slice's
+  // lines and its slice's seed - the indices and the seed a per-slice call would hash
+  const size_t L = (size_t)n_lines;
+  std::vector<int> base(L), npts(L), local(L);
+  std::vector<uint64_t> seed(L);
+  for (size_t l = 0; l < L; ++l) {
+    const int s = line_slice[l];
+    base[l] = (int)slice_offsets[s];
+    npts[l] = (int)(slice_offsets[s + 1] - slice_offsets[s]);
+    local[l] = l > 0 && line_slice[l - 1] == s ? local[l - 1] + 1 : 0;
+    seed[l] = (uint64_t)slice_seed[s];
+  }
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemcpyAsync(w.line_base, base.data(), L * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.line_npts, npts.data(), L * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.line_local, local.data(), L * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.line_seed, seed.data(), L * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.blk_offsets, blk.data(), (L + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));               // the host tables above go out of scope on return
+  hipLaunchKernelGGL(ctx_bbox_kernel, dim3(n_lines), dim3(64), 0, st, dense, n_dense, radius, w.box);
+  LAUNCH_CHECK();
+  if (n_items > 0) {
+    hipLaunchKernelGGL((ctx_ragged_crop_kernel<false>), dim3((unsigned)n_items), dim3(256), 0, st, points,
+                       (const int*)w.line_base, (const int*)w.line_npts, (const long long*)w.blk_offsets, 0, n_lines,
+                       dense, n_dense, (const float*)w.box, radius * radius, w.blkcnt, (const int*)nullptr,
+                       (const long long*)nullptr, (int*)nullptr, 0ll);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(ctx_ragged_scan_kernel, dim3(n_lines), dim3(256), 0, st, (const int*)w.blkcnt,
+                     (const long long*)w.blk_offsets, w.blkoff, counts);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(ctx_ragged_offsets_kernel, dim3(1), dim3(256), 0, st, (const int*)counts, n_lines, cand_offsets);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_context_ragged_select(const float* points, const long long* slice_offsets, int n_slices, const float* dense,
+                              int n_dense, const float* line, int m, const int* line_slice, int n_lines, float radius,
+                              float decay_scale, int n_samples, const int32_t* counts, const long long* cand_offsets,
+                              int line0, int line1, int* cand, unsigned* keys, long long cand_capacity, float* out,
+                              void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const char* what = "context_ragged_select";
+  std::vector<long long> blk;
+  TRY(ctx_ragged_plan(what, slice_offsets, n_slices, line_slice, n_lines, blk));
+  TRY(ctx_ragged_shapes(what, n_dense, m, radius));
+  if (!dense || !line || !counts || !cand_offsets || !out || (slice_offsets[n_slices] > 0 && !points))
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if (n_samples <= 0 || !(decay_scale > 0.f)) return fail(PRH_ERR_ARG, "%s: n_samples/decay_scale", what);
+  if (line0 < 0 || line1 <= line0 || line1 > n_lines)
+    return fail(PRH_ERR_ARG, "%s: lines %d..%d of %d", what, line0, line1, n_lines);
+  if (cand_capacity < 0 || (cand_capacity > 0 && (!cand || !keys)))
+    return fail(PRH_ERR_ARG, "%s: candidate buffers", what);
+  Arena a(workspace, workspace_bytes);
+  CtxRaggedWS w;
+  ctx_ragged_carve(a, w, n_lines, blk[n_lines]);
+  if (!workspace || !a.ok) return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  const long long run_items = blk[line1] - blk[line0];
+  if (run_items > 0 && cand_capacity > 0) {
+    hipLaunchKernelGGL((ctx_ragged_crop_kernel<true>), dim3((unsigned)run_items), dim3(256), 0, st, points,
+                       (const int*)w.line_base, (const int*)w.line_npts, (const long long*)w.blk_offsets, line0,
+                       line1 - line0, dense, n_dense, (const float*)w.box, radius * radius, w.blkcnt,
+                       (const int*)w.blkoff, cand_offsets, cand, cand_capacity);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(ctx_ragged_select_kernel, dim3(line1 - line0), dim3(256), 0, st, points, (const int*)w.line_base,
+                     (const int*)w.line_local, (const uint64_t*)w.line_seed, line, m, counts, cand_offsets, line0,
+                     (const int*)cand, decay_scale, n_samples, keys, cand_capacity, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
 // ------------------------------------------------------------------ scene evaluation metrics
 int prh_line_metrics(const double* noisy, const double* refined, int n_lines, int m, const double* gt,
                      const long long* gt_offsets, int n_gt, const int* gt_index, int* info, double* resampled,

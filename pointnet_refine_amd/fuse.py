@@ -298,10 +298,40 @@ def map_error(fused, gt_lines):
             "vertices": int(len(pts)), "covered_length": covered, "line_length": total}
 
 
+def refine_slices_batched(model, points, off, cands, num_line_points, num_context_points, crop_radius, decay_scale,
+                          seed, precision, min_tube_points):
+    """The per-slice loop of refine_drive / link.refine_predictions as one io.scene_offsets_ragged
+    call.  points (T,4) CUDA and off (S+1,) host offsets from drive.slice_cloud; cands: per slice the
+    list of candidate polylines in that slice's frame.  Slice si draws with seed * 1000003 + si, the
+    lines of a slice without points are counted as sparse and never reach the model, a piece whose
+    tube held fewer than min_tube_points points is left out and counted - all as in the loop.
+    Returns (pieces (P,M,3) float64, piece_slice (P,), piece_row (P,) the row in cands[slice],
+    sparse), pieces in slice order, then candidate order."""
+    from .io import scene_offsets_ragged
+    off = np.asarray(off, dtype=np.int64)
+    n_cand = np.array([len(c) for c in cands], dtype=np.int64)
+    has_points = np.diff(off) > 0
+    sparse = int(n_cand[~has_points].sum())
+    used = np.flatnonzero(has_points & (n_cand > 0))
+    if len(used) == 0:
+        return np.zeros((0, int(num_line_points), 3)), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), sparse
+    line_slice = np.repeat(used, n_cand[used])
+    line_row = np.concatenate([np.arange(n_cand[si]) for si in used])
+    raw = [v for si in used for v in cands[si]]
+    seeds = [int(seed) * 1000003 + si for si in range(len(off) - 1)]
+    offset, noisy_c, centres, counts = scene_offsets_ragged(
+        model, points.to(torch.float32), off, raw, line_slice, seeds, int(num_line_points), num_context_points,
+        crop_radius, decay_scale, precision=precision, return_counts=True)
+    refined = (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy()
+    keep = counts.cpu().numpy() >= int(min_tube_points)
+    return refined[keep], line_slice[keep], line_row[keep], sparse + int((~keep).sum())
+
+
 @torch.no_grad()
 def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, num_context_points=1024, crop_radius=0.3,
                  decay_scale=2.0, seed=0, precision=None, segment_len=None, stride=None, radius=None, max_pose_gap=None,
-                 step=STEP, min_count=MIN_COUNT, max_gap=MAX_GAP, min_tube_points=MIN_TUBE_POINTS, origin=None):
+                 step=STEP, min_count=MIN_COUNT, max_gap=MAX_GAP, min_tube_points=MIN_TUBE_POINTS, origin=None,
+                 batched=False):
     """Refine the lines of a whole drive into one drive-frame map.
 
     drive_dir_or_cloud: a drive directory (merged.pcd and, when poses is None, pose/*.json) or the
@@ -317,6 +347,9 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     refined pieces noisy_c + centres + offset are collected with their line and slice; fuse_pieces
     merges them with the input lines as carriers.  A piece whose tube held fewer than
     min_tube_points cloud points is left out and counted (the model saw padding, not a lane).
+    batched=True replaces the per-slice loop by one io.scene_offsets_ragged call over all slices
+    (refine_slices_batched): the same contexts byte for byte, the same pieces in the same order up
+    to which rows share a forward call.
 
     Returns {'fused', 'pieces' (P,M,3) float64 ego frame, 'piece_line', 'piece_slice' (P,),
     'pose_index' (plan_slices), 'poses' (S,7) of the slices, 'nodes' (fuse_pieces' node dict),
@@ -348,25 +381,32 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
         points, offsets, _ = D.slice_cloud(cloud, pq, segment_len, D.RADIUS if radius is None else radius)
         clipped = D.clip_lines(lines, pq, segment_len)
         off = offsets.cpu().numpy()
-        for si, kept in enumerate(clipped):
-            if not kept:
-                continue
-            if off[si + 1] == off[si]:
-                sparse += len(kept)                    # no cloud at all in this slice
-                continue
-            pts = points[off[si]:off[si + 1]].to(torch.float32)
-            offset, noisy_c, centres, counts = scene_offsets(model, pts, [v for _, v in kept], m, num_context_points,
-                                                             crop_radius, decay_scale, seed=int(seed) * 1000003 + si,
-                                                             precision=precision, return_counts=True)
-            refined = (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy()
-            keep = counts.cpu().numpy() >= int(min_tube_points)
-            sparse += int((~keep).sum())
-            for r, (l, _) in enumerate(kept):
-                if keep[r]:
-                    pieces.append(refined[r])
-                    piece_line.append(l)
-                    piece_slice.append(si)
-    pieces = np.stack(pieces) if pieces else np.zeros((0, m, 3))
+        if batched:
+            pieces, piece_slice, row, sparse = refine_slices_batched(
+                model, points, off, [[v for _, v in kept] for kept in clipped], m, num_context_points, crop_radius,
+                decay_scale, seed, precision, min_tube_points)
+            first = np.cumsum([0] + [len(kept) for kept in clipped])
+            piece_line = np.array([l for kept in clipped for l, _ in kept], dtype=np.int64)[first[piece_slice] + row]
+        else:
+            for si, kept in enumerate(clipped):
+                if not kept:
+                    continue
+                if off[si + 1] == off[si]:
+                    sparse += len(kept)                    # no cloud at all in this slice
+                    continue
+                pts = points[off[si]:off[si + 1]].to(torch.float32)
+                offset, noisy_c, centres, counts = scene_offsets(model, pts, [v for _, v in kept], m, num_context_points,
+                                                                 crop_radius, decay_scale, seed=int(seed) * 1000003 + si,
+                                                                 precision=precision, return_counts=True)
+                refined = (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy()
+                keep = counts.cpu().numpy() >= int(min_tube_points)
+                sparse += int((~keep).sum())
+                for r, (l, _) in enumerate(kept):
+                    if keep[r]:
+                        pieces.append(refined[r])
+                        piece_line.append(l)
+                        piece_slice.append(si)
+    pieces = np.stack(pieces) if len(pieces) else np.zeros((0, m, 3))
     piece_line = np.asarray(piece_line, dtype=np.int64)
     piece_slice = np.asarray(piece_slice, dtype=np.int64)
     fused, nodes = fuse_pieces(lines, pieces, piece_line, piece_slice, pq, step, min_count, max_gap, origin,

@@ -12,12 +12,13 @@
                      resampled noisy line + last-layer offset (model side: scene_offsets, shared
                      with metrics.evaluate_scene)
 """
+import contextlib
 import json
 
 import numpy as np
 import torch
 
-from .context import build_contexts
+from .context import build_contexts, build_contexts_ragged
 
 _XYZI_F32 = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4")])
 _XYZ_F32_I_U2 = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<u2")])
@@ -92,6 +93,37 @@ def refine_scene(model, pcd_points, raw_lines, num_line_points=32, num_context_p
     return (noisy + offset).cpu().numpy(), noisy.cpu().numpy()                                 # :146
 
 
+@contextlib.contextmanager
+def _inference_scope(model, precision):
+    """Eval mode and the encoder / decoder precision of one scene_offsets call, undone on the way out."""
+    was_training = model.training
+    model.eval()
+    from . import ops as _ops
+    enc = getattr(model, "context_encoder", None)
+    old_prec = getattr(enc, "inference_precision", None)
+    if precision not in (None, "fp32", "fp16", "layers"):
+        raise ValueError("refine_scene: precision must be None, 'fp32', 'fp16' or 'layers'")
+    # fp16: decoder GEMMs on one bf16 plane for the duration of the call (process-wide setting: the
+    # scope holds a lock and restores the previous mode on the way out, exception or not)
+    mode_scope = _ops.gemm_mode_scope("bf16") if precision == "fp16" else contextlib.nullcontext()
+    try:
+        with mode_scope:
+            if precision is not None and enc is not None:
+                enc.inference_precision = None if precision == "layers" else precision
+            yield
+    finally:
+        model.train(was_training)
+        if enc is not None:
+            enc.inference_precision = old_prec
+
+
+def _last_layer_offsets(model, ctx, noisy_c, batch_lines):
+    outs = []
+    for s in range(0, ctx.shape[0], batch_lines):
+        outs.append(model(ctx[s:s + batch_lines], noisy_c[s:s + batch_lines])[-1])   # last layer, :139-141
+    return torch.cat(outs)
+
+
 @torch.no_grad()
 def scene_offsets(model, pcd_points, raw_lines, num_line_points=32, num_context_points=1024,
                   crop_radius=0.3, decay_scale=2.0, batch_lines=2048, seed=0, precision=None, return_counts=False):
@@ -105,32 +137,30 @@ def scene_offsets(model, pcd_points, raw_lines, num_line_points=32, num_context_
     cloud = cloud.to(dev, torch.float32)
     if cloud.dim() == 2 and cloud.shape[1] > 4:
         cloud = cloud[:, :4]                      # ASCII PCDs may carry extra fields: x y z intensity come first
-    was_training = model.training
-    model.eval()
-    from . import ops as _ops
-    enc = getattr(model, "context_encoder", None)
-    old_prec = getattr(enc, "inference_precision", None)
-    if precision not in (None, "fp32", "fp16", "layers"):
-        raise ValueError("refine_scene: precision must be None, 'fp32', 'fp16' or 'layers'")
-    import contextlib
-    # fp16: decoder GEMMs on one bf16 plane for the duration of the call (process-wide setting: the
-    # scope holds a lock and restores the previous mode on the way out, exception or not)
-    mode_scope = _ops.gemm_mode_scope("bf16") if precision == "fp16" else contextlib.nullcontext()
-    try:
-        with mode_scope:
-            if precision is not None and enc is not None:
-                enc.inference_precision = None if precision == "layers" else precision
-            ctx, noisy_c, centres, counts = build_contexts(cloud, raw_lines, num_line_points, num_context_points,
-                                                           crop_radius, decay_scale, seed)
-            outs = []
-            for s in range(0, ctx.shape[0], batch_lines):
-                outs.append(model(ctx[s:s + batch_lines], noisy_c[s:s + batch_lines])[-1])   # last layer, :139-141
-            offset = torch.cat(outs)
-            return (offset, noisy_c, centres, counts) if return_counts else (offset, noisy_c, centres)
-    finally:
-        model.train(was_training)
-        if enc is not None:
-            enc.inference_precision = old_prec
+    with _inference_scope(model, precision):
+        ctx, noisy_c, centres, counts = build_contexts(cloud, raw_lines, num_line_points, num_context_points,
+                                                       crop_radius, decay_scale, seed)
+        offset = _last_layer_offsets(model, ctx, noisy_c, batch_lines)
+        return (offset, noisy_c, centres, counts) if return_counts else (offset, noisy_c, centres)
+
+
+@torch.no_grad()
+def scene_offsets_ragged(model, points, slice_offsets, raw_lines, line_slice, slice_seeds, num_line_points=32,
+                         num_context_points=1024, crop_radius=0.3, decay_scale=2.0, batch_lines=2048, precision=None,
+                         return_counts=False, max_candidate_bytes=None):
+    """scene_offsets for the lines of many slices at once: one build_contexts_ragged call (points
+    (T,4) float32 CUDA cut by slice_offsets, line i cropped from slice line_slice[i] and drawn with
+    slice_seeds[line_slice[i]]), then the eval forward in chunks of batch_lines.  The contexts are
+    byte for byte those of one scene_offsets call per slice; the offsets differ from them only by
+    which rows share a forward call.  Same return values as scene_offsets."""
+    if len(raw_lines) == 0:
+        raise ValueError("scene_offsets_ragged: at least one line expected")
+    with _inference_scope(model, precision):
+        ctx, noisy_c, centres, counts = build_contexts_ragged(points, slice_offsets, raw_lines, line_slice, slice_seeds,
+                                                              num_line_points, num_context_points, crop_radius,
+                                                              decay_scale, max_candidate_bytes)
+        offset = _last_layer_offsets(model, ctx, noisy_c, batch_lines)
+        return (offset, noisy_c, centres, counts) if return_counts else (offset, noisy_c, centres)
 
 
 class SceneSampleStream:
@@ -168,7 +198,11 @@ class SceneSampleStream:
     candidate k of an item is drawn on the device with scale ``augment[k]`` from a counter hash of
     (seed, epoch, scene, item, k) (``drive.noisy_candidates``), so every epoch sees fresh noise and
     the same epoch always the same.  Everything else - ``len()``, sharding, padding, batching - works
-    on the (item, k) pairs as before."""
+    on the (item, k) pairs as before.
+
+    Every scene is still one ``build_contexts`` call; ``context.build_contexts_ragged`` (many clouds in
+    one point buffer, every line cropped from its own) is the way to pool ``mix_scenes`` scenes into
+    one call later."""
 
     def __init__(self, data_root, num_line_points=32, num_context_points=2048, crop_radius=4.0,
                  decay_scale=2.0, split="train", device="cuda", seed=0, batch_size=None, shuffle=True,

@@ -290,7 +290,8 @@ def fuse_unmatched(pieces, piece_pose, poses_xyzq, gate=GATE, min_in=MIN_IN, out
 def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_context_points=1024, crop_radius=0.3,
                        decay_scale=2.0, seed=0, precision=None, segment_len=None, radius=None, max_pose_gap=None,
                        min_tube_points=F.MIN_TUBE_POINTS, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATIO,
-                       min_pieces=MIN_PIECES, step=F.STEP, min_count=F.MIN_COUNT, max_gap=F.MAX_GAP, origin=None):
+                       min_pieces=MIN_PIECES, step=F.STEP, min_count=F.MIN_COUNT, max_gap=F.MAX_GAP, origin=None,
+                       batched=False):
     """A detector run refined into one drive-frame map, with no GT.
 
     drive_dir holds pose/*.json and merged.pcd; results_json is the detector's output
@@ -299,7 +300,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     that has a pose; per frame, io.scene_offsets runs the model on that frame's device-resident slice
     with the pixel_to_ego lines as candidates, exactly what refine_drive does per slice; a piece
     whose tube held fewer than min_tube_points cloud points is left out and counted; fuse_unmatched
-    links and fuses the rest.
+    links and fuses the rest.  batched=True replaces the per-frame loop by one
+    io.scene_offsets_ragged call over all frames (fuse.refine_slices_batched), as in refine_drive.
 
     Returns {'fused' [per kept cluster], 'pieces' (P,M,3) float64 ego frame, 'piece_frame' (P,) the
     row of 'poses' each piece was seen from, 'piece_slice' (the same), 'pose_index' (per used frame
@@ -326,24 +328,29 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
         points, offsets, _ = D.slice_cloud(np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4), pq, segment_len,
                                            PR.RADIUS if radius is None else radius)
         off = offsets.cpu().numpy()
-        for si, n in enumerate(with_pose):
-            cands = [PR.pixel_to_ego(px) for px in frames[n]["pixels"]]
-            if not cands:
-                continue
-            if off[si + 1] == off[si]:
-                sparse += len(cands)                   # no cloud at all in this frame's slice
-                continue
-            pts = points[off[si]:off[si + 1]].to(torch.float32)
-            offset, noisy_c, centres, counts = scene_offsets(model, pts, cands, m, num_context_points, crop_radius,
-                                                             decay_scale, seed=int(seed) * 1000003 + si,
-                                                             precision=precision, return_counts=True)
-            refined = (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy()
-            keep = counts.cpu().numpy() >= int(min_tube_points)
-            sparse += int((~keep).sum())
-            for r in np.flatnonzero(keep):
-                pieces.append(refined[r])
-                piece_frame.append(si)
-    pieces = np.stack(pieces) if pieces else np.zeros((0, m, 3))
+        if batched:
+            pieces, piece_frame, _, sparse = F.refine_slices_batched(
+                model, points, off, [[PR.pixel_to_ego(px) for px in frames[n]["pixels"]] for n in with_pose], m,
+                num_context_points, crop_radius, decay_scale, seed, precision, min_tube_points)
+        else:
+            for si, n in enumerate(with_pose):
+                cands = [PR.pixel_to_ego(px) for px in frames[n]["pixels"]]
+                if not cands:
+                    continue
+                if off[si + 1] == off[si]:
+                    sparse += len(cands)                   # no cloud at all in this frame's slice
+                    continue
+                pts = points[off[si]:off[si + 1]].to(torch.float32)
+                offset, noisy_c, centres, counts = scene_offsets(model, pts, cands, m, num_context_points, crop_radius,
+                                                                 decay_scale, seed=int(seed) * 1000003 + si,
+                                                                 precision=precision, return_counts=True)
+                refined = (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy()
+                keep = counts.cpu().numpy() >= int(min_tube_points)
+                sparse += int((~keep).sum())
+                for r in np.flatnonzero(keep):
+                    pieces.append(refined[r])
+                    piece_frame.append(si)
+    pieces = np.stack(pieces) if len(pieces) else np.zeros((0, m, 3))
     piece_frame = np.asarray(piece_frame, dtype=np.int64)
     fused, nodes = fuse_unmatched(pieces, piece_frame, pq, gate, min_in, out_ratio, min_pieces, step, min_count, max_gap,
                                   origin, return_nodes=True)
