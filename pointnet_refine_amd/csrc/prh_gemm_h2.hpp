@@ -523,8 +523,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
       if (want_cs) { cs.x += a.x; cs.y += a.y; cs.z += a.z; cs.w += a.w; }
       float4 y = xb[j];
       if (PROB == PRO_BNRELU) {
-        y.x = fmaxf(fmaf(y.x, qa.x, qb.x), 0.f); y.y = fmaxf(fmaf(y.y, qa.y, qb.y), 0.f);
-        y.z = fmaxf(fmaf(y.z, qa.z, qb.z), 0.f); y.w = fmaxf(fmaf(y.w, qa.w, qb.w), 0.f);
+        // rows beyond the split read z = 0, i.e. relu(shift) * sB: unbounded by the operand
+        // maximum (a column whose mean lies many standard deviations from zero), and inf in the
+        // fp16 planes times A's exact zero would be NaN - relu_f16 keeps them finite
+        y.x = relu_f16(fmaf(y.x, qa.x, qb.x)); y.y = relu_f16(fmaf(y.y, qa.y, qb.y));
+        y.z = relu_f16(fmaf(y.z, qa.z, qb.z)); y.w = relu_f16(fmaf(y.w, qa.w, qb.w));
       } else {
         y.x *= sBm; y.y *= sBm; y.z *= sBm; y.w *= sBm;
       }

@@ -90,6 +90,10 @@ __device__ __forceinline__ float load_amax(const float* p) {
   return __uint_as_float(__builtin_amdgcn_readfirstlane(u));
 }
 
+// relu of an already scaled value, clamped to 2^15: a no-op on every element the operand maximum
+// covers (amax * S < 2^14), and one instruction (v_med3_f32) like the plain relu it replaces
+__device__ __forceinline__ float relu_f16(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, 32768.f); }
+
 // split two (already scaled) floats into packed fp16 pairs (h, l)
 __device__ __forceinline__ void split2h(float a0, float a1, unsigned& h, unsigned& l) {
   f32x2 v = {a0, a1};
@@ -624,7 +628,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_s3_kernel(const TNParams p) {
   // Plain A operand (PRO_NONE): rows beyond the split and columns beyond Mo need no select -
   // the buffer descriptor returns 0 for the rows, and the column mask rides on the scale
   // (finite neighbours x 0).  With A exactly zero there, B needs no row mask either (finite
-  // x 0), and its column mask is the zeroed coefficient pair / scale.
+  // x 0), and its column mask is the zeroed coefficient pair / scale.  Finite is not free for a
+  // BN+ReLU B operand: a row beyond the split reads z = 0 and becomes relu(shift) * sB, which no
+  // operand maximum bounds - relu_f16 clamps it below the fp16 limit.
   constexpr bool LEAN = PROA == PRO_NONE && NPL == 2;
   const float sAm = aok ? sA : 0.f, sBm = bok ? sB : 0.f;
   const bool want_cs = p.colsum != nullptr && tile_n == 0;
@@ -683,7 +689,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_s3_kernel(const TNParams p) {
       const bool rok = (r0 + j) < p_end;
       if (LEAN) {
         ta[j] = xa[j] * sAm;
-        tb[j] = PROB == PRO_BNRELU ? fmaxf(fmaf(xb[j], qa, qb), 0.f) : xb[j] * sBm;
+        tb[j] = PROB == PRO_BNRELU ? relu_f16(fmaf(xb[j], qa, qb)) : xb[j] * sBm;
         if (want_cs) csum += ta[j];
         continue;
       }

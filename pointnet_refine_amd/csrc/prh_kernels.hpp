@@ -110,7 +110,7 @@ __global__ void bn_fwd_finalize_kernel(const double* __restrict__ sl, int P, int
 // Largest value of relu(z*scale + shift) from the per-row-block column maxima / minima the
 // statistics epilogue recorded (the activation is convex in z, so its maximum over a set of
 // rows sits at that set's largest or smallest z): the exact operand maximum of the next GEMM,
-// without a pass over the activations.  grid (ceil(N/32), BN_SLICES); part[] -> absmax_final.
+// without a pass over the activations.  grid (<= ceil(N/32), BN_SLICES); part[] -> absmax_final.
 __global__ __launch_bounds__(256) void act_amax_kernel(const float* __restrict__ ws_c,
                                                        const float* __restrict__ ws_d, int R, long ld, int N,
                                                        const float* __restrict__ scale,
@@ -118,19 +118,21 @@ __global__ __launch_bounds__(256) void act_amax_kernel(const float* __restrict__
                                                        float* __restrict__ part) {
   __shared__ float red[256];
   const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int col = blockIdx.x * 32 + c, sl = blockIdx.y;
+  const int sl = blockIdx.y;
   const int per = (R + BN_SLICES - 1) / BN_SLICES;
   const int r0 = sl * per, r1 = (r0 + per < R) ? r0 + per : R;
-  float mx = -3.0e38f, mn = 3.0e38f;
-  if (col < N)
+  float a = 0.f;
+  // the grid is capped at ABSMAX_MAX_BLOCKS partials: a wider layer takes further column trips
+  for (int col = blockIdx.x * 32 + c; col < N; col += gridDim.x * 32) {
+    float mx = -3.0e38f, mn = 3.0e38f;
     for (int i = r0 + g; i < r1; i += 8) {
       mx = fmaxf(mx, ws_c[(size_t)i * ld + col]);
       mn = fminf(mn, ws_d[(size_t)i * ld + col]);
     }
-  float a = 0.f;
-  if (col < N && mx >= mn) {
-    const float sc = scale[col], sh = shift[col];
-    a = fmaxf(fmaxf(fmaf(mx, sc, sh), fmaf(mn, sc, sh)), 0.f);
+    if (mx >= mn) {
+      const float sc = scale[col], sh = shift[col];
+      a = fmaxf(a, fmaxf(fmaf(mx, sc, sh), fmaf(mn, sc, sh)));
+    }
   }
   red[threadIdx.x] = a;
   __syncthreads();

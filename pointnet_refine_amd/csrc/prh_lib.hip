@@ -816,13 +816,18 @@ int bn_coeffs(const prh_bn_layer& ly, int P, int training, float momentum, float
     hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(cdiv(ly.cout, 128)), dim3(128), 0, st, stat2, P,
                        ly.cout, ly.gamma, ly.beta, ly.running_mean, ly.running_var,
                        ly.num_batches_tracked, momentum, eps, mean, rstd, scale, shift);
-    if (amax_slot != nullptr && ws_c != nullptr && cdiv(ly.cout, 32) * BN_SLICES <= ABSMAX_MAX_BLOCKS) {
+    if (amax_slot != nullptr && ws_c != nullptr) {
+      // every requested slot is written: its consumers do not measure.  apart holds
+      // ABSMAX_MAX_BLOCKS partials, so a layer wider than that many 32-column blocks per slice
+      // has each block walk several column groups
+      int gx = cdiv(ly.cout, 32);
+      gx = gx > ABSMAX_MAX_BLOCKS / BN_SLICES ? ABSMAX_MAX_BLOCKS / BN_SLICES : gx;
       LAUNCH_CHECK();
-      hipLaunchKernelGGL(act_amax_kernel, dim3(cdiv(ly.cout, 32), BN_SLICES), dim3(256), 0, st, ws_c, ws_d,
+      hipLaunchKernelGGL(act_amax_kernel, dim3(gx, BN_SLICES), dim3(256), 0, st, ws_c, ws_d,
                          si.count, (long)ly.cout, ly.cout, (const float*)scale, (const float*)shift, apart);
       LAUNCH_CHECK();
       hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, (const float*)apart,
-                         cdiv(ly.cout, 32) * BN_SLICES, amax_slot);
+                         gx * BN_SLICES, amax_slot);
     }
   } else {
     hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3(cdiv(ly.cout, 256)), dim3(256), 0, st, ly.gamma,

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import threading
+import weakref
 from typing import List, Optional, Sequence
 
 import torch
@@ -389,8 +390,8 @@ class LinearFn(torch.autograd.Function):
         if n % 4:
             raise RuntimeError("pointnet_refine_amd.linear backward: out_features must be a multiple of 4")
         dy2 = dy.reshape(rows, n)
-        hint = _DY_AMAX.pop(dy.data_ptr(), None) if _DY_AMAX else None
-        dy_amax = hint[0] if (hint is not None and hint[1] == tuple(dy.shape) and dy2.data_ptr() == dy.data_ptr()) else None
+        hint = _hint_take(dy)
+        dy_amax = hint if (hint is not None and dy2.data_ptr() == dy.data_ptr()) else None
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         dev = x2.device
@@ -1039,10 +1040,29 @@ def _rows_view(t: torch.Tensor, name: str):
     return t, t.stride(1)
 
 
-# gradient tensor address -> (1-element bound of its largest magnitude, shape): filled by the
-# producer of a gradient that knows the bound (the attention backward), consumed once by
-# LinearFn.backward
+# id(gradient tensor) -> (1-element bound of its largest magnitude, shape, weak reference to the
+# tensor): filled by the producer of a gradient that knows the bound (the attention backward),
+# consumed once by LinearFn.backward.  A hint belongs to one tensor OBJECT (autograd hands the
+# object a backward returned to the next node): it is taken only by that object and dies with
+# it, so a hint nobody consumed can never be picked up by a later tensor that the allocator
+# placed at the same address.
 _DY_AMAX = {}
+
+
+def _hint_put(t, amax):
+    key = id(t)
+
+    def _drop(ref, key=key):
+        h = _DY_AMAX.get(key)
+        if h is not None and h[2] is ref:
+            del _DY_AMAX[key]
+
+    _DY_AMAX[key] = (amax, tuple(t.shape), weakref.ref(t, _drop))
+
+
+def _hint_take(t):
+    h = _DY_AMAX.pop(id(t), None) if _DY_AMAX else None
+    return h[0] if (h is not None and h[2]() is t and h[1] == tuple(t.shape)) else None
 
 
 KV_GRAD_IN_PLACE = True     # False: the K / V projection gradients get buffers of their own (A/B, debugging)
@@ -1085,12 +1105,12 @@ class KVTokenFn(torch.autograd.Function):
         dk, dv = a.dk, a.dv
         if a.part is not None:
             # bounds of max|dV|, max|dK| for the K/V projections' backward GEMMs: picked up by
-            # LinearFn.backward through the gradient tensors' addresses (one reduction of the
+            # LinearFn.backward through the gradient tensor objects (one reduction of the
             # per-wave maxima instead of a read pass over each gradient buffer)
             mx = a.part.amax(dim=(0, 1))
             _DY_AMAX.clear()      # at most this call's two hints are ever live (popped by their consumers)
-            _DY_AMAX[dv.data_ptr()] = (mx[0:1], tuple(dv.shape))
-            _DY_AMAX[dk.data_ptr()] = (mx[1:2], tuple(dk.shape))
+            _hint_put(dv, mx[0:1])
+            _hint_put(dk, mx[1:2])
         a.dk = a.dv = a.part = None
         a.written = set()
         return dk, dv, None, None
