@@ -5,11 +5,12 @@ prediction paired with the GT line the global assignment gives it - the files
 examples/evaluate_scenes.py reads.  Every frame of the drive goes through one slice, one clip, one
 cost and one assignment launch on the GPU.
 
-    python examples/predictions_to_scenes.py DRIVE_DIR GT_JSON RESULTS_JSON OUT_DIR [--evaluate CHECKPOINT]
+    python examples/predictions_to_scenes.py DRIVE_DIR GT_JSON RESULTS_JSON OUT_DIR [--evaluate CHECKPOINT [--batched]]
 
 --evaluate CHECKPOINT scores what was written with metrics.evaluate_scene (CHECKPOINT: a
 LineRefineNet state_dict, or "procedural" for deterministic weights that exercise the path only)
-and prints the mean ADE / Lat before and after over valid, non-bad-match rows.
+and prints the mean ADE / Lat before and after over valid, non-bad-match rows.  --batched scores
+every written frame with one metrics.evaluate_scenes call (clouds parsed on the device) instead.
 """
 import argparse
 import os
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("results_json")
     ap.add_argument("out_dir")
     ap.add_argument("--evaluate", metavar="CHECKPOINT", default=None)
+    ap.add_argument("--batched", action="store_true", help="--evaluate: one metrics.evaluate_scenes call for all frames")
     args = ap.parse_args()
     from pointnet_refine_amd import io, metrics, predictions
     res = predictions.predictions_to_scenes(args.drive_dir, args.gt_json, args.results_json, args.out_dir)
@@ -44,9 +46,17 @@ def main():
     model = model.cuda().eval()
     keep = {k: [] for k in ("ade_noisy", "ade_refined", "lat_noisy", "lat_refined")}
     rows = bad = 0
+    if args.batched:
+        from pointnet_refine_amd import pcd
+        scenes = [(pcd.read_pcd(os.path.join(args.out_dir, f"{ts}.pcd"), device="cuda"),
+                   io.load_scene_items(os.path.join(args.out_dir, f"{ts}.json"))) for ts in res["written"]]
+        evaluated = iter(metrics.evaluate_scenes(model, scenes))
     for ts in res["written"]:
-        items = io.load_scene_items(os.path.join(args.out_dir, f"{ts}.json"))
-        ev = metrics.evaluate_scene(model, io.load_pcd_data(os.path.join(args.out_dir, f"{ts}.pcd")), items)
+        if args.batched:
+            ev = next(evaluated)
+        else:
+            items = io.load_scene_items(os.path.join(args.out_dir, f"{ts}.json"))
+            ev = metrics.evaluate_scene(model, io.load_pcd_data(os.path.join(args.out_dir, f"{ts}.pcd")), items)
         use = ev["valid"] & ~ev["bad_match"]
         rows, bad = rows + len(use), bad + int(ev["bad_match"].sum())
         for k in keep:

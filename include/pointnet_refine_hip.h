@@ -426,6 +426,28 @@ size_t prh_shift_sweep_workspace_bytes(int n_pred, int n_gt, int n_shifts);
 int prh_shift_sweep(const double* pred, int n_pred, const double* gt, int n_gt, const double* shifts, int n_shifts,
                     double* out, void* workspace, size_t workspace_bytes, int device, void* stream);
 
+/* Ragged alignment sweep: n_problems independent prh_shift_sweep problems in one launch pair.
+ *   pred [*,3], shifts [*,2], out [*] are flat fp64 device buffers; problem p owns the rows
+ *   pred_offsets[p] .. pred_offsets[p+1] of pred and shift_offsets[p] .. shift_offsets[p+1] of
+ *   shifts and out.  gt [*,3] holds n_gt_sets point sets cut by gt_offsets [n_gt_sets+1]; problem p
+ *   measures against set gt_index[p], so problems may share a set.  All offset and index arrays
+ *   are HOST arrays (int64 offsets starting at 0, int32 indices): the call checks them, uploads a
+ *   per-problem table and synchronises the stream once before it launches.
+ *   out[shift_offsets[p] + s] = mean_q min_g |pred_q + (dx_s, dy_s, 0) - gt_g| over p's rows.
+ * Bitwise equal to one prh_shift_sweep call per problem: both run the same block routine (256
+ * queries x 16 shifts, tiles counted from the problem's own first point and shift) and the same
+ * in-order reduction of the block partials, in fp64 without contraction.
+ * Work items (problem, query tile, shift tile) form a flat 1-D grid: at most 2^31 - 1 items per
+ * call and fewer than 2^31 points, GT points and shifts per problem; no other per-problem limit.
+ * PRH_ERR_ARG for a problem without a prediction point, a GT point or a shift and for a GT index
+ * out of range; PRH_ERR_WORKSPACE below ..._workspace_bytes (0 there means the arrays are refused). */
+size_t prh_shift_sweep_ragged_workspace_bytes(const long long* pred_offsets, const long long* shift_offsets,
+                                              int n_problems);
+int prh_shift_sweep_ragged(const double* pred, const long long* pred_offsets, const double* gt,
+                           const long long* gt_offsets, int n_gt_sets, const int* gt_index, const double* shifts,
+                           const long long* shift_offsets, int n_problems, double* out, void* workspace,
+                           size_t workspace_bytes, int device, void* stream);
+
 /* Drive slicing (tools/generate_train_data.py:134-182,247-273; tools/augment_train_data.py:18-54).
  * poses [n_slices,7] fp64 = x y z qx qy qz qw (the quaternion is normalised).  A point of cloud
  * [npts,4] float32 belongs to slice s when, in float32 with every operation rounded separately,

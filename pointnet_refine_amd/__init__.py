@@ -5,8 +5,10 @@ context_proj, line point-MLP) behind the reference's nn.Module surface.
 """
 from .model import (DetrTransformerDecoderLayer, LineRefineNet, MultiScalePointNetEncoder,  # noqa: F401
                     PositionalEncoding)
-from .metrics import calibrate_alignment, evaluate_scene, line_metrics, shift_sweep  # noqa: F401
+from .metrics import (calibrate_alignment, calibrate_alignments, evaluate_scene, evaluate_scenes,  # noqa: F401
+                      line_metrics, shift_sweep, shift_sweep_ragged)
 
 __all__ = ["LineRefineNet", "MultiScalePointNetEncoder", "PositionalEncoding",
            "DetrTransformerDecoderLayer",
-           "line_metrics", "shift_sweep", "calibrate_alignment", "evaluate_scene"]
+           "line_metrics", "shift_sweep", "calibrate_alignment", "evaluate_scene",
+           "shift_sweep_ragged", "calibrate_alignments", "evaluate_scenes"]

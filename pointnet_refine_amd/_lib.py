@@ -79,6 +79,7 @@ EXPORTS = [
     "prh_context_workspace_bytes", "prh_context_build",
     "prh_context_ragged_workspace_bytes", "prh_context_ragged_count", "prh_context_ragged_select",
     "prh_line_metrics", "prh_shift_sweep_workspace_bytes", "prh_shift_sweep",
+    "prh_shift_sweep_ragged_workspace_bytes", "prh_shift_sweep_ragged",
     "prh_drive_slice_workspace_bytes", "prh_drive_slice_count", "prh_drive_slice_write",
     "prh_drive_clip_workspace_bytes", "prh_drive_clip_count", "prh_drive_clip_write",
     "prh_drive_noise_workspace_bytes", "prh_drive_noise",
@@ -237,6 +238,10 @@ def _bind(lib):
     lib.prh_shift_sweep_workspace_bytes.argtypes = [i, i, i]
     lib.prh_shift_sweep.restype = i
     lib.prh_shift_sweep.argtypes = [vp, i, vp, i, vp, i, vp, vp, sz, i, vp]
+    lib.prh_shift_sweep_ragged_workspace_bytes.restype = sz
+    lib.prh_shift_sweep_ragged_workspace_bytes.argtypes = [vp, vp, i]
+    lib.prh_shift_sweep_ragged.restype = i
+    lib.prh_shift_sweep_ragged.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, i, vp, vp, sz, i, vp]
     ll, dbl = C.c_longlong, C.c_double
     lib.prh_drive_slice_workspace_bytes.restype = sz
     lib.prh_drive_slice_workspace_bytes.argtypes = [i, i]

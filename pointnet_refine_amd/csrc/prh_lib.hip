@@ -2506,6 +2506,96 @@ int prh_shift_sweep(const double* pred, int n_pred, const double* gt, int n_gt, 
   return PRH_OK;
 }
 
+// ragged sweep: host plan shared by the workspace query and the entry point.  Checks every offset
+// array and builds the per-problem table, the work-item scan and the partial-sum CSR.
+struct SweepRaggedWS { MetSweepProblem* prob; long long* item_offsets; long long* shift_offsets; double* partial; };
+static void sweep_ragged_carve(Arena& a, SweepRaggedWS& w, int n, long long n_partial) {
+  w.prob = (MetSweepProblem*)a.f((size_t)n * sizeof(MetSweepProblem) / sizeof(float));
+  w.item_offsets = (long long*)a.f(2 * ((size_t)n + 1));
+  w.shift_offsets = (long long*)a.f(2 * ((size_t)n + 1));
+  w.partial = (double*)a.f(2 * (size_t)n_partial);
+}
+static int sweep_ragged_plan(const char* what, const long long* pred_offsets, const long long* gt_offsets,
+                             int n_gt_sets, const int* gt_index, const long long* shift_offsets, int n,
+                             std::vector<MetSweepProblem>* prob, std::vector<long long>* items, long long* n_partial) {
+  if (!pred_offsets || !shift_offsets || n <= 0 || (gt_offsets == nullptr) != (gt_index == nullptr) ||
+      (gt_offsets && n_gt_sets <= 0))
+    return fail(PRH_ERR_ARG, "%s: bad argument (offset arrays and at least one problem)", what);
+  if (pred_offsets[0] != 0 || shift_offsets[0] != 0 || (gt_offsets && gt_offsets[0] != 0))
+    return fail(PRH_ERR_ARG, "%s: offsets must start at 0", what);
+  if (gt_offsets)
+    for (int g = 0; g < n_gt_sets; ++g)
+      if (gt_offsets[g + 1] < gt_offsets[g]) return fail(PRH_ERR_ARG, "%s: gt_offsets must not decrease (set %d)", what, g);
+  if (prob) prob->resize((size_t)n);
+  if (items) items->assign((size_t)n + 1, 0);
+  long long n_items = 0, part = 0;
+  for (int p = 0; p < n; ++p) {
+    const long long P = pred_offsets[p + 1] - pred_offsets[p], S = shift_offsets[p + 1] - shift_offsets[p];
+    long long G = 1, g0 = 0;
+    if (gt_offsets) {
+      const int g = gt_index[p];
+      if (g < 0 || g >= n_gt_sets) return fail(PRH_ERR_ARG, "%s: problem %d names GT set %d of %d", what, p, g, n_gt_sets);
+      G = gt_offsets[g + 1] - gt_offsets[g];
+      g0 = gt_offsets[g];
+    }
+    if (P <= 0 || G <= 0 || S <= 0)
+      return fail(PRH_ERR_ARG, "%s: problem %d needs at least one point, one GT point and one shift", what, p);
+    if (P > 0x7fffffffll || G > 0x7fffffffll || S > 0x7fffffffll)
+      return fail(PRH_ERR_ARG, "%s: problem %d: at most 2^31 - 1 points, GT points and shifts per problem", what, p);
+    const long long n_qt = (P + SW_THREADS - 1) / SW_THREADS, n_st = (S + SW_SB - 1) / SW_SB;
+    if (prob) (*prob)[(size_t)p] = MetSweepProblem{pred_offsets[p], g0, shift_offsets[p], part, (int)P, (int)G, (int)S, (int)n_qt};
+    n_items += n_qt * n_st;                              // < 2^23 * 2^27: no overflow before the check
+    if (n_items > 0x7fffffffll)
+      return fail(PRH_ERR_ARG, "%s: more than 2^31 - 1 (problem, query tile, shift tile) work items", what);
+    if (items) (*items)[(size_t)p + 1] = n_items;
+    part += n_qt * S;
+  }
+  *n_partial = part;
+  return PRH_OK;
+}
+size_t prh_shift_sweep_ragged_workspace_bytes(const long long* pred_offsets, const long long* shift_offsets,
+                                              int n_problems) {
+  long long n_partial = 0;
+  if (sweep_ragged_plan("shift_sweep_ragged", pred_offsets, nullptr, 0, nullptr, shift_offsets, n_problems, nullptr,
+                        nullptr, &n_partial) != PRH_OK)
+    return 0;
+  Arena a; SweepRaggedWS w;
+  sweep_ragged_carve(a, w, n_problems, n_partial);
+  return a.off + 256;
+}
+int prh_shift_sweep_ragged(const double* pred, const long long* pred_offsets, const double* gt,
+                           const long long* gt_offsets, int n_gt_sets, const int* gt_index, const double* shifts,
+                           const long long* shift_offsets, int n_problems, double* out, void* workspace,
+                           size_t workspace_bytes, int device, void* stream) {
+  const char* what = "shift_sweep_ragged";
+  if (!pred || !gt || !shifts || !out || !gt_offsets || !gt_index) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  std::vector<MetSweepProblem> prob;
+  std::vector<long long> items;
+  long long n_partial = 0;
+  TRY(sweep_ragged_plan(what, pred_offsets, gt_offsets, n_gt_sets, gt_index, shift_offsets, n_problems, &prob, &items,
+                        &n_partial));
+  Arena a(workspace, workspace_bytes);
+  SweepRaggedWS w;
+  sweep_ragged_carve(a, w, n_problems, n_partial);
+  if (!workspace || !a.ok) return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  const size_t n = (size_t)n_problems;
+  const long long n_items = items[n], total_shifts = shift_offsets[n];
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemcpyAsync(w.prob, prob.data(), n * sizeof(MetSweepProblem), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.item_offsets, items.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.shift_offsets, shift_offsets, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));                 // the host tables above go out of scope on return
+  hipLaunchKernelGGL(met_sweep_ragged_kernel, dim3((unsigned)n_items), dim3(SW_THREADS), 0, st, pred, gt, shifts,
+                     (const MetSweepProblem*)w.prob, (const long long*)w.item_offsets, n_problems, w.partial);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(met_sweep_ragged_reduce_kernel, dim3((unsigned)((total_shifts + 255) / 256)), dim3(256), 0, st,
+                     (const double*)w.partial, (const MetSweepProblem*)w.prob, (const long long*)w.shift_offsets,
+                     n_problems, total_shifts, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
 // ------------------------------------------------------------------ drive slicing
 struct DrvWS { DrvPose* pose; int* cnt; long long* tile; };
 void drv_carve(Arena& a, DrvWS& w, int npts, int S) {

@@ -8,6 +8,9 @@
 //   met_sweep_kernel  calibrate_alignment's inner loop (:170-193) for S shifts in one launch:
 //                     per-block partial sums of min_g |pred_p + (dx_s,dy_s,0) - gt_g| over the
 //                     block's queries; met_sweep_reduce_kernel adds them in a fixed order
+//   met_sweep_ragged_kernel   many such sweeps in one launch: a flat grid of (problem, query tile,
+//                     shift tile) items over CSR buffers; it and met_sweep_kernel both drive
+//                     met_sweep_block / met_sweep_mean, so a problem gets the same bytes either way
 // All arithmetic is fp64 with FMA contraction off, and every distance is
 // sqrt((dx*dx + dy*dy) + dz*dz), the order np.linalg.norm(axis=1) uses: scene coordinates can be
 // UTM-sized (1e5..1e6 m), where fp32 - or the |q|^2 + |r|^2 - 2 q.r expansion - loses the
@@ -216,17 +219,20 @@ __global__ __launch_bounds__(64) void met_line_kernel(const double* __restrict__
   }
 }
 
-// Block (qt, st): queries qt*256 + tid against shifts st*16 .. st*16+15, every GT point.
-// partial[s * n_qt + qt] = sum over the block's queries of sqrt(min_g d^2), in a fixed order.
-// The shifted query is formed first (pred + (dx,dy,0)), as the reference does before its KDTree query.
-__global__ __launch_bounds__(SW_THREADS) void met_sweep_kernel(const double* __restrict__ pred, int P,
-                                                               const double* __restrict__ gt, int G,
-                                                               const double* __restrict__ shifts, int S,
-                                                               double* __restrict__ partial, int n_qt) {
+// Sweep block (qt, st) of one problem: queries qt*256 + tid against shifts st*16 .. st*16+15, every
+// GT point.  partial[s * n_qt + qt] = sum over the block's queries of sqrt(min_g d^2), in a fixed
+// order.  The shifted query is formed first (pred + (dx,dy,0)), as the reference does before its
+// KDTree query.  pred / gt / shifts / partial point at the problem's own first point, shift and
+// partial, so the per-problem and the ragged kernels hand a block the same operands in the same
+// order: their results are the same bytes.
+__device__ __forceinline__ void met_sweep_block(const double* __restrict__ pred, int P,
+                                                const double* __restrict__ gt, int G,
+                                                const double* __restrict__ shifts, int S,
+                                                double* __restrict__ partial, int n_qt, int qt, int st) {
 #pragma clang fp contract(off)
   __shared__ double gx[SW_TILE], gy[SW_TILE], gz[SW_TILE];
   __shared__ double red[SW_SB][SW_THREADS / 64];
-  const int tid = threadIdx.x, q = blockIdx.x * SW_THREADS + tid, s0 = blockIdx.y * SW_SB;
+  const int tid = threadIdx.x, q = qt * SW_THREADS + tid, s0 = st * SW_SB;
   const bool live = q < P;
   const int qc = live ? q : P - 1;
   const double px = pred[3 * (size_t)qc], py = pred[3 * (size_t)qc + 1], qz = pred[3 * (size_t)qc + 2] + 0.0;
@@ -234,8 +240,8 @@ __global__ __launch_bounds__(SW_THREADS) void met_sweep_kernel(const double* __r
 #pragma unroll
   for (int s = 0; s < SW_SB; ++s) {
     const int sc = s0 + s < S ? s0 + s : S - 1;
-    qx[s] = px + shifts[2 * sc];
-    qy[s] = py + shifts[2 * sc + 1];
+    qx[s] = px + shifts[2 * (size_t)sc];
+    qy[s] = py + shifts[2 * (size_t)sc + 1];
     best[s] = __builtin_inf();
   }
   for (int t0 = 0; t0 < G; t0 += SW_TILE) {
@@ -265,7 +271,23 @@ __global__ __launch_bounds__(SW_THREADS) void met_sweep_kernel(const double* __r
   }
   __syncthreads();
   if (tid < SW_SB && s0 + tid < S)
-    partial[(size_t)(s0 + tid) * n_qt + blockIdx.x] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+    partial[(size_t)(s0 + tid) * n_qt + qt] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+
+// (sum of shift s's block partials, in block order) / P
+__device__ __forceinline__ double met_sweep_mean(const double* __restrict__ partial, int n_qt, int s, int P) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+  for (int b = 0; b < n_qt; ++b) acc += partial[(size_t)s * n_qt + b];
+  return acc / (double)P;
+}
+
+// One problem: grid (n_qt, ceil(S/16)).
+__global__ __launch_bounds__(SW_THREADS) void met_sweep_kernel(const double* __restrict__ pred, int P,
+                                                               const double* __restrict__ gt, int G,
+                                                               const double* __restrict__ shifts, int S,
+                                                               double* __restrict__ partial, int n_qt) {
+  met_sweep_block(pred, P, gt, G, shifts, S, partial, n_qt, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // out[s] = (sum of the shift's block partials, in block order) / P
@@ -273,9 +295,54 @@ __global__ __launch_bounds__(256) void met_sweep_reduce_kernel(const double* __r
                                                                int P, double* __restrict__ out) {
   const int s = blockIdx.x * 256 + threadIdx.x;
   if (s >= S) return;
-  double acc = 0.0;
-  for (int b = 0; b < n_qt; ++b) acc += partial[(size_t)s * n_qt + b];
-  out[s] = acc / (double)P;
+  out[s] = met_sweep_mean(partial, n_qt, s, P);
+}
+
+// ---- ragged sweep: many independent problems in one launch pair
+// Problem p: predictions pred[pred0 .. pred0+P), GT points gt[gt0 .. gt0+G), shifts and outputs
+// [sh0 .. sh0+S), block partials partial[part0 .. part0 + n_qt*S) - rows of the flat buffers.
+struct MetSweepProblem {
+  long long pred0, gt0, sh0, part0;
+  int P, G, S, n_qt;
+};
+
+// The last entry of offsets[lo..hi) that is <= at (offsets strictly increase: no problem is empty)
+__device__ __forceinline__ int met_find(const long long* __restrict__ offsets, int lo, int hi, long long at) {
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offsets[mid] <= at) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// Flat 1-D grid of (problem, query tile, shift tile) work items.  item_offsets (n+1): exclusive scan
+// of n_qt_p * ceil(S_p/16); within a problem the query tile runs fastest.
+__global__ __launch_bounds__(SW_THREADS) void met_sweep_ragged_kernel(const double* __restrict__ pred,
+                                                                      const double* __restrict__ gt,
+                                                                      const double* __restrict__ shifts,
+                                                                      const MetSweepProblem* __restrict__ prob,
+                                                                      const long long* __restrict__ item_offsets,
+                                                                      int n_problems, double* __restrict__ partial) {
+  const long long item = (long long)blockIdx.x;
+  const int p = met_find(item_offsets, 0, n_problems, item);
+  const MetSweepProblem pr = prob[p];
+  const long long r = item - item_offsets[p];
+  const int st = (int)(r / pr.n_qt), qt = (int)(r - (long long)st * pr.n_qt);
+  met_sweep_block(pred + 3 * (size_t)pr.pred0, pr.P, gt + 3 * (size_t)pr.gt0, pr.G, shifts + 2 * (size_t)pr.sh0, pr.S,
+                  partial + (size_t)pr.part0, pr.n_qt, qt, st);
+}
+
+// One thread per (problem, shift) of the flat shift buffer; shift_offsets (n+1) finds the problem.
+__global__ __launch_bounds__(256) void met_sweep_ragged_reduce_kernel(const double* __restrict__ partial,
+                                                                      const MetSweepProblem* __restrict__ prob,
+                                                                      const long long* __restrict__ shift_offsets,
+                                                                      int n_problems, long long total_shifts,
+                                                                      double* __restrict__ out) {
+  const long long at = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (at >= total_shifts) return;
+  const int p = met_find(shift_offsets, 0, n_problems, at);
+  const MetSweepProblem pr = prob[p];
+  out[at] = met_sweep_mean(partial + (size_t)pr.part0, pr.n_qt, (int)(at - pr.sh0), pr.P);
 }
 
 }  // namespace prh

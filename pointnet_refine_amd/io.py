@@ -200,13 +200,16 @@ class SceneSampleStream:
     the same epoch always the same.  Everything else - ``len()``, sharding, padding, batching - works
     on the (item, k) pairs as before.
 
-    Every scene is still one ``build_contexts`` call; ``context.build_contexts_ragged`` (many clouds in
-    one point buffer, every line cropped from its own) is the way to pool ``mix_scenes`` scenes into
-    one call later."""
+    ``ragged=False`` builds every scene's contexts with one ``build_contexts`` call.  ``ragged=True``
+    pools the scenes of one ``mix_scenes`` group that this rank drew samples from into ONE
+    ``context.build_contexts_ragged`` call: their clouds are concatenated into one point buffer, every
+    sample is cropped from its own scene's cloud and drawn with its own scene's seed, so the batches
+    are byte for byte those of ``ragged=False`` - only the number of builder calls changes.  With
+    ``batch_size=None`` (one batch per scene) there is nothing to pool and ``ragged`` is ignored."""
 
     def __init__(self, data_root, num_line_points=32, num_context_points=2048, crop_radius=4.0,
                  decay_scale=2.0, split="train", device="cuda", seed=0, batch_size=None, shuffle=True,
-                 rank=None, world_size=None, mix_scenes=4, drop_last=False, augment=None):
+                 rank=None, world_size=None, mix_scenes=4, drop_last=False, augment=None, ragged=False):
         import os
         import torch.distributed as dist
         self.num_line_points, self.num_context_points = num_line_points, num_context_points
@@ -219,6 +222,7 @@ class SceneSampleStream:
             raise ValueError(f"SceneSampleStream: rank {self.rank} outside world_size {self.world}")
         self.batch_size, self.shuffle = batch_size, bool(shuffle)
         self.mix_scenes, self.drop_last = max(1, int(mix_scenes)), bool(drop_last)
+        self.ragged = bool(ragged)
         self.augment = None if augment is None else tuple(float(s) for s in augment)
         if self.augment is not None and not 1 <= len(self.augment) <= 8:
             raise ValueError("SceneSampleStream: augment takes 1..8 noise scales")
@@ -264,7 +268,9 @@ class SceneSampleStream:
         order = g.permutation(len(self.scenes)) if self.shuffle else np.arange(len(self.scenes))
         return [(int(si), mine.get(int(si), [])) for si in order]
 
-    def _scene_samples(self, si, pairs):
+    def _scene_inputs(self, si, pairs):
+        """(cloud (P,4) on the device, raw noisy lines, resampled GT (n,M,3), builder seed) of this
+        rank's samples of scene si."""
         from .context import resample_polyline
         pcd_path, json_path, _ = self.scenes[si]
         if self.device.type == "cuda":
@@ -284,11 +290,35 @@ class SceneSampleStream:
                                       (int(self.seed) * 1000003 + self.epoch) * 65537 + si, self.device)
             raw_noisy = [cands[k][row[i]] for i, k in pairs]
         gt = np.stack([resample_polyline(items[i]["position"], self.num_line_points) for i, _ in pairs])
-        ctx, noisy_c, centres, counts = build_contexts(
-            cloud, raw_noisy, self.num_line_points, self.num_context_points, self.crop_radius, self.decay_scale,
-            seed=((self.seed * 1000003 + self.epoch) * 65537 + si) * 1021 + self.rank)
+        return cloud, raw_noisy, gt, ((self.seed * 1000003 + self.epoch) * 65537 + si) * 1021 + self.rank
+
+    def _samples(self, ctx, noisy_c, centres, counts, gt):
         gt_c = torch.from_numpy(gt).to(self.device, torch.float32) - centres[:, None, :]
         return {"context": ctx, "noisy_line": noisy_c, "target_offset": gt_c - noisy_c, "points_in_tube": counts}
+
+    def _scene_samples(self, si, pairs):
+        cloud, raw_noisy, gt, seed = self._scene_inputs(si, pairs)
+        return self._samples(*build_contexts(cloud, raw_noisy, self.num_line_points, self.num_context_points,
+                                             self.crop_radius, self.decay_scale, seed=seed), gt)
+
+    def _group_samples(self, group):
+        """The samples of several scenes [(scene index, pairs)], in that order, from one
+        build_contexts_ragged call: the rows _scene_samples gives per scene, concatenated."""
+        clouds, raw, gts, seeds, line_slice = [], [], [], [], []
+        for s, (si, pairs) in enumerate(group):
+            cloud, raw_noisy, gt, seed = self._scene_inputs(si, pairs)
+            clouds.append(cloud)
+            raw.extend(raw_noisy)
+            gts.append(gt)
+            seeds.append(seed)
+            line_slice.extend([s] * len(pairs))
+        slice_offsets = np.zeros(len(clouds) + 1, dtype=np.int64)
+        slice_offsets[1:] = np.cumsum([c.shape[0] for c in clouds])
+        points = torch.cat(clouds)
+        del clouds
+        return self._samples(*build_contexts_ragged(points, slice_offsets, raw, line_slice, seeds, self.num_line_points,
+                                                    self.num_context_points, self.crop_radius, self.decay_scale),
+                             np.concatenate(gts))
 
     def __iter__(self):
         plan = self._plan()
@@ -311,10 +341,17 @@ class SceneSampleStream:
                 yield {k: pool[k][:bs] for k in keys}
                 pool = {k: pool[k][bs:] for k in keys} if pool[keys[0]].shape[0] > bs else None
 
+        group = []                               # ragged: this rank's scenes of the current mix_scenes group
         for j, (si, pairs) in enumerate(plan):
-            if pairs:
+            if pairs and self.ragged:
+                group.append((si, pairs))
+            elif pairs:
                 d = self._scene_samples(si, pairs)
                 pool = d if pool is None else {k: torch.cat([pool[k], d[k]]) for k in keys}
+            if group and ((j + 1) % self.mix_scenes == 0 or j + 1 == len(plan)):
+                d = self._group_samples(group)
+                pool = d if pool is None else {k: torch.cat([pool[k], d[k]]) for k in keys}
+                group = []
             if (j + 1) % self.mix_scenes == 0 and pool is not None:
                 if self.shuffle:
                     perm = torch.randperm(pool[keys[0]].shape[0], generator=g).to(self.device)
