@@ -4,6 +4,7 @@ input line in the drive frame (pointnet_refine_amd/fuse.py).
 
     python examples/refine_drive.py DRIVE_DIR LINES_JSON --checkpoint CKPT --out MAP.json
                                     [--noise S] [--seed N] [--gt GT_JSON] [--png DIR] [--batched]
+                                    [--support [--intensity-floor F]]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; LINES_JSON the lines to refine in the drive file layout
 (items[].category / attributes / position); MAP.json gets the fused map in the same layout.
@@ -11,7 +12,12 @@ DRIVE_DIR holds pose/*.json and merged.pcd; LINES_JSON the lines to refine in th
 way to try the pipeline on a drive that only has ground truth.  With --gt (default: LINES_JSON when
 --noise is given) three map_error figures against the ground truth are printed: the input lines,
 the refined pieces before fusion, and the fused map; GT_JSON must list the same lines in the same
-order.  --png DIR draws the fused map over the merged cloud (view3d.render_cloud3d).
+order.  --support scores the input lines and the fused map against the cloud itself, with no GT
+(pointnet_refine_amd/support.py): one MAP SUPPORT line with the share of the map's 0.5 m stations
+that have lidar points under them, the intensity-weighted lateral offset of those points from the
+input lines and from the fused map (where the paint lies; --intensity-floor F is subtracted from
+the intensity first, so asphalt weighs nothing) and the markings counted by type; every line's
+figures and its marking (solid / dashed / none) go into MAP.json's attributes.  --png DIR draws the fused map over the merged cloud (view3d.render_cloud3d).
 
 Without --checkpoint the model carries deterministic procedural weights (the run then exercises the
 path and says nothing about accuracy).
@@ -45,6 +51,15 @@ def show(label, e):
           f"({e['vertices']} vertices)")
 
 
+def show_support(fused, before, attributes):
+    kinds = [a["marking"] for a in attributes]
+    counted = ", ".join(f"{kinds.count(k)} {k}" for k in ("solid", "dashed", "none", "unknown") if kinds.count(k))
+    move = f"{fused['offset_w_mean']:+.4f} m" if before is None else \
+        f"{before['offset_w_mean']:+.4f} m -> {fused['offset_w_mean']:+.4f} m"
+    print(f"MAP SUPPORT  {100.0 * fused['supported_share']:.1f} % of {fused['nodes']} stations supported   "
+          f"offset_w mean {move}   markings: {counted or 'no lines'}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("drive_dir")
@@ -57,6 +72,8 @@ def main():
     ap.add_argument("--png", default=None)
     ap.add_argument("--step", type=float, default=0.5)
     ap.add_argument("--batched", action="store_true", help="contexts of all slices in one ragged GPU pass")
+    ap.add_argument("--support", action="store_true", help="score the map against the cloud (no GT needed)")
+    ap.add_argument("--intensity-floor", type=float, default=0.0)
     args = ap.parse_args()
 
     from pointnet_refine_amd import drive, fuse
@@ -67,12 +84,17 @@ def main():
         lines = [c[0] for c in drive.noisy_candidates(lines, (args.noise,), seed=args.seed)]
         print(f"Perturbed {len(lines)} lines at scale {args.noise} (seed {args.seed})")
     res = fuse.refine_drive(load_model(args.checkpoint), args.drive_dir, None, lines, seed=args.seed, step=args.step,
-                            batched=args.batched)
+                            batched=args.batched, support=args.support, intensity_floor=args.intensity_floor)
     rep = res["report"]
     print(f"{rep['slices']} slices, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['nodes_used']} of {rep['nodes']} nodes used, {rep['fused_polylines']} polylines")
-    n = fuse.write_map_json(args.out, res["fused"], categories=[it["category"] for it in items],
-                            attributes=[it["attributes"] for it in items])
+    attributes = [dict(it["attributes"]) for it in items]
+    if args.support:
+        sup = res["support"]
+        show_support(sup["fused"], sup["input"], sup["attributes"])
+        for attr, marking in zip(attributes, sup["attributes"]):
+            attr.update({k: None if v != v else v for k, v in marking.items()})      # nan has no JSON form
+    n = fuse.write_map_json(args.out, res["fused"], categories=[it["category"] for it in items], attributes=attributes)
     print(f"Wrote {n} polylines to {args.out}")
     if gt_path is not None:
         gt = [it["points"] for it in drive.load_gt_items(gt_path)]

@@ -5,12 +5,18 @@ frames into lanes and fused into one polyline per lane in the drive frame
 
     python examples/refine_predictions.py DRIVE_DIR RESULTS_JSON --checkpoint CKPT --out MAP.json
                                           [--gt GT_JSON] [--png DIR] [--batched]
+                                          [--support [--intensity-floor F]]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; RESULTS_JSON is the detector's output
 (predictions.load_results); MAP.json gets the fused map in the drive file layout
 (items[].category / attributes / position), one item per polyline with its cluster as 'source_line'.
 With --gt every fused cluster is attributed to the ground-truth line of smallest mean distance
 (fuse.project_to_lines) and the map's distance to those lines is printed (fuse.map_error).
+--support scores the fused map against the cloud itself (pointnet_refine_amd/support.py): one MAP
+SUPPORT line with the share of the map's 0.5 m stations that have lidar points under them, the
+intensity-weighted lateral offset of those points (--intensity-floor F is subtracted from the
+intensity first) and the markings counted by type; every cluster's figures and its marking (solid /
+dashed / none) go into MAP.json's attributes.
 --png DIR draws the fused map over a BEV intensity map of the merged cloud (bev.py).
 
 Without --checkpoint the model carries deterministic procedural weights (the run then exercises the
@@ -70,18 +76,29 @@ def main():
     ap.add_argument("--gate", type=float, default=1.0)
     ap.add_argument("--min-pieces", type=int, default=2)
     ap.add_argument("--batched", action="store_true", help="contexts of all frames in one ragged GPU pass")
+    ap.add_argument("--support", action="store_true", help="score the map against the cloud (no GT needed)")
+    ap.add_argument("--intensity-floor", type=float, default=0.0)
     args = ap.parse_args()
 
     from pointnet_refine_amd import drive, fuse, link
     res = link.refine_predictions(load_model(args.checkpoint), args.drive_dir, args.results_json, seed=args.seed,
-                                  step=args.step, gate=args.gate, min_pieces=args.min_pieces, batched=args.batched)
+                                  step=args.step, gate=args.gate, min_pieces=args.min_pieces, batched=args.batched,
+                                  support=args.support, intensity_floor=args.intensity_floor)
     rep = res["report"]
     print(f"{rep['slices']} frames, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['candidates']} candidate pairs, {rep['edges']} edges, {rep['clusters']} clusters, "
           f"{rep['clusters_kept']} kept ({rep['pieces_unlinked']} pieces unlinked), "
           f"{rep['nodes_used']} of {rep['nodes']} nodes used, {rep['fused_polylines']} polylines")
     fused = res["fused"]
-    n = fuse.write_map_json(args.out, fused, categories=["lane_line"] * len(fused))
+    attributes = None
+    if args.support:
+        sup = res["support"]
+        attributes = [{k: None if v != v else v for k, v in a.items()} for a in sup["attributes"]]   # nan has no JSON form
+        kinds = [a["marking"] for a in attributes]
+        counted = ", ".join(f"{kinds.count(k)} {k}" for k in ("solid", "dashed", "none", "unknown") if kinds.count(k))
+        print(f"MAP SUPPORT  {100.0 * sup['fused']['supported_share']:.1f} % of {sup['fused']['nodes']} stations supported   "
+              f"offset_w mean {sup['fused']['offset_w_mean']:+.4f} m   markings: {counted or 'no lines'}")
+    n = fuse.write_map_json(args.out, fused, categories=["lane_line"] * len(fused), attributes=attributes)
     print(f"Wrote {n} polylines to {args.out}")
     if args.gt is not None:
         gt = [it["points"] for it in drive.load_gt_items(args.gt)]

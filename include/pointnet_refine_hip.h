@@ -858,6 +858,63 @@ int prh_link_stats(const double* world, const double* cum, long long n_pieces, i
                    const long long* pair_offsets, const int* pair_j, long long n_pairs, double gate, int* pair_count,
                    double* pair_sum, int device, void* stream);
 
+/* Cloud support - the rule.
+ * What the merged cloud holds in the tube around every station of every map polyline: how many
+ * points, how bright, on which side, how high.  It needs no ground truth.  The conventions are
+ * those of "Map fusion - the rule": fp64, one rounding per operation, no contraction, a 3-vector
+ * dot is (p0 * q0 + p1 * q1) + p2 * q2, the origin is subtracted from the line vertices on the
+ * host, cum is the cumulative arc length of the shifted vertices computed on the host; the same
+ * bits go to the device and to the oracle (tests/_support_oracle.py).
+ * Inputs.  A cloud [T,4] float32 = x y z intensity in the drive frame, T < 2^31.  n_lines polylines
+ * in CSR form.  Parameters step (default 0.5 m, the station spacing), radius (default 0.3 m, 0 <
+ * radius <= 8, the tube radius) and intensity_floor (default 0), subtracted from the intensity
+ * before weighting.
+ * Nodes.  A line with at least one vertex has the nodes j = 0 .. floor(cum_total / step), as in
+ * fusion step 4; node_offsets [n_lines+1] numbers them line after line.
+ * Per point.  A point with a non-finite field is skipped.  Otherwise w[c] = (double)p[c] -
+ * origin[c].
+ * Per (point, line), independently for every line:
+ * 1. Projection.  Exactly fusion step 2: segments k = (a, b) with e = b - a and L2 = e.e > 0 are
+ *    usable; u = clamp(((w - a).e) / L2, 0, 1), c = a + u e, h = w - c, d2 = |h|^2.  The first k
+ *    with the strictly smallest d2 wins.  A line without a usable segment gets no hit.
+ * 2. Hit.  A hit iff d2 <= r2, where r2 = radius * radius is computed once on the host and passed
+ *    in: membership needs no sqrt.
+ * 3. Station.  s = cum[k] + u (cum[k+1] - cum[k]); j = min((long long)floor(s / step + 0.5),
+ *    n_nodes_l - 1).
+ * 4. Lateral offset.  With g = w - a and exy2 = e0 e0 + e1 e1: t = exy2 > 0 ? (e0 g1 - e1 g0) /
+ *    sqrt(exy2) : 0.  Positive is left of the line's direction seen from above.
+ * 5. Height.  hz = h[2].
+ * 6. Weight.  wI = min(max((double)I - intensity_floor, 0), 4096).
+ * 7. Fixed point, round-half-even (rint): qi = rint(wI * 256), qt = rint(t * 65536), qz =
+ *    rint(hz * 65536).
+ * 8. Accumulate into row node_offsets[l] + j of acc [n_nodes,8] int64: [0] += 1, [1] += (qi > 0),
+ *    [2] += qi, [3] += qt, [4] += qt * qt, [5] += qi * qt, [6] += qz.  Column [7] stays 0.
+ * A point inside the tubes of two lines counts for both.
+ * The sums are integers, so the result does not depend on the order of the points or on the
+ * launch shape: it is bitwise reproducible by construction.  With radius <= 8 and the weight clamp
+ * every addend is below 2^40; the host raises OverflowError when a node counts 2^22 points or
+ * more, so no column can pass 2^62.
+ *
+ * prh_support_accumulate: one thread per point, steps 1-8.  The host lays a uniform xy grid over the
+ * lines' bounding box expanded by the radius: cell (ix, iy) = (floor((x - grid_x0) / grid_cell),
+ * floor((y - grid_y0) / grid_cell)) in fp64, the same monotone expression on host and device, 0 <=
+ * ix < grid_nx, 0 <= iy < grid_ny, at most prh_support_max_cells() = 2^22 cells.  cell_offsets
+ * [grid_nx*grid_ny+1] int32 is the CSR of cell_entries [n_entries,2] int32 = (line, segment), cell
+ * iy * grid_nx + ix listing every segment whose radius-expanded box overlaps the cell, sorted by
+ * line, then by segment.  A thread leaves when its point is outside the grid or its cell is empty;
+ * otherwise it walks the list, keeps the best segment per line and flushes a hit when the line
+ * changes.  Every segment within radius of a point is in that point's list, so the first strictly
+ * smallest d2 of the list is step 1's whenever the point is a hit: the grid changes the cost, never
+ * the result.  cloud must be 16-byte aligned; acc is added to, so the caller zeroes it.  The adds
+ * are 64-bit integer atomics. */
+int prh_support_max_cells(void);
+int prh_support_accumulate(const float* cloud, long long n_points, double origin_x, double origin_y, double origin_z,
+                           double grid_x0, double grid_y0, double grid_cell, int grid_nx, int grid_ny,
+                           const int* cell_offsets, const int* cell_entries, long long n_entries,
+                           const double* line_vertices, const long long* line_offsets, const double* line_cum,
+                           int n_lines, const long long* node_offsets, long long n_nodes, double step, double r2,
+                           double intensity_floor, long long* acc, int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

@@ -94,6 +94,7 @@ EXPORTS = [
     "prh_fuse_gather_workspace_bytes", "prh_fuse_gather",
     "prh_link_tile", "prh_link_pairs_per_block", "prh_link_pairs_workspace_bytes", "prh_link_pairs_count",
     "prh_link_pairs_write", "prh_link_stats",
+    "prh_support_max_cells", "prh_support_accumulate",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -336,6 +337,11 @@ def _bind(lib):
     lib.prh_link_pairs_write.argtypes = [vp, ll, i, vp, dbl, vp, vp, vp, sz, i, vp]
     lib.prh_link_stats.restype = i
     lib.prh_link_stats.argtypes = [vp, vp, ll, i, vp, vp, ll, dbl, vp, vp, i, vp]
+    lib.prh_support_max_cells.restype = i
+    lib.prh_support_max_cells.argtypes = []
+    lib.prh_support_accumulate.restype = i
+    lib.prh_support_accumulate.argtypes = [vp, ll, dbl, dbl, dbl, dbl, dbl, dbl, i, i, vp, vp, ll, vp, vp, vp, i, vp, ll,
+                                           dbl, dbl, dbl, vp, i, vp]
     lib.prh_pcd_group_rows.restype = i
     lib.prh_pcd_group_rows.argtypes = []
     lib.prh_pcd_format_workspace_bytes.restype = sz

@@ -31,6 +31,7 @@
 #include "prh_view.hpp"
 #include "prh_fuse.hpp"
 #include "prh_link.hpp"
+#include "prh_support.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
@@ -3336,6 +3337,36 @@ int prh_link_stats(const double* world, const double* cum, long long n_pieces, i
   hipLaunchKernelGGL(link_stats_kernel, dim3((unsigned)((n_pairs + LINK_PAIRS - 1) / LINK_PAIRS)), dim3(LINK_THREADS), 0,
                      (hipStream_t)stream, world, cum, (int)n_pieces, M, pair_offsets, pair_j, n_pairs, gate, pair_count,
                      pair_sum);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ cloud support
+int prh_support_max_cells(void) { return 1 << 22; }
+int prh_support_accumulate(const float* cloud, long long n_points, double origin_x, double origin_y, double origin_z,
+                           double grid_x0, double grid_y0, double grid_cell, int grid_nx, int grid_ny,
+                           const int* cell_offsets, const int* cell_entries, long long n_entries,
+                           const double* line_vertices, const long long* line_offsets, const double* line_cum,
+                           int n_lines, const long long* node_offsets, long long n_nodes, double step, double r2,
+                           double intensity_floor, long long* acc, int device, void* stream) {
+  if (n_points < 0 || n_points > 0x7fffffffll || n_lines < 0 || n_nodes < 0 || n_entries < 0 || n_entries > 0x7fffffffll ||
+      grid_nx < 0 || grid_ny < 0 || !(step > 0.0) || !(r2 > 0.0) || !(r2 <= 64.0) || !(intensity_floor == intensity_floor))
+    return fail(PRH_ERR_ARG, "support_accumulate: bad argument (fewer than 2^31 points, step > 0, 0 < radius <= 8)");
+  if ((long long)grid_nx * grid_ny > (long long)prh_support_max_cells())
+    return fail(PRH_ERR_ARG, "support_accumulate: at most %d grid cells", prh_support_max_cells());
+  if (n_points == 0 || n_nodes == 0 || n_entries == 0 || grid_nx == 0 || grid_ny == 0) return PRH_OK;
+  if (!(grid_cell > 0.0) || !(grid_x0 == grid_x0) || !(grid_y0 == grid_y0))
+    return fail(PRH_ERR_ARG, "support_accumulate: bad grid");
+  if (((uintptr_t)cloud & 15) != 0) return fail(PRH_ERR_ARG, "support_accumulate: cloud must be 16-byte aligned");
+  if (!cloud || !cell_offsets || !cell_entries || !line_vertices || !line_offsets || !line_cum || !node_offsets || !acc ||
+      n_lines == 0)
+    return fail(PRH_ERR_ARG, "support_accumulate: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  SupportGrid grid{grid_x0, grid_y0, grid_cell, grid_nx, grid_ny};
+  hipLaunchKernelGGL(support_kernel, dim3((unsigned)((n_points + SUPPORT_THREADS - 1) / SUPPORT_THREADS)),
+                     dim3(SUPPORT_THREADS), 0, (hipStream_t)stream, (const float4*)cloud, n_points, origin_x, origin_y,
+                     origin_z, grid, cell_offsets, (const int2*)cell_entries, line_vertices, line_offsets, line_cum,
+                     node_offsets, n_lines, step, r2, intensity_floor, (unsigned long long*)acc);
   LAUNCH_CHECK();
   return PRH_OK;
 }

@@ -11,6 +11,7 @@ polyline per input line (``csrc/prh_fuse.hpp``; the rule is in ``include/pointne
                      segments that pass it) and the host's step 6 (nodes -> polylines)
   map_error          distance of a fused map to its lines and the share of their length it covers
   refine_drive       plan_slices, slice_cloud, clip_lines, io.scene_offsets per slice, fuse_pieces
+  cloud_support      refine_drive(support=True): support.map_support of the input lines and the fused map
   write_map_json     the drive file layout drive.load_gt_items reads
 
     res = refine_drive(model, "DRIVE_annotation_raw_data", None, [it["points"] for it in items])
@@ -331,7 +332,7 @@ def refine_slices_batched(model, points, off, cands, num_line_points, num_contex
 def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, num_context_points=1024, crop_radius=0.3,
                  decay_scale=2.0, seed=0, precision=None, segment_len=None, stride=None, radius=None, max_pose_gap=None,
                  step=STEP, min_count=MIN_COUNT, max_gap=MAX_GAP, min_tube_points=MIN_TUBE_POINTS, origin=None,
-                 batched=False):
+                 batched=False, support=False, support_radius=None, intensity_floor=0.0):
     """Refine the lines of a whole drive into one drive-frame map.
 
     drive_dir_or_cloud: a drive directory (merged.pcd and, when poses is None, pose/*.json) or the
@@ -350,10 +351,15 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     batched=True replaces the per-slice loop by one io.scene_offsets_ragged call over all slices
     (refine_slices_batched): the same contexts byte for byte, the same pieces in the same order up
     to which rows share a forward call.
+    support=True scores the input lines and the fused map against the cloud (support.map_support
+    with tube radius support_radius, default crop_radius, and intensity_floor): the lateral offset
+    of the paint before and after refinement, with no GT.
 
     Returns {'fused', 'pieces' (P,M,3) float64 ego frame, 'piece_line', 'piece_slice' (P,),
     'pose_index' (plan_slices), 'poses' (S,7) of the slices, 'nodes' (fuse_pieces' node dict),
-    'report': {'slices', 'pieces', 'pieces_sparse' (left out), 'nodes', 'nodes_used', 'fused_polylines'}}."""
+    'report': {'slices', 'pieces', 'pieces_sparse' (left out), 'nodes', 'nodes_used', 'fused_polylines'}}
+    and, with support=True, 'support': {'input', 'fused' (map_support's dicts), 'attributes'
+    (support.marking_attributes of the fused map, per line)}."""
     from . import drive as D
     from .io import load_pcd_data, scene_offsets
     G.device("fuse")
@@ -414,5 +420,21 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     report = {"slices": len(chosen), "pieces": int(len(pieces)), "pieces_sparse": int(sparse),
               "nodes": int(len(nodes["C"])), "nodes_used": int((nodes["C"] >= min_count).sum()),
               "fused_polylines": int(sum(len(f) for f in fused))}
-    return {"fused": fused, "pieces": pieces, "piece_line": piece_line, "piece_slice": piece_slice,
-            "pose_index": chosen, "poses": pq, "nodes": nodes, "report": report}
+    res = {"fused": fused, "pieces": pieces, "piece_line": piece_line, "piece_slice": piece_slice,
+           "pose_index": chosen, "poses": pq, "nodes": nodes, "report": report}
+    if support:
+        res["support"] = cloud_support(cloud, fused, lines, step, crop_radius if support_radius is None else support_radius,
+                                       intensity_floor, nodes["origin"])
+    return res
+
+
+def cloud_support(cloud, fused, lines, step, radius, intensity_floor, origin):
+    """refine_drive's and link.refine_predictions' 'support' entry: the cloud goes to the device
+    once and is read once per map.  lines None: no input map to score."""
+    from . import support as S
+    cloud_t = S._cloud(cloud, G.device("support"), "cloud_support")
+    kw = dict(step=step, radius=radius, intensity_floor=intensity_floor, origin=origin, per_line=True)
+    out = {} if lines is None else {"input": S.map_support(cloud_t, lines, **kw)}
+    out["fused"] = S.map_support(cloud_t, fused, **kw)
+    out["attributes"] = S.marking_attributes(out["fused"])
+    return out

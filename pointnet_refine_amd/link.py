@@ -291,7 +291,7 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
                        decay_scale=2.0, seed=0, precision=None, segment_len=None, radius=None, max_pose_gap=None,
                        min_tube_points=F.MIN_TUBE_POINTS, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATIO,
                        min_pieces=MIN_PIECES, step=F.STEP, min_count=F.MIN_COUNT, max_gap=F.MAX_GAP, origin=None,
-                       batched=False):
+                       batched=False, support=False, support_radius=None, intensity_floor=0.0):
     """A detector run refined into one drive-frame map, with no GT.
 
     drive_dir holds pose/*.json and merged.pcd; results_json is the detector's output
@@ -323,6 +323,7 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     with_pose = np.flatnonzero(chosen >= 0)
     pq = D.poses_xyzq(poses, chosen[with_pose]) if len(with_pose) else np.zeros((0, 7))
     pieces, piece_frame, sparse = [], [], 0
+    cloud = None
     if len(with_pose):
         cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
         points, offsets, _ = D.slice_cloud(np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4), pq, segment_len,
@@ -361,5 +362,12 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
               "edges": int(nodes["links"]["edge"].sum()),
               "clusters": int(all_clusters.max()) + 1 if len(all_clusters) else 0, "clusters_kept": len(fused),
               "pieces_unlinked": int((nodes["cluster"] < 0).sum())}
-    return {"fused": fused, "pieces": pieces, "piece_frame": piece_frame, "piece_slice": piece_frame.copy(),
-            "pose_index": [int(c) for c in chosen[with_pose]], "poses": pq, "nodes": nodes, "report": report}
+    res = {"fused": fused, "pieces": pieces, "piece_frame": piece_frame, "piece_slice": piece_frame.copy(),
+           "pose_index": [int(c) for c in chosen[with_pose]], "poses": pq, "nodes": nodes, "report": report}
+    if support:
+        if cloud is None:
+            cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
+        res["support"] = F.cloud_support(np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4), fused, None, step,
+                                         crop_radius if support_radius is None else support_radius, intensity_floor,
+                                         nodes["origin"])
+    return res
