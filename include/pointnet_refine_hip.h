@@ -247,6 +247,18 @@ int prh_linear_forward_full(const float* x, long ldx, const float* w, const floa
  * (src/model.py:131) leaves the GEMM epilogue already dropped out; no mask tensor exists, the backward
  * reads the decision off the output (prh_relu_mask_absmax with scale = 1 / (1 - p)). */
 
+/* Same plus the output's largest magnitude as a by-product: y_amax_out[0] = max|y| over exactly the elements
+ * written (after bias, residual, ReLU and dropout; a NaN is dropped as by fmaxf, rows = 0 gives 0) - the x_amax
+ * of the GEMM that reads y next, without a read pass over y.  On the second-generation split-fp16 core (GEMM
+ * mode 3, large 16-B aligned shapes) the maximum comes out of the GEMM epilogue plus one tiny reduction
+ * launch; every other core measures y after the GEMM, so the value is valid on return either way.
+ * y_amax_out NULL: exactly prh_linear_forward_full.  Otherwise the workspace is required
+ * (prh_linear_forward_workspace_bytes). */
+int prh_linear_forward_amax(const float* x, long ldx, const float* w, const float* b, const float* resid,
+                            long ldres, float* y, int rows, int k, int n, int relu, const float* x_amax,
+                            const float* w_amax, float dropout_p, unsigned dropout_seed, float* y_amax_out,
+                            void* workspace, size_t workspace_bytes, int device, void* stream);
+
 /* Operand maxima for the split-fp16 cores, measured once by the caller and handed to every GEMM
  * that reads the operand (x_amax / w_amax / dy_amax arguments; NULL = the launch measures it):
  * out[0] = max |x| over [rows, cols] (ld >= cols).  prh_linear_uses_operand_maxima: 1 when a
@@ -272,6 +284,12 @@ int prh_linear_uses_operand_maxima(int rows, int k, int n);
  * and hidden <= 256) for the decoder's query positions, which carry gradients. */
 int prh_pos_hidden_forward(const float* xyz, long ld, const float* w0, const float* b0, float* h,
                            long rows, int hidden, int device, void* stream);
+/* ... with h_amax_out[0] = max h (h >= 0) from the same pass plus one tiny reduction launch (NULL: exactly
+ * prh_pos_hidden_forward, no workspace needed). */
+size_t prh_pos_hidden_forward_workspace_bytes(void);
+int prh_pos_hidden_forward_amax(const float* xyz, long ld, const float* w0, const float* b0, float* h,
+                                long rows, int hidden, float* h_amax_out, void* workspace, size_t workspace_bytes,
+                                int device, void* stream);
 size_t prh_pos_hidden_backward_workspace_bytes(long rows, int hidden);
 int prh_pos_hidden_backward(const float* xyz, long ld, const float* h, const float* dh, const float* w0,
                             float* dxyz, float* dw0, float* db0, long rows, int hidden, void* workspace,
@@ -305,6 +323,14 @@ int prh_linear_backward_full(const float* x, long ldx, const float* w, const flo
                              float* dw, float* db, int rows, int k, int n, const float* x_amax,
                              const float* dy_amax, const float* w_amax, void* workspace,
                              size_t workspace_bytes, int device, void* stream);
+/* ... dx_accumulate != 0: dx += dy W (dx holds the addend on entry: the gradient fan-in of a tensor two
+ * Linears read is summed in the second one's dgrad epilogue, one fp32 addition per element, instead of a
+ * separate add pass), and dx_amax_out[0] = max|dx| of what dx holds afterwards (NULL = not wanted; produced
+ * by the epilogue or measured, as in prh_linear_forward_amax).  Both off: exactly prh_linear_backward_full. */
+int prh_linear_backward_amax(const float* x, long ldx, const float* w, const float* dy, float* dx,
+                             float* dw, float* db, int rows, int k, int n, const float* x_amax,
+                             const float* dy_amax, const float* w_amax, int dx_accumulate, float* dx_amax_out,
+                             void* workspace, size_t workspace_bytes, int device, void* stream);
 
 /* Stack of <= PRH_MAX_LAYERS shared-MLP layers applied to x [P,cin0]:
  * LineRefineNet.point_mlp, src/model.py:150-159,200-201 (relu_last = 0).

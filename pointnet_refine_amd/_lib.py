@@ -66,8 +66,9 @@ EXPORTS = [
     "prh_encoder_fused_image_bytes", "prh_encoder_fused_prepare", "prh_encoder_fused_workspace_bytes",
     "prh_encoder_fused_forward",
     "prh_linear_forward_workspace_bytes", "prh_linear_forward", "prh_linear_forward_ex",
-    "prh_linear_forward_full", "prh_operand_absmax_workspace_bytes", "prh_operand_absmax",
-    "prh_linear_uses_operand_maxima", "prh_linear_backward_full", "prh_pos_hidden_forward", "prh_pos_hidden_backward_workspace_bytes",
+    "prh_linear_forward_full", "prh_linear_forward_amax", "prh_operand_absmax_workspace_bytes", "prh_operand_absmax",
+    "prh_linear_uses_operand_maxima", "prh_linear_backward_full", "prh_linear_backward_amax", "prh_pos_hidden_forward",
+    "prh_pos_hidden_forward_workspace_bytes", "prh_pos_hidden_forward_amax", "prh_pos_hidden_backward_workspace_bytes",
     "prh_pos_hidden_backward", "prh_linear_small_forward", "prh_linear_small_backward_workspace_bytes",
     "prh_linear_small_backward",
     "prh_linear_backward_workspace_bytes", "prh_linear_backward", "prh_linear_backward_ex",
@@ -180,6 +181,14 @@ def _bind(lib):
     lib.prh_linear_forward_ex.argtypes = [vp, lg, vp, vp, vp, i, i, i, i, vp, vp, sz, i, vp]
     lib.prh_linear_forward_full.restype = i
     lib.prh_linear_forward_full.argtypes = [vp, lg, vp, vp, vp, lg, vp, i, i, i, i, vp, vp, f, C.c_uint, vp, sz, i, vp]
+    lib.prh_linear_forward_amax.restype = i
+    lib.prh_linear_forward_amax.argtypes = [vp, lg, vp, vp, vp, lg, vp, i, i, i, i, vp, vp, f, C.c_uint, vp, vp, sz, i, vp]
+    lib.prh_linear_backward_amax.restype = i
+    lib.prh_linear_backward_amax.argtypes = [vp, lg, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, i, vp, vp, sz, i, vp]
+    lib.prh_pos_hidden_forward_workspace_bytes.restype = sz
+    lib.prh_pos_hidden_forward_workspace_bytes.argtypes = []
+    lib.prh_pos_hidden_forward_amax.restype = i
+    lib.prh_pos_hidden_forward_amax.argtypes = [vp, lg, vp, vp, vp, lg, i, vp, vp, sz, i, vp]
     lib.prh_operand_absmax_workspace_bytes.restype = sz
     lib.prh_operand_absmax_workspace_bytes.argtypes = []
     lib.prh_operand_absmax.restype = i

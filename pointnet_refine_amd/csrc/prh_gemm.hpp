@@ -444,17 +444,29 @@ __device__ __forceinline__ void st4e(char* base, int off, float4 v) {
 // `profiles/r03p_epilogue_experiments.txt`): the shorter epilogue changes how far the workgroups of an XCD drift
 // apart, and with them the re-reads of the 8 MB weight image out of the Infinity Cache.  The bf16-storage launches
 // (k-loops a third as long, not power-bound) take the buffer-addressed form: 42.8 instead of 48.4 GB and 1-4 % less time.
-template <int EPI, int MT, class ACC, bool C16>
+// AMAX (EPI_BIAS, fp32 storage): the epilogue also keeps the largest magnitude of exactly the elements it
+// stores (after bias, residual, ReLU and dropout, where `ok` holds; fmaxf drops a NaN, nothing stored gives 0)
+// and hands the wave's maximum back through *wave_amax - the operand maximum of the GEMM that reads this
+// output next, without a pass over it.  In this form E1 may be C itself (C += A W^T: every element is
+// loaded and stored by the same lane, the store depends on the load), so its pointers are not __restrict__.
+// A compile-time option: the other instantiations have no register to spare (see below) and stay as they are.
+typedef char* __restrict__ epi_wptr_r;
+typedef const char* __restrict__ epi_rptr_r;
+template <int EPI, int MT, class ACC, bool C16, bool AMAX = false>
 __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, int rbase_,
                                                 int cbase, int rb, int lane, float* scratch,
-                                                bool bias_done = false) {     // bias already in acc
+                                                bool bias_done = false,      // bias already in acc
+                                                float* wave_amax = nullptr) {
+  static_assert(!AMAX || (EPI == EPI_BIAS && !C16), "output maximum: EPI_BIAS with fp32 storage");
+  typedef typename std::conditional<AMAX, char*, epi_wptr_r>::type wptr;
+  typedef typename std::conditional<AMAX, const char*, epi_rptr_r>::type rptr;
   const int rbase = __builtin_amdgcn_readfirstlane(rbase_);
   const float* biasp = bias_done ? nullptr : p.bias;
   constexpr int ES = C16 ? 2 : 4;
   const bool rowvec = EPI == EPI_DGRAD && (p.flags & F_E1_ROWVEC) != 0;
   const int ees = (C16 && !rowvec) ? 2 : 4;
-  char* __restrict__ Cb = reinterpret_cast<char*>(p.C) + (size_t)rbase * p.ldc * ES;
-  const char* __restrict__ Eb = p.E1 != nullptr ? reinterpret_cast<const char*>(p.E1) + (size_t)rbase * p.lde1 * ees : nullptr;
+  wptr Cb = reinterpret_cast<char*>(p.C) + (size_t)rbase * p.ldc * ES;
+  rptr Eb = p.E1 != nullptr ? reinterpret_cast<const char*>(p.E1) + (size_t)rbase * p.lde1 * ees : nullptr;
   const int ldc = (int)p.ldc, lde1 = (int)p.lde1;
   const int mrows = p.M - rbase;
   const int rr = lane >> 4, c4 = (lane & 15) * 4;     // row-major phase: 4 rows x 16 float4
@@ -491,9 +503,10 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
   // row groups: ~100 serialized round trips per tile.
   const int col4c = col4 < p.N ? col4 : (p.N - 4);
   // load bases: a wave tile entirely below the matrix reads (and discards) row 0 instead
-  const char* __restrict__ Cl = mrows > 0 ? Cb : reinterpret_cast<const char*>(p.C);
-  const char* __restrict__ El = mrows > 0 ? Eb : reinterpret_cast<const char*>(p.E1);
+  rptr Cl = mrows > 0 ? Cb : reinterpret_cast<const char*>(p.C);
+  rptr El = mrows > 0 ? Eb : reinterpret_cast<const char*>(p.E1);
   const bool acc_old = EPI == EPI_DGRAD && accum;
+  float amx = 0.f;      // AMAX: largest |v| this lane stored
   // Batches of 4 row groups (two per 32-row block), software-pipelined one deep: batch b+1's
   // operand loads are issued before batch b is processed.  (Measured against the unpipelined
   // order on one box: fusion dgrad 49.6 vs 50.0 ms - the wave sharing the SIMD already covers
@@ -594,6 +607,7 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
         }
       }
       if (ok) st4e<C16>(Cb, lr * ldc + col4, v);
+      if (AMAX && ok) amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
     // keep the running column sums here: left alone, the compiler sinks all 64 accumulation
     // steps into the F_STATS branch below and carries every v and z there (32 spilled VGPRs,
@@ -629,14 +643,20 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
       *reinterpret_cast<float4*>(p.ws_b + (size_t)rb * p.N + col4) = s2;
     }
   }
+  if (AMAX) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o));
+    *wave_amax = amx;
+  }
 }
 
-template <int EPI, int MT, class ACC, bool C16 = false>
+template <int EPI, int MT, class ACC, bool C16 = false, bool AMAX = false>
 __device__ __forceinline__ void nt_epilogue_vec(ACC& acc, const NTParams& p, int rbase_,
                                                 int cbase, int rb, int lane, float* scratch,
-                                                bool bias_done = false) {     // bias already in acc
+                                                bool bias_done = false,      // bias already in acc
+                                                float* wave_amax = nullptr) {
   if constexpr (!C16) {
-    nt_epilogue_vec_r2<EPI, MT, ACC, false>(acc, p, rbase_, cbase, rb, lane, scratch, bias_done);
+    nt_epilogue_vec_r2<EPI, MT, ACC, false, AMAX>(acc, p, rbase_, cbase, rb, lane, scratch, bias_done, wave_amax);
     return;
   }
   const int rbase = __builtin_amdgcn_readfirstlane(rbase_);

@@ -118,10 +118,14 @@ __device__ __forceinline__ void h2_compute(f32x4 (&acc)[8][4], const char* st, i
 // mix (fp16 MFMA on random mantissas + fp32 operand stream from HBM + split arithmetic); a denser issue stream is
 // paid back in clock (MI355X_MICROARCH.md, "DVFS give-back" item 3).  Off by default.
 // PP stays a template parameter: bench.py finds this kernel's PMC traffic by the prefix "prh::gemm_nt_h2_kernel<PRO, EPI,".
-template <int PRO, int EPI, bool PP = false>
+// AMAX (plain EPI_BIAS launches of the Linear entry points): the epilogue keeps the largest |output| it
+// stores, the workgroup's eight wave maxima meet in LDS and p.ws_a[blockIdx.x] takes the result (ws_a is
+// free in EPI_BIAS); absmax_final_kernel reduces the partials like those of a stand-alone read pass.
+template <int PRO, int EPI, bool PP = false, bool AMAX = false>
 __global__ __launch_bounds__(512, 2) void gemm_nt_h2_kernel(const NTParams p,
                                                             const char* __restrict__ Wp) {
   static_assert(PRO == PRO_NONE || PRO == PRO_BNRELU || PRO == PRO_GATE1, "prologue not supported");
+  static_assert(!AMAX || (PRO == PRO_NONE && EPI == EPI_BIAS), "output maximum: plain EPI_BIAS launches only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef PRH_STAMP
   unsigned t_acc[4] = {0u, 0u, 0u, 0u};
@@ -374,8 +378,21 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_h2_kernel(const NTParams p,
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[i][j][r] *= unscale;
-  nt_epilogue_vec<EPI, 4>(acc, p, m0 + wm, n0 + wn, tile_m * 2 + (wave >> 2), lane,
-                          reinterpret_cast<float*>(smem) + wave * (32 * EPI_LDW));
+  if constexpr (AMAX) {
+    float wmax = 0.f;
+    nt_epilogue_vec<EPI, 4, f32x4[8][4], false, true>(acc, p, m0 + wm, n0 + wn, tile_m * 2 + (wave >> 2), lane,
+                                                       reinterpret_cast<float*>(smem) + wave * (32 * EPI_LDW), false, &wmax);
+    __syncthreads();                   // every wave is done with its epilogue scratch
+    float* red = reinterpret_cast<float*>(smem);
+    if (lane == 0) red[wave] = wmax;
+    __syncthreads();
+    if (tid == 0)
+      p.ws_a[blockIdx.x] = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])),
+                                 fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));
+  } else {
+    nt_epilogue_vec<EPI, 4>(acc, p, m0 + wm, n0 + wn, tile_m * 2 + (wave >> 2), lane,
+                            reinterpret_cast<float*>(smem) + wave * (32 * EPI_LDW));
+  }
 #ifdef PRH_STAMP
   PRH_TICK(2)                        // epilogue: instructions issued
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

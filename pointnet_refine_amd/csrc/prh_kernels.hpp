@@ -735,10 +735,13 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restr
 // in place from the (B, N, C) context rows (ld = C), not from a sliced copy.
 // Thread -> 4 consecutive columns; the block covers 256 / (H/4) rows per pass.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pos_hidden_fwd_kernel(const float* __restrict__ xyz, long ld,
-                                                             const float* __restrict__ w0,
-                                                             const float* __restrict__ b0,
-                                                             float* __restrict__ h, long P, int H) {
+template <bool AMAX>
+__device__ __forceinline__ void pos_hidden_fwd_body(const float* __restrict__ xyz, long ld,
+                                                    const float* __restrict__ w0,
+                                                    const float* __restrict__ b0,
+                                                    float* __restrict__ h, long P, int H,
+                                                    float* __restrict__ part) {
+  float m = 0.f;
   const int cg = H >> 2, tc = threadIdx.x % cg, tr = threadIdx.x / cg, rpp = 256 / cg;
   float w[4][3], b[4];
 #pragma unroll
@@ -755,7 +758,32 @@ __global__ __launch_bounds__(256) void pos_hidden_fwd_kernel(const float* __rest
     o.z = fmaxf(fmaf(x2, w[2][2], fmaf(x1, w[2][1], fmaf(x0, w[2][0], b[2]))), 0.f);
     o.w = fmaxf(fmaf(x2, w[3][2], fmaf(x1, w[3][1], fmaf(x0, w[3][0], b[3]))), 0.f);
     *reinterpret_cast<float4*>(h + r * H + 4 * tc) = o;
+    if (AMAX) m = fmaxf(fmaxf(m, fmaxf(o.x, o.y)), fmaxf(o.z, o.w));
   }
+  if constexpr (AMAX) {
+    __shared__ float red[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  }
+}
+
+__global__ __launch_bounds__(256) void pos_hidden_fwd_kernel(const float* __restrict__ xyz, long ld,
+                                                             const float* __restrict__ w0,
+                                                             const float* __restrict__ b0,
+                                                             float* __restrict__ h, long P, int H) {
+  pos_hidden_fwd_body<false>(xyz, ld, w0, b0, h, P, H, nullptr);
+}
+// The same pass with the block's largest h into part[blockIdx.x] (h >= 0): the operand maximum of the
+// Linear(H, H) that reads h next, for absmax_final_kernel to reduce - no read pass over h.
+__global__ __launch_bounds__(256) void pos_hidden_fwd_amax_kernel(const float* __restrict__ xyz, long ld,
+                                                                  const float* __restrict__ w0,
+                                                                  const float* __restrict__ b0,
+                                                                  float* __restrict__ h, long P, int H,
+                                                                  float* __restrict__ part) {
+  pos_hidden_fwd_body<true>(xyz, ld, w0, b0, h, P, H, part);
 }
 
 // Its backward: dz = dh * (h > 0); part[block][c*4 + j] = sum_r dz[r,c] * xyz[r,j] (j < 3) and

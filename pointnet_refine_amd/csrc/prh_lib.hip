@@ -409,8 +409,15 @@ inline void small_tn_plan(int P, int Mo, int Ni, int& splits, int& rps) {
 }
 
 // ------------------------------------------------------------------ launch helpers
+// amax_part (plain EPI_BIAS launches): scratch of nt_amax_part_floats(M, N) floats; when the launch lands on
+// the second-generation split-fp16 core it runs the instantiation whose epilogue keeps the largest |C| it
+// stores, one partial per workgroup, and *amax_tiles is their number (0: this core has no such epilogue)
+inline size_t nt_amax_part_floats(int M, int N) {
+  const size_t t = (size_t)cdiv(M < 1 ? 1 : M, S3_BM) * cdiv(N < 1 ? 1 : N, S3_BN);
+  return (t > (size_t)ABSMAX_MAX_BLOCKS ? t : (size_t)ABSMAX_MAX_BLOCKS) + 64;
+}
 template <int PRO, int EPI>
-int launch_nt(Cores c, NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   // p.amaxA is filled in when measured
+int launch_nt_core(Cores c, NTParams& p, hipStream_t st, StatInfo* si, float* amax_part, long* amax_tiles) {   // p.amaxA is filled in when measured
   if (p.M <= 0 || p.N <= 0) return PRH_OK;
   if ((p.K & 3) || (PRO != PRO_GATE1 && (p.lda & 3)) || (p.ldw & 3) ||
       (PRO == PRO_BNBWD && (p.lda2 & 3)))
@@ -463,6 +470,18 @@ int launch_nt(Cores c, NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   
           if (attr_h2 != PRH_OK) return attr_h2;
           snprintf(nm, sizeof(nm), "gemm_nt_h2<%d,%d> K=%d N=%d", PRO, EPI, p.K, p.N);
           ProfScope ps(nm, 2.0 * p.M * (double)p.N * p.K, by, st);
+          if constexpr (PRO == PRO_NONE && EPI == EPI_BIAS) {
+            if (amax_part != nullptr) {
+              static const int attr_am = allow_big_lds(gemm_nt_h2_kernel<PRO, EPI, false, true>);
+              if (attr_am != PRH_OK) return attr_am;
+              const long wgs = (long)NTl * cdiv(p.M, 256);
+              p.ws_a = amax_part;
+              hipLaunchKernelGGL((gemm_nt_h2_kernel<PRO, EPI, false, true>), dim3((unsigned)wgs), dim3(512), lds, st, p, img);
+              LAUNCH_CHECK();
+              *amax_tiles = wgs;
+              return PRH_OK;
+            }
+          }
           if (g_h2_pp)
             hipLaunchKernelGGL((gemm_nt_h2_kernel<PRO, EPI, true>), dim3((unsigned)(NTl * cdiv(p.M, 256))), dim3(512),
                                lds, st, p, img);
@@ -508,6 +527,22 @@ int launch_nt(Cores c, NTParams& p, hipStream_t st, StatInfo* si = nullptr) {   
   LAUNCH_CHECK();
   if (si) { si->count = 2 * cdiv(p.M, BM); si->rows = 64; }
   return PRH_OK;
+}
+
+// amax_out: the largest |C| of the launch is valid there on return - from the epilogue where the core has that
+// form, else from a read pass over C (small core, first-generation and fp32 cores, modes other than 3)
+template <int PRO, int EPI>
+int launch_nt(Cores c, NTParams& p, hipStream_t st, StatInfo* si = nullptr, float* amax_out = nullptr,
+              float* amax_part = nullptr) {
+  long tiles = 0;
+  TRY_RC((launch_nt_core<PRO, EPI>(c, p, st, si, amax_part, &tiles)));
+  if (amax_out == nullptr) return PRH_OK;
+  if (tiles > 0) {
+    hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, (const float*)amax_part, (int)tiles, amax_out);
+    LAUNCH_CHECK();
+    return PRH_OK;
+  }
+  return measure_absmax<PRO_NONE>(p.C, p.ldc, nullptr, 0, nullptr, nullptr, nullptr, p.M, p.N, amax_out, amax_part, st);
 }
 
 constexpr int TN_S3_MAX_LD = 4096;   // widest operand row the split TN core accepts
@@ -1048,9 +1083,10 @@ void stack_bwd_scratch_carve(Cores c, Arena& a, StackBwdScratch& sc, int P, cons
 }
 
 // ---- workspace layouts of the entry points (measure with Arena(), carve with Arena(ptr,n))
-struct LinearBwdWS { float* wT; float* slab; float* cslab; char* wprep; };
+struct LinearBwdWS { float* wT; float* slab; float* cslab; char* wprep; float* dxpart; };
 void linear_bwd_carve(Cores c, Arena& a, LinearBwdWS& w, int rows, int k, int n) {
   w.wprep = (char*)a.f(s3_weight_bytes(k, n) / sizeof(float) + 64);
+  w.dxpart = a.f(nt_amax_part_floats(rows, k));      // partial maxima of dx (prh_linear_backward_amax)
   w.wT = a.f((size_t)k * n);
   w.slab = a.f(tn_slab_floats(c, rows, n, k));
   w.cslab = a.f(tn_colsum_floats(c, rows, n, k));
@@ -1173,8 +1209,8 @@ const char* prh_version(void) { return "pointnet_refine_hip 0.3 (gfx950: fp32 MF
 
 // ------------------------------------------------------------------ Linear
 size_t prh_linear_forward_workspace_bytes(int rows, int k, int n) {
-  (void)rows;
-  return s3_weight_bytes(n, k) + 512;
+  // weight image, then the partial output maxima of prh_linear_forward_amax
+  return align_up(s3_weight_bytes(n, k) + 512, 256) + nt_amax_part_floats(rows, n) * sizeof(float) + 256;
 }
 
 int prh_linear_forward_ex(const float* x, long ldx, const float* w, const float* b, float* y,
@@ -1187,8 +1223,17 @@ int prh_linear_forward_full(const float* x, long ldx, const float* w, const floa
                             long ldres, float* y, int rows, int k, int n, int relu, const float* x_amax,
                             const float* w_amax, float dropout_p, unsigned dropout_seed, void* workspace,
                             size_t workspace_bytes, int device, void* stream) {
+  return prh_linear_forward_amax(x, ldx, w, b, resid, ldres, y, rows, k, n, relu, x_amax, w_amax, dropout_p,
+                                 dropout_seed, nullptr, workspace, workspace_bytes, device, stream);
+}
+int prh_linear_forward_amax(const float* x, long ldx, const float* w, const float* b, const float* resid,
+                            long ldres, float* y, int rows, int k, int n, int relu, const float* x_amax,
+                            const float* w_amax, float dropout_p, unsigned dropout_seed, float* y_amax_out,
+                            void* workspace, size_t workspace_bytes, int device, void* stream) {
   if (!x || !w || !y || rows < 0 || k <= 0 || n <= 0 || (resid != nullptr && ldres < n))
     return fail(PRH_ERR_ARG, "linear_forward_full: bad argument");
+  if (y_amax_out != nullptr && (workspace == nullptr || workspace_bytes < prh_linear_forward_workspace_bytes(rows, k, n)))
+    return fail(PRH_ERR_WORKSPACE, "linear_forward_amax: workspace too small (%zu bytes)", workspace_bytes);
   if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(PRH_ERR_ARG, "linear_forward_full: dropout_p must be in [0,1)");
   HIP_TRY(hipSetDevice(device));
   NTParams p; memset(&p, 0, sizeof(p));
@@ -1204,7 +1249,10 @@ int prh_linear_forward_full(const float* x, long ldx, const float* w, const floa
   if (workspace != nullptr && workspace_bytes >= s3_weight_bytes(n, k) + 256)
     p.wprep = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   p.amaxA = x_amax;
-  return launch_nt<PRO_NONE, EPI_BIAS>(cores_of(gemm_mode()), p, (hipStream_t)stream);
+  float* part = nullptr;
+  if (y_amax_out != nullptr)
+    part = reinterpret_cast<float*>((((uintptr_t)workspace + 255) & ~(uintptr_t)255) + align_up(s3_weight_bytes(n, k) + 512, 256));
+  return launch_nt<PRO_NONE, EPI_BIAS>(cores_of(gemm_mode()), p, (hipStream_t)stream, nullptr, y_amax_out, part);
 }
 int prh_linear_forward(const float* x, long ldx, const float* w, const float* b, float* y,
                        int rows, int k, int n, int relu, void* workspace, size_t workspace_bytes,
@@ -1271,6 +1319,31 @@ int prh_pos_hidden_forward(const float* xyz, long ld, const float* w0, const flo
   if (nb > 8192) nb = 8192;
   hipLaunchKernelGGL(pos_hidden_fwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, xyz, ld,
                      w0, b0, h, rows, hidden);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+size_t prh_pos_hidden_forward_workspace_bytes(void) { return (size_t)8192 * sizeof(float) + 256; }
+int prh_pos_hidden_forward_amax(const float* xyz, long ld, const float* w0, const float* b0, float* h,
+                                long rows, int hidden, float* h_amax_out, void* workspace, size_t workspace_bytes,
+                                int device, void* stream) {
+  if (h_amax_out == nullptr) return prh_pos_hidden_forward(xyz, ld, w0, b0, h, rows, hidden, device, stream);
+  if (!xyz || !w0 || !h || rows < 0 || ld < 3) return fail(PRH_ERR_ARG, "pos_hidden_forward: bad argument");
+  if (!pos_hidden_ok(hidden))
+    return fail(PRH_ERR_ARG, "pos_hidden_forward: hidden=%d must be a power of two in [4, 1024]", hidden);
+  HIP_TRY(hipSetDevice(device));
+  Arena a(workspace, workspace_bytes);
+  float* part = a.f(8192);
+  if (!a.ok || workspace == nullptr) return fail(PRH_ERR_WORKSPACE, "pos_hidden_forward_amax: workspace too small (%zu bytes)", workspace_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  const long rpp = 256 / (hidden / 4);
+  long nb = (rows + rpp * 4 - 1) / (rpp * 4);
+  if (nb > 8192) nb = 8192;
+  if (rows > 0) {
+    hipLaunchKernelGGL(pos_hidden_fwd_amax_kernel, dim3((unsigned)nb), dim3(256), 0, st, xyz, ld, w0, b0, h, rows,
+                       hidden, part);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)(rows > 0 ? nb : 0), h_amax_out);
   LAUNCH_CHECK();
   return PRH_OK;
 }
@@ -1378,7 +1451,16 @@ int prh_linear_backward_full(const float* x, long ldx, const float* w, const flo
                              float* dw, float* db, int rows, int k, int n, const float* x_amax,
                              const float* dy_amax_in, const float* w_amax, void* workspace,
                              size_t workspace_bytes, int device, void* stream) {
+  return prh_linear_backward_amax(x, ldx, w, dy, dx, dw, db, rows, k, n, x_amax, dy_amax_in, w_amax, 0, nullptr,
+                                  workspace, workspace_bytes, device, stream);
+}
+int prh_linear_backward_amax(const float* x, long ldx, const float* w, const float* dy, float* dx,
+                             float* dw, float* db, int rows, int k, int n, const float* x_amax,
+                             const float* dy_amax_in, const float* w_amax, int dx_accumulate, float* dx_amax_out,
+                             void* workspace, size_t workspace_bytes, int device, void* stream) {
   if (!x || !w || !dy || rows < 0 || k <= 0 || n <= 0) return fail(PRH_ERR_ARG, "linear_backward: bad argument");
+  if ((dx_accumulate || dx_amax_out != nullptr) && dx == nullptr)
+    return fail(PRH_ERR_ARG, "linear_backward_amax: dx_accumulate / dx_amax_out need dx");
   if ((k & 3) || (n & 3)) return fail(PRH_ERR_ARG, "linear_backward: k=%d and n=%d must be multiples of 4", k, n);
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
@@ -1394,8 +1476,11 @@ int prh_linear_backward_full(const float* x, long ldx, const float* w, const flo
   if (dx != nullptr && !big16) {      // small problem: dgrad with the weight as stored (no transposed copy)
     NTParams p; memset(&p, 0, sizeof(p));
     p.A = dy; p.lda = n; p.W = w; p.ldw = k; p.C = dx; p.ldc = k; p.M = rows; p.N = k; p.K = n;
+    if (dx_accumulate) { p.flags = F_RESID; p.E1 = dx; p.lde1 = k; }
     if (small_nt_ok(p, true) && !(nt_use_s3(c, rows, k, n))) {
       TRY((launch_small<true>(p, st)));
+      if (dx_amax_out != nullptr)
+        TRY_RC((measure_absmax<PRO_NONE>(dx, k, nullptr, 0, nullptr, nullptr, nullptr, rows, k, dx_amax_out, lw.dxpart, st)));
       dx_done = true;
     }
   }
@@ -1406,7 +1491,11 @@ int prh_linear_backward_full(const float* x, long ldx, const float* w, const flo
     p.wprep = lw.wprep;
     p.amaxA = dy_amax;
     p.amaxW = w_amax;        // max |W^T| = max |W|
-    TRY((launch_nt<PRO_NONE, EPI_BIAS>(c, p, st)));
+    // dx += dy W: the old dx is the epilogue's residual operand; the instantiation with the output maximum is
+    // the one whose epilogue may read and write the same buffer, so an accumulating call takes it as well
+    if (dx_accumulate) { p.flags = F_RESID; p.E1 = dx; p.lde1 = k; }
+    TRY((launch_nt<PRO_NONE, EPI_BIAS>(c, p, st, nullptr, dx_amax_out,
+                                      (dx_accumulate || dx_amax_out != nullptr) ? lw.dxpart : nullptr)));
     dy_amax = p.amaxA;       // measured once for both GEMMs (lives in the head of lw.wprep)
   }
   if (dw != nullptr || db != nullptr) {

@@ -138,17 +138,27 @@ class PositionalEncoding(nn.Module):
         super().__init__()
         self.mlp = nn.Sequential(nn.Linear(in_dim, out_dim), nn.ReLU(), nn.Linear(out_dim, out_dim))
 
-    def forward(self, xyz, resid=None):
-        """resid: optional tensor added to the encoding (the decoder's k-input memory + pos,
-        src/model.py:123-126) - on the GPU it rides on the second Linear's epilogue."""
+    def hidden(self, xyz):
+        """(h, max h): Linear(3,H)+ReLU as one elementwise HIP pass over the points in place (a 3-deep GEMM is
+        HBM work); the pass also reports h's largest value (None where nothing consumes it, ops.PRODUCER_MAXIMA)."""
         l0, l2 = self.mlp[0], self.mlp[2]
         if l0.in_features != 3 or not ops.pos_hidden_supported(l0.out_features) or l2.out_features % 4:
             raise RuntimeError(f"pointnet_refine_amd: PositionalEncoding({l0.in_features}, {l2.out_features}) is not "
                                "supported by the HIP path (3-wide points, power-of-two hidden width <= 1024)")
-        # Linear(3,H)+ReLU: one elementwise HIP pass over the points in place (a 3-deep GEMM is HBM
-        # work); Linear(H,H) (+ resid) on the HIP GEMM cores
-        h = ops.pos_hidden(xyz, l0.weight, l0.bias)
-        return ops.linear(h, l2.weight, l2.bias, None, False, resid)
+        return ops.pos_hidden_with_amax(xyz, l0.weight, l0.bias)
+
+    def forward(self, xyz, resid=None):
+        """resid: optional tensor added to the encoding (the decoder's k-input memory + pos,
+        src/model.py:123-126) - on the GPU it rides on the second Linear's epilogue."""
+        l2 = self.mlp[2]
+        h, h_amax = self.hidden(xyz)
+        # Linear(H,H) (+ resid) on the HIP GEMM cores.  With a residual (the context side: B*N rows) h's maximum
+        # feeds the GEMM and the output's maximum is noted on the result for the Linear that reads it next
+        if resid is None:
+            return ops.linear(h, l2.weight, l2.bias, h_amax)
+        y, y_amax = ops.linear_with_amax(h, l2.weight, l2.bias, h_amax, False, resid)
+        ops.amax_note(y, y_amax)
+        return y
 
 
 class DetrTransformerDecoderLayer(nn.Module):
@@ -218,8 +228,9 @@ class DetrTransformerDecoderLayer(nn.Module):
         # linear2(dropout(relu(linear1(tgt)))) (src/model.py:131): ReLU AND the dropout ride on linear1's epilogue
         pd = self.dropout.p if self.training else 0.0
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if pd > 0.0 else 0
-        hid = ops.linear(tgt, self.linear1.weight, self.linear1.bias, None, True, None, pd, seed)
-        tgt2 = _lin(hid, self.linear2.weight, self.linear2.bias)
+        # hid's largest magnitude is a by-product of that epilogue: linear2 takes it instead of a read pass over hid
+        hid, hid_amax = ops.linear_with_amax(tgt, self.linear1.weight, self.linear1.bias, None, True, None, pd, seed)
+        tgt2 = ops.linear(hid, self.linear2.weight, self.linear2.bias, hid_amax)
         tgt = _add_norm(tgt, tgt2, self.norm3, self.dropout3, self.training)
         return tgt
 
@@ -268,7 +279,9 @@ class LineRefineNet(nn.Module):
                 _warn_saturated(e)
         _, fused, fused_amax = ops.encoder_with_amax(context, enc._param_list(), enc._bn_buffer_list(), False,
                                                      enc.training, enc.bn1.momentum, enc.bn1.eps)
-        return ops.linear(fused, self.context_proj.weight, self.context_proj.bias, fused_amax)
+        memory, mem_amax = ops.linear_with_amax(fused, self.context_proj.weight, self.context_proj.bias, fused_amax)
+        ops.amax_note(memory, mem_amax)      # decode() hands it to the V projection and the positional residual's consumer
+        return memory
 
     def encode_line(self, noisy_line):
         """noisy_line (B,M,3) -> initial queries (B,M,256): point_mlp (src/model.py:200-201)."""
@@ -314,7 +327,11 @@ class LineRefineNet(nn.Module):
             else:
                 mempos = self.pos_emb(context[:, :, :3], resid=memory)
                 k_all, v_all = ops.cast_perm_bf16(mempos), ops.cast_perm_bf16(memory)
-        else:
+        # split-fp16 training path: pos_emb's second Linear and the two wide projections are ONE autograd node
+        # that hands every operand maximum from its producer to its consumer (ops.PosKVFn)
+        span = (not fold and ops.producer_maxima_on(memory.is_cuda) and memory.dtype == torch.float32
+                and context.dtype == torch.float32)
+        if not fold and not span:
             mempos = self.pos_emb(context[:, :, :3], resid=memory)      # memory + pos_mem, (B, N, 256)
         cat = ops.cat_rows
         if d != 256:
@@ -326,6 +343,11 @@ class LineRefineNet(nn.Module):
             bv = cat([l.cross_attn.in_proj_bias[2 * d:] for l in layers])
         if fold:
             pass
+        elif span:
+            h, h_amax = self.pos_emb.hidden(context[:, :, :3])
+            l2 = self.pos_emb.mlp[2]
+            k_all, v_all = ops.pos_kv_project(h, memory, l2.weight, l2.bias, wk, bk, wv, bv, h_amax,
+                                              ops.amax_of(memory))       # (B, N, 6*256) each
         elif ops.bf16_mode() and mempos.is_cuda:
             # bf16 mode (BASELINE config 3): the wide K / V buffers and their gradients live in bf16
             k_all = ops.linear_out16(mempos, wk, bk)                # (B, N, 6*256) bf16

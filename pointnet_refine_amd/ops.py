@@ -274,8 +274,71 @@ def operand_absmax(t):
     return out
 
 
+# True: a kernel of ours that writes a split-fp16 GEMM operand also reports its largest magnitude (GEMM epilogue,
+# pos_hidden pass), the consumer takes that instead of a read pass over the operand, and the gradient fan-in at
+# `memory` is summed in the V projection's dgrad epilogue.  False: measured maxima and the stock add (A/B, debugging).
+PRODUCER_MAXIMA = True
+
+# id(activation tensor) -> (1-element largest magnitude its producer reported, shape, weak reference): the
+# forward-side counterpart of the gradient hints below (_hint_put): belongs to one tensor OBJECT, dies with it.
+_X_AMAX = {}
+
+
+def amax_note(t, amax):
+    """Attach the producer's max|t| to the tensor object `t` (model.py hands `memory`'s on to decode())."""
+    if amax is not None:
+        _note_put(_X_AMAX, t, amax)
+
+
+def amax_of(t):
+    """The maximum noted for this very tensor object, or None."""
+    h = _X_AMAX.get(id(t)) if _X_AMAX else None
+    return h[0] if (h is not None and h[2]() is t and h[1] == tuple(t.shape)) else None
+
+
+def _linear_fwd(x2, w, b, r2, relu, x_amax, dropout_p, seed, want_amax=False):
+    """prh_linear_forward_amax on contiguous 2-D operands -> (y, x_amax, w_amax, y_amax).  The operand maxima
+    of the split-fp16 cores are measured once here (x: unless supplied) and kept for the backward GEMMs, which
+    read x (wgrad) and W^T (dgrad) again; want_amax: max|y| comes back as a 1-element device tensor."""
+    rows, k = x2.shape
+    n = w.shape[0]
+    dev = x2.device
+    y = torch.empty((rows, n), dtype=torch.float32, device=dev)
+    ws = _ws(dev, L.lib().prh_linear_forward_workspace_bytes(rows, k, n))
+    w_amax = None
+    if n % 4 == 0 and L.lib().prh_linear_uses_operand_maxima(rows, k, n):
+        if x_amax is None:
+            x_amax = operand_absmax(x2)
+        w_amax = operand_absmax(w)
+    y_amax = torch.empty(1, dtype=torch.float32, device=dev) if want_amax else None
+    L.check(L.lib().prh_linear_forward_amax(_p(x2), k, _p(w), _p(b), _p(r2), n, _p(y), rows, k, n,
+                                            int(bool(relu)), _p(x_amax), _p(w_amax), float(dropout_p),
+                                            int(seed) & 0xFFFFFFFF, _p(y_amax), _p(ws), ws.numel(),
+                                            dev.index, _stream(dev)),
+            "prh_linear_forward")
+    return y, x_amax, w_amax, y_amax
+
+
+def _linear_bwd(x2, w, dy2, x_amax, dy_amax, w_amax, dx, dw, db, accumulate=False, want_amax=False):
+    """prh_linear_backward_amax: dx (None: skipped; accumulate: dx += dy W), dw, db written in place.
+    Returns max|dx| afterwards as a 1-element device tensor when want_amax."""
+    rows, k = x2.shape
+    n = w.shape[0]
+    dev = x2.device
+    ws = _ws(dev, L.lib().prh_linear_backward_workspace_bytes(rows, k, n))
+    dx_amax = torch.empty(1, dtype=torch.float32, device=dev) if (want_amax and dx is not None) else None
+    L.check(L.lib().prh_linear_backward_amax(_p(x2), k, _p(w), _p(dy2), _p(dx), _p(dw), _p(db), rows,
+                                             k, n, _p(x_amax), _p(dy_amax), _p(w_amax), int(bool(accumulate)),
+                                             _p(dx_amax), _p(ws), ws.numel(), dev.index, _stream(dev)),
+            "prh_linear_backward")
+    return dx_amax
+
+
 class LinearFn(torch.autograd.Function):
     """y = x W^T + b on the fp32 MFMA GEMM core (context_proj, src/model.py:147,194)."""
+
+    want_y_amax = False      # set by linear_with_amax() for the one call it makes
+    last_y_amax = None       # max|y| of that call (None: not produced)
 
     @staticmethod
     def forward(ctx, x, w, b, x_amax=None, relu=False, resid=None, dropout_p=0.0, seed=0):
@@ -306,8 +369,6 @@ class LinearFn(torch.autograd.Function):
             x2 = x2.contiguous()
         w = w.contiguous()
         rows = x2.shape[0]
-        y = torch.empty((rows, n), dtype=torch.float32, device=x.device)
-        ws = _ws(x.device, L.lib().prh_linear_forward_workspace_bytes(rows, k, n))
         r2 = None
         if resid is not None:
             _req_gpu_f32(resid, "residual")
@@ -316,18 +377,8 @@ class LinearFn(torch.autograd.Function):
             r2 = resid.reshape(rows, n)
             if not r2.is_contiguous():
                 r2 = r2.contiguous()
-        # operand maxima of the split-fp16 cores: measured once here and kept for the backward
-        # GEMMs, which read x (wgrad) and W^T (dgrad) again
-        w_amax = None
-        if n % 4 == 0 and L.lib().prh_linear_uses_operand_maxima(rows, k, n):
-            if x_amax is None:
-                x_amax = operand_absmax(x2)
-            w_amax = operand_absmax(w)
-        L.check(L.lib().prh_linear_forward_full(_p(x2), k, _p(w), _p(b), _p(r2), n, _p(y), rows, k, n,
-                                                int(bool(relu)), _p(x_amax), _p(w_amax), float(dropout_p),
-                                                int(seed) & 0xFFFFFFFF, _p(ws), ws.numel(),
-                                                x.device.index, _stream(x.device)),
-                "prh_linear_forward")
+        want, LinearFn.want_y_amax = LinearFn.want_y_amax, False
+        y, x_amax, w_amax, LinearFn.last_y_amax = _linear_fwd(x2, w, b, r2, relu, x_amax, dropout_p, seed, want)
         ctx.has_resid = resid is not None
         ctx.w_amax = w_amax
         if relu:
@@ -408,12 +459,7 @@ class LinearFn(torch.autograd.Function):
         dx = torch.empty_like(x2) if need_dx else None
         dw, tw = _grad_buf(ctx.w_sink, w.shape, dev, need_dw)
         db, tb = _grad_buf(ctx.b_sink, (n,), dev, need_db)
-        nb = L.lib().prh_linear_backward_workspace_bytes(rows, k, n)
-        ws = _ws(dev, nb)
-        L.check(L.lib().prh_linear_backward_full(_p(x2), k, _p(w), _p(dy2), _p(dx), _p(dw), _p(db), rows,
-                                                 k, n, _p(ctx.x_amax), _p(dy_amax), _p(ctx.w_amax), _p(ws),
-                                                 ws.numel(), dev.index, _stream(dev)),
-                "prh_linear_backward")
+        _linear_bwd(x2, w, dy2, ctx.x_amax, dy_amax, ctx.w_amax, dx, dw, db)
         dres = None
         if ctx.has_resid and ctx.needs_input_grad[5]:
             dres = dy2.reshape(*ctx.xshape[:-1], n)      # (masked by the ReLU when there is one)
@@ -422,6 +468,24 @@ class LinearFn(torch.autograd.Function):
 
 def linear(x, w, b=None, x_amax=None, relu=False, resid=None, dropout_p=0.0, seed=0):
     return LinearFn.apply(x, w, b, x_amax, relu, resid, dropout_p, seed)
+
+
+def producer_maxima_on(device_ok=True) -> bool:
+    """The producers report their output maxima: the switch is on and the split-fp16 cores (GEMM mode 3) consume them."""
+    return bool(PRODUCER_MAXIMA and device_ok and L.lib().prh_get_gemm_mode() == 3)
+
+
+def linear_with_amax(x, w, b=None, x_amax=None, relu=False, resid=None, dropout_p=0.0, seed=0):
+    """linear() plus max|y| as a 1-element device tensor, a by-product of the GEMM epilogue (None when the
+    switch is off, outside GEMM mode 3 or for a bf16 input): the x_amax of the Linear that reads y next."""
+    LinearFn.last_y_amax = None
+    LinearFn.want_y_amax = producer_maxima_on(x.is_cuda) and x.dtype == torch.float32
+    try:
+        y = LinearFn.apply(x, w, b, x_amax, relu, resid, dropout_p, seed)
+    finally:
+        LinearFn.want_y_amax = False
+    amax, LinearFn.last_y_amax = LinearFn.last_y_amax, None
+    return y, amax
 
 
 class LinearOut16Fn(torch.autograd.Function):
@@ -477,6 +541,9 @@ class PosHiddenFn(torch.autograd.Function):
     (context[:, :, :3]); it is read in place.  Point gradients (the decoder's query positions)
     for hidden <= 256."""
 
+    want_amax = False      # set by pos_hidden_with_amax() for the one call it makes
+    last_amax = None
+
     @staticmethod
     def forward(ctx, xyz, w0, b0):
         ctx.w_sink, ctx.b_sink = _sink_view(w0), _sink_view(b0)
@@ -496,8 +563,13 @@ class PosHiddenFn(torch.autograd.Function):
             ld = 3
         w0 = w0.contiguous()
         h = torch.empty((*xyz.shape[:-1], hdim), dtype=torch.float32, device=xyz.device)
-        L.check(L.lib().prh_pos_hidden_forward(_p(xyz), ld, _p(w0), _p(b0), _p(h), rows, hdim,
-                                               xyz.device.index, _stream(xyz.device)), "prh_pos_hidden_forward")
+        want, PosHiddenFn.want_amax = PosHiddenFn.want_amax, False
+        amax = torch.empty(1, dtype=torch.float32, device=xyz.device) if want else None
+        ws = _ws(xyz.device, L.lib().prh_pos_hidden_forward_workspace_bytes()) if want else None
+        L.check(L.lib().prh_pos_hidden_forward_amax(_p(xyz), ld, _p(w0), _p(b0), _p(h), rows, hdim, _p(amax), _p(ws),
+                                                    ws.numel() if want else 0, xyz.device.index, _stream(xyz.device)),
+                "prh_pos_hidden_forward")
+        PosHiddenFn.last_amax = amax
         ctx.save_for_backward(xyz, h, w0)
         ctx.ld, ctx.has_bias = ld, b0 is not None
         return h
@@ -577,6 +649,18 @@ def linear_small_supported(k, n):
 
 def pos_hidden(xyz, w0, b0=None):
     return PosHiddenFn.apply(xyz, w0, b0)
+
+
+def pos_hidden_with_amax(xyz, w0, b0=None):
+    """pos_hidden() plus max h from the same pass (None when the switch is off or outside GEMM mode 3)."""
+    PosHiddenFn.last_amax = None
+    PosHiddenFn.want_amax = producer_maxima_on(xyz.is_cuda)
+    try:
+        h = PosHiddenFn.apply(xyz, w0, b0)
+    finally:
+        PosHiddenFn.want_amax = False
+    amax, PosHiddenFn.last_amax = PosHiddenFn.last_amax, None
+    return h, amax
 
 
 def pos_hidden_supported(hidden):
@@ -1049,15 +1133,19 @@ def _rows_view(t: torch.Tensor, name: str):
 _DY_AMAX = {}
 
 
-def _hint_put(t, amax):
+def _note_put(table, t, amax):
     key = id(t)
 
     def _drop(ref, key=key):
-        h = _DY_AMAX.get(key)
+        h = table.get(key)
         if h is not None and h[2] is ref:
-            del _DY_AMAX[key]
+            del table[key]
 
-    _DY_AMAX[key] = (amax, tuple(t.shape), weakref.ref(t, _drop))
+    table[key] = (amax, tuple(t.shape), weakref.ref(t, _drop))
+
+
+def _hint_put(t, amax):
+    _note_put(_DY_AMAX, t, amax)
 
 
 def _hint_take(t):
@@ -1285,6 +1373,89 @@ def attention_block(q, k_all, v_all, token, arena, block_index: int, heads: int,
     ((B,N,n*C), contiguous); their gradients are assembled in the arena (see kv_token)."""
     return AttentionFn.apply(q, k_all.detach(), v_all.detach(), heads, dropout_p, seed, token, arena,
                              block_index)
+
+
+class PosKVFn(torch.autograd.Function):
+    """The decoder's context side in one node: mempos = h W2^T + b2 + memory (second Linear of pos_emb with the
+    residual on its epilogue), k_all = mempos Wk^T + bk, v_all = memory Wv^T + bv (src/model.py:64-75,123-126 for
+    all six layers).  Every operand one of these GEMMs reads was written by a kernel that reports its largest
+    magnitude (h: pos_hidden, memory: context_proj, mempos and the two dgrads: GEMM epilogues), so no read pass
+    measures them; and the two gradients that meet at `memory` are summed where the second one is produced
+    (dx_accumulate), not by an add over (B, N, 256).  The GEMM, wgrad and bias-gradient launches are those of
+    three LinearFn nodes, with the same operands and scales: the results are bit-identical."""
+
+    @staticmethod
+    def forward(ctx, h, memory, w2, b2, wk, bk, wv, bv, h_amax, mem_amax):
+        for t, nm in ((h, "hidden"), (memory, "memory"), (w2, "weight"), (wk, "weight"), (wv, "weight")):
+            _req_gpu_f32(t, nm)
+        d, k = w2.shape
+        if h.shape[-1] != k or memory.shape[-1] != d or wk.shape[1] != d or wv.shape[1] != d or \
+                tuple(memory.shape[:-1]) != tuple(h.shape[:-1]) or (k | d | wk.shape[0] | wv.shape[0]) % 4:
+            raise RuntimeError(f"pos_kv_project: shapes {tuple(h.shape)}, {tuple(memory.shape)}, {tuple(w2.shape)}, "
+                               f"{tuple(wk.shape)}, {tuple(wv.shape)} do not fit (widths multiples of 4)")
+        ctx.sinks = [_sink_view(t) for t in (w2, b2, wk, bk, wv, bv)]
+        h2 = h.reshape(-1, k)
+        m2 = memory.reshape(-1, d)
+        h2 = h2 if h2.is_contiguous() else h2.contiguous()
+        m2 = m2 if m2.is_contiguous() else m2.contiguous()
+        w2, wk, wv = w2.contiguous(), wk.contiguous(), wv.contiguous()
+        mempos, h_amax, w2_amax, mp_amax = _linear_fwd(h2, w2, b2, m2, False, h_amax, 0.0, 0, True)
+        k_all, mp_amax, wk_amax, _ = _linear_fwd(mempos, wk, bk, None, False, mp_amax, 0.0, 0)
+        v_all, mem_amax, wv_amax, _ = _linear_fwd(m2, wv, bv, None, False, mem_amax, 0.0, 0)
+        ctx.save_for_backward(h2, m2, mempos, w2, wk, wv)
+        ctx.amax = (h_amax, mp_amax, mem_amax, w2_amax, wk_amax, wv_amax)
+        ctx.has_bias = (b2 is not None, bk is not None, bv is not None)
+        ctx.hshape, ctx.mshape = h.shape, memory.shape
+        lead = tuple(memory.shape[:-1])
+        return k_all.reshape(*lead, wk.shape[0]), v_all.reshape(*lead, wv.shape[0])
+
+    @staticmethod
+    def backward(ctx, dk, dv):
+        h2, m2, mempos, w2, wk, wv = ctx.saved_tensors
+        h_amax, mp_amax, mem_amax, w2_amax, wk_amax, wv_amax = ctx.amax
+        rows, dev = h2.shape[0], h2.device
+        d, k = w2.shape
+
+        def rows_of(g, n):
+            g2 = g.reshape(rows, n)
+            hint = _hint_take(g)
+            amax = hint if (hint is not None and g2.data_ptr() == g.data_ptr()) else None
+            if g2.dtype != torch.float32:
+                g2, amax = g2.float(), None
+            return (g2 if g2.is_contiguous() else g2.contiguous()), amax
+
+        dk2, dk_amax = rows_of(dk, wk.shape[0])
+        dv2, dv_amax = rows_of(dv, wv.shape[0])
+        ng = ctx.needs_input_grad
+        need_dh, need_dmem = ng[0], ng[1]
+        need_a = need_dh or need_dmem or ng[2] or (ctx.has_bias[0] and ng[3])
+        bufs = [_grad_buf(ctx.sinks[i], shp, dev, ng[2 + i] and (i % 2 == 0 or ctx.has_bias[i // 2]))
+                for i, shp in enumerate((w2.shape, (d,), wk.shape, (wk.shape[0],), wv.shape, (wv.shape[0],)))]
+        # 1. K projection: d_mempos into A, with its maximum out of the dgrad epilogue
+        A = torch.empty((rows, d), dtype=torch.float32, device=dev) if need_a else None
+        a_amax = _linear_bwd(mempos, wk, dk2, mp_amax, dk_amax, wk_amax, A, bufs[2][0], bufs[3][0], want_amax=True)
+        # 2. second Linear of pos_emb on dy = A: dW2, db2, dh (its residual's gradient is A itself)
+        dh = torch.empty_like(h2) if need_dh else None
+        if need_dh or bufs[0][0] is not None or bufs[1][0] is not None:
+            _linear_bwd(h2, w2, A, h_amax, a_amax, w2_amax, dh, bufs[0][0], bufs[1][0])
+        # 3. V projection: A += dv Wv, d_memory complete, with the maximum of the sum
+        if need_dmem:
+            a_amax = _linear_bwd(m2, wv, dv2, mem_amax, dv_amax, wv_amax, A, bufs[4][0], bufs[5][0],
+                                 accumulate=True, want_amax=True)
+        elif bufs[4][0] is not None or bufs[5][0] is not None:
+            _linear_bwd(m2, wv, dv2, mem_amax, dv_amax, wv_amax, None, bufs[4][0], bufs[5][0])
+        d_mem = None
+        if need_dmem:
+            d_mem = A.reshape(ctx.mshape)
+            if a_amax is not None:
+                _hint_put(d_mem, a_amax)       # taken by the backward of the Linear that produced `memory`
+        grads = [_grad_ret(*bt) for bt in bufs]
+        return (dh.reshape(ctx.hshape) if need_dh else None, d_mem, *grads, None, None)
+
+
+def pos_kv_project(h, memory, w2, b2, wk, bk, wv, bv, h_amax=None, mem_amax=None):
+    """(k_all, v_all) = ((h W2^T + b2 + memory) Wk^T + bk, memory Wv^T + bv): see PosKVFn."""
+    return PosKVFn.apply(h, memory, w2, b2, wk, bk, wv, bv, h_amax, mem_amax)
 
 
 def cast_perm_bf16(x):
