@@ -4,7 +4,7 @@ frames into lanes and fused into one polyline per lane in the drive frame
 (pointnet_refine_amd/link.py).
 
     python examples/refine_predictions.py DRIVE_DIR RESULTS_JSON --checkpoint CKPT --out MAP.json
-                                          [--gt GT_JSON] [--png DIR] [--batched]
+                                          [--gt GT_JSON] [--png DIR] [--batched] [--device-sync]
                                           [--support [--intensity-floor F]]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; RESULTS_JSON is the detector's output
@@ -17,6 +17,8 @@ SUPPORT line with the share of the map's 0.5 m stations that have lidar points u
 intensity-weighted lateral offset of those points (--intensity-floor F is subtracted from the
 intensity first) and the markings counted by type; every cluster's figures and its marking (solid /
 dashed / none) go into MAP.json's attributes.
+--device-sync runs the linking's edges, clusters and arc synchronisation on the GPU as well
+(link.link_sync): the same map, without copying the candidate pairs' statistics to the host.
 --png DIR draws the fused map over a BEV intensity map of the merged cloud (bev.py).
 
 Without --checkpoint the model carries deterministic procedural weights (the run then exercises the
@@ -76,6 +78,7 @@ def main():
     ap.add_argument("--gate", type=float, default=1.0)
     ap.add_argument("--min-pieces", type=int, default=2)
     ap.add_argument("--batched", action="store_true", help="contexts of all frames in one ragged GPU pass")
+    ap.add_argument("--device-sync", action="store_true", help="piece linking steps 5-6 on the GPU (the same map)")
     ap.add_argument("--support", action="store_true", help="score the map against the cloud (no GT needed)")
     ap.add_argument("--intensity-floor", type=float, default=0.0)
     args = ap.parse_args()
@@ -83,7 +86,8 @@ def main():
     from pointnet_refine_amd import drive, fuse, link
     res = link.refine_predictions(load_model(args.checkpoint), args.drive_dir, args.results_json, seed=args.seed,
                                   step=args.step, gate=args.gate, min_pieces=args.min_pieces, batched=args.batched,
-                                  support=args.support, intensity_floor=args.intensity_floor)
+                                  support=args.support, intensity_floor=args.intensity_floor,
+                                  device_sync=args.device_sync)
     rep = res["report"]
     print(f"{rep['slices']} frames, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['candidates']} candidate pairs, {rep['edges']} edges, {rep['clusters']} clusters, "

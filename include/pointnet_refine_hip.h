@@ -839,10 +839,10 @@ int prh_fuse_gather(const double* world, const double* s, long long n_pieces, in
  *    sum_other, the coordinate along j, is sum_b of i -> j plus sum_a of j -> i.  Every sum starts
  *    at 0 and runs over i -> j in ascending k, then j -> i in ascending k, so the result is bitwise
  *    reproducible and independent of the launch shape.
- * 5. Edges (host).  A candidate is an edge iff n_in >= min_in and out_ratio * n_out <= n_in, in
+ * 5. Edges (host, or prh_link_edges).  A candidate is an edge iff n_in >= min_in and out_ratio * n_out <= n_in, in
  *    integers.  rho = +1 if sum_dot >= 0, else -1; delta = (sum_self - rho * sum_other) / n_in: the
  *    arc coordinate along i of a point is delta + rho times its coordinate along j.
- * 6. Clusters and arc synchronisation (host).  Clusters are the connected components of the edge
+ * 6. Clusters and arc synchronisation (host, or prh_link_label_round and prh_link_tree_level).  Clusters are the connected components of the edge
  *    graph, numbered by ascending smallest member.  That member is the root: level 0, sigma = +1,
  *    o = 0.  A piece at level n + 1 takes as parent, among its neighbours at level n, the one with
  *    the largest n_in; ties go to the smallest index.  For child b, parent a and their edge (i, j):
@@ -883,6 +883,64 @@ int prh_link_pairs_write(const double* world, long long n_pieces, int points_per
 int prh_link_stats(const double* world, const double* cum, long long n_pieces, int points_per_piece,
                    const long long* pair_offsets, const int* pair_j, long long n_pairs, double gate, int* pair_count,
                    double* pair_sum, int device, void* stream);
+
+/* Steps 5-6 and cum on the device (csrc/prh_link_sync.hpp).  The rule above is unchanged; these give
+ * the bits of its host statement (link.piece_cums, link.edges_of, link.sync_pieces), so the
+ * candidates' statistics need not leave the device.  No float atomic, no sort, and no atomic whose
+ * arrival order can show in a result.  At most 2^24 pieces everywhere.
+ * prh_link_cum: world [n_pieces*M,3] fp64 -> cum [n_pieces*M] fp64, one thread per piece: cum[0] = 0,
+ * cum[k+1] = cum[k] + sqrt((e0 * e0 + e1 * e1) + e2 * e2) with e = A[k+1] - A[k], sequentially, no
+ * contraction.  Subtraction, multiplication, addition and sqrt are correctly rounded on both sides,
+ * so the bits are those of the host's cum.
+ * prh_link_edges: step 5 for every candidate, one thread each.  pair_count [n_pairs,2] int32 and
+ * pair_sum [n_pairs,4] fp64 are prh_link_stats' outputs.  Out: pair_i [n_pairs] int32, the i with
+ * pair_offsets[i] <= p < pair_offsets[i+1]; edge [n_pairs] uint8 = n_in >= min_in && out_ratio *
+ * n_out <= n_in in 64-bit integers (counts of -1, a bad pair_j, are no edge); rho [n_pairs] int8 = +1
+ * if sum_dot >= 0.0 (so for -0.0), else -1 (so for NaN); delta [n_pairs] fp64 = (sum_self - rho *
+ * sum_other) / (double)n_in where n_in > 0, else 0: rho * sum_other is exact, the subtraction and the
+ * division round once each, as on the host.  edge_scan [2 * prh_link_edges_blocks(n_pairs) + 1]
+ * int64 is scratch that prh_link_edges_compact reads; edge_scan[prh_link_edges_blocks(n_pairs)] is
+ * the number of edges, which the caller reads to size the next call's buffers.
+ * prh_link_edges_compact: the edges in candidate order (ballot / popcount behind the scanned block
+ * counts: the order is the candidates', whatever the launch does).  edge_ij [n_edges,2] int32 = i j,
+ * edge_w [n_edges,2] int32 = n_in rho, edge_delta [n_edges] fp64.  The later calls read only these.
+ * prh_link_label_round: one round of the components.  label [n_pieces] int32 starts as 0 .. n_pieces
+ * - 1, filled by the caller.  The first kernel does, per edge, atomicMin(label[i], label[j]) and the
+ * other way round, and sets *changed (a device int32, zeroed by the call) when an atomic lowered a
+ * label; the second chases every label to a label that is its own.  The caller repeats the call until
+ * it reads *changed == 0.  Then label[p] is the smallest member of p's component, bitwise the same in
+ * every run: every stored label is a member of the component and labels only fall; a round that
+ * lowered nothing changed no word of label, so its plain loads next to the atomics all read the value
+ * the launch before left, label is equal across every edge and its own label everywhere, and the
+ * smallest member m, whose label is a member <= m, holds m.  The number of rounds may differ from run
+ * to run; the fixed point cannot.  The cluster number is the rank of label[p] among the p with
+ * label[p] == p.
+ * prh_link_tree_init / prh_link_tree_level: the spanning trees, a level per call.  init sets level
+ * [n_pieces] int32 to 0 at the roots (label[p] == p) and -1 elsewhere, parent int32 to -1, sign int32
+ * to +1, offset fp64 to 0 and key uint64 to 0.  level(n) runs two kernels over the edges: per
+ * directed edge a -> b with level[a] == n and b unplaced, atomicMax(key[b], (n_in << 32) |
+ * (0xFFFFFFFF - a)) - the largest n_in, ties to the smallest a, and a maximum does not depend on
+ * the order it is taken in (n_in <= 128 and a < 2^24, so the key fits; 0 means none); then the one
+ * directed edge whose key won (a pair occurs once among the candidates) writes level[b] = n + 1,
+ * parent[b] = a, sign[b] = rho * sign[a] and offset[b] = offset[a] + sign[a] * delta if a is the
+ * edge's i, else offset[a] - sign[b] * delta: sign * delta is exact, so one rounding per offset, as
+ * on the host.  *placed (device int32, zeroed by the call) is set when a piece was placed; the
+ * caller calls n = 0, 1, .. until it reads 0, after at most n_pieces levels. */
+int prh_link_cum(const double* world, long long n_pieces, int points_per_piece, double* cum, int device, void* stream);
+long long prh_link_edges_blocks(long long n_pairs);
+int prh_link_edges(const long long* pair_offsets, long long n_pieces, const int* pair_count, const double* pair_sum,
+                   long long n_pairs, long long min_in, long long out_ratio, int* pair_i, unsigned char* edge,
+                   signed char* rho, double* delta, long long* edge_scan, int device, void* stream);
+int prh_link_edges_compact(const int* pair_i, const int* pair_j, const int* pair_count, const unsigned char* edge,
+                           const signed char* rho, const double* delta, long long n_pairs, const long long* edge_scan,
+                           long long n_edges, int* edge_ij, int* edge_w, double* edge_delta, int device, void* stream);
+int prh_link_label_round(const int* edge_ij, long long n_edges, long long n_pieces, int* label, int* changed, int device,
+                         void* stream);
+int prh_link_tree_init(const int* label, long long n_pieces, int* level, int* parent, int* sign, double* offset,
+                       unsigned long long* key, int device, void* stream);
+int prh_link_tree_level(const int* edge_ij, const int* edge_w, const double* edge_delta, long long n_edges,
+                        long long n_pieces, int n, int* level, int* parent, int* sign, double* offset,
+                        unsigned long long* key, int* placed, int device, void* stream);
 
 /* Cloud support - the rule.
  * What the merged cloud holds in the tube around every station of every map polyline: how many

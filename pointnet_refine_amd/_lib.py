@@ -95,6 +95,8 @@ EXPORTS = [
     "prh_fuse_gather_workspace_bytes", "prh_fuse_gather",
     "prh_link_tile", "prh_link_pairs_per_block", "prh_link_pairs_workspace_bytes", "prh_link_pairs_count",
     "prh_link_pairs_write", "prh_link_stats",
+    "prh_link_cum", "prh_link_edges_blocks", "prh_link_edges", "prh_link_edges_compact", "prh_link_label_round",
+    "prh_link_tree_init", "prh_link_tree_level",
     "prh_support_max_cells", "prh_support_accumulate",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
@@ -346,6 +348,20 @@ def _bind(lib):
     lib.prh_link_pairs_write.argtypes = [vp, ll, i, vp, dbl, vp, vp, vp, sz, i, vp]
     lib.prh_link_stats.restype = i
     lib.prh_link_stats.argtypes = [vp, vp, ll, i, vp, vp, ll, dbl, vp, vp, i, vp]
+    lib.prh_link_cum.restype = i
+    lib.prh_link_cum.argtypes = [vp, ll, i, vp, i, vp]
+    lib.prh_link_edges_blocks.restype = ll
+    lib.prh_link_edges_blocks.argtypes = [ll]
+    lib.prh_link_edges.restype = i
+    lib.prh_link_edges.argtypes = [vp, ll, vp, vp, ll, ll, ll, vp, vp, vp, vp, vp, i, vp]
+    lib.prh_link_edges_compact.restype = i
+    lib.prh_link_edges_compact.argtypes = [vp, vp, vp, vp, vp, vp, ll, vp, ll, vp, vp, vp, i, vp]
+    lib.prh_link_label_round.restype = i
+    lib.prh_link_label_round.argtypes = [vp, ll, ll, vp, vp, i, vp]
+    lib.prh_link_tree_init.restype = i
+    lib.prh_link_tree_init.argtypes = [vp, ll, vp, vp, vp, vp, vp, i, vp]
+    lib.prh_link_tree_level.restype = i
+    lib.prh_link_tree_level.argtypes = [vp, vp, vp, ll, ll, i, vp, vp, vp, vp, vp, vp, i, vp]
     lib.prh_support_max_cells.restype = i
     lib.prh_support_max_cells.argtypes = []
     lib.prh_support_accumulate.restype = i

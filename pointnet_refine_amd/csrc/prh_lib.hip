@@ -31,6 +31,7 @@
 #include "prh_view.hpp"
 #include "prh_fuse.hpp"
 #include "prh_link.hpp"
+#include "prh_link_sync.hpp"
 #include "prh_support.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
@@ -3426,6 +3427,110 @@ int prh_link_stats(const double* world, const double* cum, long long n_pieces, i
   hipLaunchKernelGGL(link_stats_kernel, dim3((unsigned)((n_pairs + LINK_PAIRS - 1) / LINK_PAIRS)), dim3(LINK_THREADS), 0,
                      (hipStream_t)stream, world, cum, (int)n_pieces, M, pair_offsets, pair_j, n_pairs, gate, pair_count,
                      pair_sum);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// steps 5-6 and cum on the device (prh_link_sync.hpp)
+static inline bool link_size_bad(long long n_pieces) { return n_pieces < 0 || n_pieces > (1ll << 24); }
+static inline unsigned sync_grid(long long n) { return (unsigned)((n + SYNC_THREADS - 1) / SYNC_THREADS); }
+int prh_link_cum(const double* world, long long n_pieces, int points_per_piece, double* cum, int device, void* stream) {
+  if (link_size_bad(n_pieces) || points_per_piece < 2 || points_per_piece > FUSE_MAX_POINTS)
+    return fail(PRH_ERR_ARG, "link_cum: bad argument (at most 2^24 pieces of 2..%d points)", FUSE_MAX_POINTS);
+  if (n_pieces == 0) return PRH_OK;
+  if (!world || !cum) return fail(PRH_ERR_ARG, "link_cum: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(link_cum_kernel, dim3(sync_grid(n_pieces)), dim3(SYNC_THREADS), 0, (hipStream_t)stream, world,
+                     (int)n_pieces, points_per_piece, cum);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+long long prh_link_edges_blocks(long long n_pairs) {
+  return n_pairs < 0 ? 0 : (n_pairs + SYNC_THREADS - 1) / SYNC_THREADS;
+}
+// edge_scan: [0 .. blocks] the exclusive scan of the blocks' edge counts, [blocks + 1 .. 2 blocks] the counts
+int prh_link_edges(const long long* pair_offsets, long long n_pieces, const int* pair_count, const double* pair_sum,
+                   long long n_pairs, long long min_in, long long out_ratio, int* pair_i, unsigned char* edge,
+                   signed char* rho, double* delta, long long* edge_scan, int device, void* stream) {
+  if (link_size_bad(n_pieces) || n_pairs < 0 || min_in < 1 || out_ratio < 0 ||
+      n_pairs >= (long long)SYNC_THREADS * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "link_edges: bad argument (at most 2^24 pieces, min_in >= 1, out_ratio >= 0)");
+  if (!edge_scan) return fail(PRH_ERR_ARG, "link_edges: null pointer");
+  if (n_pairs > 0 && (n_pieces == 0 || !pair_offsets || !pair_count || !pair_sum || !pair_i || !edge || !rho || !delta))
+    return fail(PRH_ERR_ARG, "link_edges: null pointer, or pairs without pieces");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  const long long blocks = prh_link_edges_blocks(n_pairs);
+  long long* block_count = edge_scan + blocks + 1;
+  if (blocks > 0) {
+    hipLaunchKernelGGL(link_edges_kernel, dim3((unsigned)blocks), dim3(SYNC_THREADS), 0, st, pair_offsets, (int)n_pieces,
+                       pair_count, pair_sum, n_pairs, min_in, out_ratio, pair_i, edge, rho, delta, block_count);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(link_scan_kernel, dim3(1), dim3(LINK_SCAN_THREADS), 0, st, (const long long*)block_count,
+                     (int)blocks, edge_scan);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_link_edges_compact(const int* pair_i, const int* pair_j, const int* pair_count, const unsigned char* edge,
+                           const signed char* rho, const double* delta, long long n_pairs, const long long* edge_scan,
+                           long long n_edges, int* edge_ij, int* edge_w, double* edge_delta, int device, void* stream) {
+  if (n_pairs < 0 || n_edges < 0 || n_edges > n_pairs || n_pairs >= (long long)SYNC_THREADS * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "link_edges_compact: bad argument (0 <= n_edges <= n_pairs)");
+  if (n_edges == 0) return PRH_OK;
+  if (!pair_i || !pair_j || !pair_count || !edge || !rho || !delta || !edge_scan || !edge_ij || !edge_w || !edge_delta)
+    return fail(PRH_ERR_ARG, "link_edges_compact: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(link_compact_kernel, dim3((unsigned)prh_link_edges_blocks(n_pairs)), dim3(SYNC_THREADS), 0,
+                     (hipStream_t)stream, pair_i, pair_j, pair_count, edge, rho, delta, n_pairs, edge_scan, n_edges, edge_ij,
+                     edge_w, edge_delta);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_link_label_round(const int* edge_ij, long long n_edges, long long n_pieces, int* label, int* changed, int device,
+                         void* stream) {
+  if (link_size_bad(n_pieces) || n_edges < 0 || n_edges >= (long long)SYNC_THREADS * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "link_label_round: bad argument (at most 2^24 pieces)");
+  if (!changed || (n_pieces > 0 && !label) || (n_edges > 0 && !edge_ij))
+    return fail(PRH_ERR_ARG, "link_label_round: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(changed, 0, sizeof(int), st));
+  if (n_edges == 0 || n_pieces == 0) return PRH_OK;
+  hipLaunchKernelGGL(link_hook_kernel, dim3(sync_grid(n_edges)), dim3(SYNC_THREADS), 0, st, edge_ij, n_edges, (int)n_pieces,
+                     label, changed);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(link_jump_kernel, dim3(sync_grid(n_pieces)), dim3(SYNC_THREADS), 0, st, (int)n_pieces, label);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_link_tree_init(const int* label, long long n_pieces, int* level, int* parent, int* sign, double* offset,
+                       unsigned long long* key, int device, void* stream) {
+  if (link_size_bad(n_pieces)) return fail(PRH_ERR_ARG, "link_tree_init: at most 2^24 pieces");
+  if (n_pieces == 0) return PRH_OK;
+  if (!label || !level || !parent || !sign || !offset || !key) return fail(PRH_ERR_ARG, "link_tree_init: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(link_tree_init_kernel, dim3(sync_grid(n_pieces)), dim3(SYNC_THREADS), 0, (hipStream_t)stream, label,
+                     (int)n_pieces, level, parent, sign, offset, key);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_link_tree_level(const int* edge_ij, const int* edge_w, const double* edge_delta, long long n_edges,
+                        long long n_pieces, int n, int* level, int* parent, int* sign, double* offset,
+                        unsigned long long* key, int* placed, int device, void* stream) {
+  if (link_size_bad(n_pieces) || n_edges < 0 || n < 0 || n_edges >= (long long)SYNC_THREADS * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "link_tree_level: bad argument (at most 2^24 pieces, level >= 0)");
+  if (!placed || (n_edges > 0 && (!edge_ij || !edge_w || !edge_delta || !level || !parent || !sign || !offset || !key)))
+    return fail(PRH_ERR_ARG, "link_tree_level: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(placed, 0, sizeof(int), st));
+  if (n_edges == 0 || n_pieces == 0) return PRH_OK;
+  hipLaunchKernelGGL(link_propose_kernel, dim3(sync_grid(n_edges)), dim3(SYNC_THREADS), 0, st, edge_ij, edge_w, n_edges,
+                     (int)n_pieces, n, (const int*)level, key);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(link_place_kernel, dim3(sync_grid(n_edges)), dim3(SYNC_THREADS), 0, st, edge_ij, edge_w, edge_delta,
+                     n_edges, (int)n_pieces, n, (const unsigned long long*)key, level, parent, sign, offset, placed);
   LAUNCH_CHECK();
   return PRH_OK;
 }

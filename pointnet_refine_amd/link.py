@@ -8,6 +8,9 @@ per cluster from the pieces themselves and hands them to the standard fusion.
   link_pieces         HIP: candidate pairs from boxes (steps 1-2), two-way projection statistics of
                       every candidate (steps 3-4); host: which candidates are edges (step 5)
   sync_pieces         host: clusters, a spanning tree per cluster, sign and arc offset per piece (step 6)
+  link_sync           HIP: steps 1-6 and cum on the device (csrc/prh_link_sync.hpp), the bits of
+                      piece_cums, link_pieces and sync_pieces; fuse_unmatched(device_sync=True) and
+                      refine_predictions(device_sync=True) go through it (default off)
   fuse_unmatched      steps 1-8 from ego-frame pieces: pieces_to_world, link_pieces, sync_pieces,
                       prh_fuse_gather for the draft carriers, fuse_pieces for the map
   refine_predictions  a detector run to a map: load_results, slice_cloud, io.scene_offsets per frame,
@@ -16,9 +19,10 @@ per cluster from the pieces themselves and hands them to the standard fusion.
     res = refine_predictions(model, "DRIVE_annotation_raw_data", "results.json")
     fuse.write_map_json("map.json", res["fused"])
 
-Candidates come from an all-pairs box test, O(P^2): right for a drive (2.9e8 tests at 24,000 pieces);
-a spatial grid for maps beyond about 1e5 pieces is not built.  The GPU functions have no CPU
-fallback: without a GPU they raise RuntimeError.
+Candidates come from an all-pairs box test, O(P^2): measured at 2.0 ms for 24,000 pieces (2.9e8 tests)
+and 11.5 ms for 100,008 pieces (5.0e9 tests) on one MI355X, next to 5.2 ms of prh_link_stats at 24,000
+(profiles/r16_link_sync_bench.txt), so a spatial grid is not built and is not needed at 1e5 pieces.
+The GPU functions have no CPU fallback: without a GPU they raise RuntimeError.
 """
 import os
 
@@ -149,8 +153,10 @@ def arc_positions(cum, sync):
 
 
 # ------------------------------------------------------------------ GPU side
-def _link(dev, world_t, frame, cum, gate, min_in, out_ratio):
-    """Steps 1-5 on a CUDA (P,M,3) float64 tensor of shifted drive-frame points."""
+def _link_stats(dev, world_t, frame, cum_t, gate):
+    """Steps 1-4 on a CUDA (P,M,3) float64 tensor of shifted drive-frame points; cum_t (P,M) on the
+    device, or a callable that gives it (asked only when there are candidates).  Returns (offsets
+    (P+1,) numpy, offsets, pair_j, count, sums on the device)."""
     n_p, m = world_t.shape[:2]
     lib = L.lib()
     fr = torch.from_numpy(frame.astype(np.int32)).to(dev)
@@ -167,15 +173,165 @@ def _link(dev, world_t, frame, cum, gate, min_in, out_ratio):
     if n_pairs:
         L.check(lib.prh_link_pairs_write(G.ptr(world_t), n_p, m, G.ptr(fr), float(gate), G.ptr(offsets), G.ptr(pair_j),
                                          G.ptr(ws), nb, dev.index, G.stream(dev)), "prh_link_pairs_write")
-        cum_t = torch.from_numpy(np.ascontiguousarray(cum)).to(dev)
+        if callable(cum_t):
+            cum_t = cum_t()
         L.check(lib.prh_link_stats(G.ptr(world_t), G.ptr(cum_t), n_p, m, G.ptr(offsets), G.ptr(pair_j), n_pairs,
                                    float(gate), G.ptr(count), G.ptr(sums), dev.index, G.stream(dev)), "prh_link_stats")
+    return off, offsets, pair_j, count, sums
+
+
+def _link(dev, world_t, frame, cum, gate, min_in, out_ratio):
+    """Steps 1-5 on a CUDA (P,M,3) float64 tensor of shifted drive-frame points."""
+    n_p = world_t.shape[0]
+    off, _, pair_j, count, sums = _link_stats(dev, world_t, frame,
+                                              lambda: torch.from_numpy(np.ascontiguousarray(cum)).to(dev), gate)
     count, sums = count.cpu().numpy(), sums.cpu().numpy()
     pairs = np.stack([np.repeat(np.arange(n_p, dtype=np.int64), np.diff(off)), pair_j.cpu().numpy().astype(np.int64)], 1)
     edge, rho, delta = edges_of(count[:, 0], count[:, 1], sums[:, 1], sums[:, 2], sums[:, 3], min_in, out_ratio)
     return {"pairs": pairs, "n_in": count[:, 0].copy(), "n_out": count[:, 1].copy(), "sum_d": sums[:, 0].copy(),
             "sum_self": sums[:, 1].copy(), "sum_other": sums[:, 2].copy(), "sum_dot": sums[:, 3].copy(), "edge": edge,
             "rho": rho, "delta": delta}
+
+
+# ------------------------------------------------------------------ steps 5-6 on the device
+KEY_LOW = 0xFFFFFFFF
+
+
+def parent_key(n_in, a):
+    """The 64-bit key a neighbour a with n_in points in offers a piece it could be the parent of:
+    (n_in << 32) | (2^32 - 1 - a).  The largest key is the largest n_in, ties to the smallest a; 0
+    means no offer.  0 <= n_in < 2^31, 0 <= a < 2^32."""
+    n_in, a = int(n_in), int(a)
+    if not (0 <= n_in < 1 << 31 and 0 <= a <= KEY_LOW):
+        raise ValueError("parent_key: 0 <= n_in < 2^31 and 0 <= a < 2^32")
+    return (n_in << 32) | (KEY_LOW - a)
+
+
+def parent_of_key(key):
+    """parent_key's inverse: (n_in, a)."""
+    key = int(key)
+    return key >> 32, KEY_LOW - (key & KEY_LOW)
+
+
+def device_cums(dev, world_t):
+    """(P,M) float64 on the device: piece_cums' bits from prh_link_cum."""
+    n_p, m = world_t.shape[:2]
+    cum_t = torch.zeros((n_p, m), dtype=torch.float64, device=dev)
+    L.check(L.lib().prh_link_cum(G.ptr(world_t), n_p, m, G.ptr(cum_t), dev.index, G.stream(dev)), "prh_link_cum")
+    return cum_t
+
+
+def device_edges(dev, n_p, offsets, pair_j, count, sums, min_in, out_ratio):
+    """Step 5 on the device.  Returns ({'pair_i' int32, 'edge' uint8, 'rho' int8, 'delta' float64}
+    per candidate, {'ij' (E,2) int32, 'w' (E,2) int32 = n_in rho, 'delta' (E,) float64} the edges in
+    candidate order), all CUDA tensors; one 8-byte read sizes the second."""
+    lib = L.lib()
+    n_pairs = int(pair_j.shape[0])
+    per = {"pair_i": torch.zeros((n_pairs,), dtype=torch.int32, device=dev),
+           "edge": torch.zeros((n_pairs,), dtype=torch.uint8, device=dev),
+           "rho": torch.zeros((n_pairs,), dtype=torch.int8, device=dev),
+           "delta": torch.zeros((n_pairs,), dtype=torch.float64, device=dev)}
+    blocks = int(lib.prh_link_edges_blocks(n_pairs))
+    scan = torch.zeros((2 * blocks + 1,), dtype=torch.int64, device=dev)
+    L.check(lib.prh_link_edges(G.ptr(offsets), n_p, G.ptr(count), G.ptr(sums), n_pairs, int(min_in), int(out_ratio),
+                               G.ptr(per["pair_i"]), G.ptr(per["edge"]), G.ptr(per["rho"]), G.ptr(per["delta"]),
+                               G.ptr(scan), dev.index, G.stream(dev)), "prh_link_edges")
+    n_edges = int(scan[blocks].item())
+    edges = {"ij": torch.zeros((n_edges, 2), dtype=torch.int32, device=dev),
+             "w": torch.zeros((n_edges, 2), dtype=torch.int32, device=dev),
+             "delta": torch.zeros((n_edges,), dtype=torch.float64, device=dev)}
+    L.check(lib.prh_link_edges_compact(G.ptr(per["pair_i"]), G.ptr(pair_j), G.ptr(count), G.ptr(per["edge"]),
+                                       G.ptr(per["rho"]), G.ptr(per["delta"]), n_pairs, G.ptr(scan), n_edges,
+                                       G.ptr(edges["ij"]), G.ptr(edges["w"]), G.ptr(edges["delta"]), dev.index,
+                                       G.stream(dev)), "prh_link_edges_compact")
+    return per, edges
+
+
+def device_components(dev, n_p, edges):
+    """Step 6's clusters on the device: (label (P,) int32 CUDA, the component's smallest member;
+    rounds run).  One 4-byte read per round."""
+    lib = L.lib()
+    label = torch.arange(n_p, dtype=torch.int32, device=dev)
+    changed = torch.zeros((1,), dtype=torch.int32, device=dev)
+    n_edges, rounds = int(edges["ij"].shape[0]), 0
+    while n_edges and n_p:
+        L.check(lib.prh_link_label_round(G.ptr(edges["ij"]), n_edges, n_p, G.ptr(label), G.ptr(changed), dev.index,
+                                         G.stream(dev)), "prh_link_label_round")
+        rounds += 1
+        if int(changed.item()) == 0:
+            break
+        if rounds > n_p + 1:
+            raise RuntimeError("link: the component rounds did not settle")
+    return label, rounds
+
+
+def device_tree(dev, n_p, edges, label):
+    """Step 6's spanning trees on the device: ({'level', 'parent', 'sign' int32, 'offset' float64}
+    CUDA, levels run).  One 4-byte read per level."""
+    lib = L.lib()
+    t = {"level": torch.zeros((n_p,), dtype=torch.int32, device=dev),
+         "parent": torch.zeros((n_p,), dtype=torch.int32, device=dev),
+         "sign": torch.zeros((n_p,), dtype=torch.int32, device=dev),
+         "offset": torch.zeros((n_p,), dtype=torch.float64, device=dev)}
+    key = torch.zeros((n_p,), dtype=torch.int64, device=dev)           # the library reads it as uint64
+    placed = torch.zeros((1,), dtype=torch.int32, device=dev)
+    L.check(lib.prh_link_tree_init(G.ptr(label), n_p, G.ptr(t["level"]), G.ptr(t["parent"]), G.ptr(t["sign"]),
+                                   G.ptr(t["offset"]), G.ptr(key), dev.index, G.stream(dev)), "prh_link_tree_init")
+    n_edges, n = int(edges["ij"].shape[0]), 0
+    while n_edges and n < n_p:
+        L.check(lib.prh_link_tree_level(G.ptr(edges["ij"]), G.ptr(edges["w"]), G.ptr(edges["delta"]), n_edges, n_p, n,
+                                        G.ptr(t["level"]), G.ptr(t["parent"]), G.ptr(t["sign"]), G.ptr(t["offset"]),
+                                        G.ptr(key), G.ptr(placed), dev.index, G.stream(dev)), "prh_link_tree_level")
+        if int(placed.item()) == 0:
+            break
+        n += 1
+    return t, n
+
+
+def _link_sync(dev, world_t, frame, gate, min_in, out_ratio, return_links):
+    """Steps 1-6 on a CUDA (P,M,3) float64 tensor of shifted drive-frame points: link_sync's result."""
+    n_p = int(world_t.shape[0])
+    cum_t = device_cums(dev, world_t)
+    off, offsets, pair_j, count, sums = _link_stats(dev, world_t, frame, cum_t, gate)
+    per, edges = device_edges(dev, n_p, offsets, pair_j, count, sums, min_in, out_ratio)
+    label, _ = device_components(dev, n_p, edges)
+    tree, _ = device_tree(dev, n_p, edges, label)
+    root = label == torch.arange(n_p, dtype=torch.int32, device=dev)
+    rank = torch.cumsum(root.to(torch.int64), 0) - 1                   # integers: exact in any order
+    cluster = rank[label.to(torch.int64)] if n_p else rank
+    res = {"cluster": cluster.cpu().numpy(), "level": tree["level"].cpu().numpy().astype(np.int64),
+           "parent": tree["parent"].cpu().numpy().astype(np.int64), "sign": tree["sign"].cpu().numpy().astype(np.int8),
+           "offset": tree["offset"].cpu().numpy(), "cum": cum_t.cpu().numpy(), "candidates": int(pair_j.shape[0]),
+           "edges": int(edges["ij"].shape[0])}
+    if return_links:
+        cnt, sm = count.cpu().numpy(), sums.cpu().numpy()
+        res["links"] = {"pairs": np.stack([per["pair_i"].cpu().numpy().astype(np.int64),
+                                           pair_j.cpu().numpy().astype(np.int64)], 1),
+                        "n_in": cnt[:, 0].copy(), "n_out": cnt[:, 1].copy(), "sum_d": sm[:, 0].copy(),
+                        "sum_self": sm[:, 1].copy(), "sum_other": sm[:, 2].copy(), "sum_dot": sm[:, 3].copy(),
+                        "edge": per["edge"].cpu().numpy().astype(bool), "rho": per["rho"].cpu().numpy(),
+                        "delta": per["delta"].cpu().numpy()}
+    return res
+
+
+def _origin_of(w, origin):
+    if origin is None:
+        return np.floor(w[0, 0] / 1000.0) * 1000.0 if len(w) else np.zeros(3)
+    return np.asarray(origin, dtype=np.float64).reshape(3)
+
+
+def link_sync(world, piece_frame, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATIO, origin=None, return_links=False):
+    """Steps 1-6 on the device: link_pieces' inputs; the candidates' statistics stay on the device.
+    Returns sync_pieces' five arrays ('cluster', 'level', 'parent' int64, 'sign' int8, 'offset'
+    float64, bitwise what sync_pieces(link_pieces(..)) gives) plus 'cum' (P,M) float64 (piece_cums'
+    bits), 'candidates' and 'edges' (two ints); return_links=True adds 'links', link_pieces' dict,
+    copied to the host only then.  Bitwise reproducible: csrc/prh_link_sync.hpp says why."""
+    w = F._check_pieces(world, "link_sync")
+    fr = F._check_index(piece_frame, len(w), np.iinfo(np.int32).max, "piece_frame", "link_sync")
+    _check_params(gate, min_in, out_ratio, "link_sync")
+    dev = G.device("link")
+    shifted = np.ascontiguousarray(w - _origin_of(w, origin))
+    return _link_sync(dev, torch.from_numpy(shifted).to(dev), fr, gate, min_in, out_ratio, return_links)
 
 
 def link_pieces(world, piece_frame, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATIO, origin=None):
@@ -188,11 +344,7 @@ def link_pieces(world, piece_frame, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATI
     fr = F._check_index(piece_frame, len(w), np.iinfo(np.int32).max, "piece_frame", "link_pieces")
     _check_params(gate, min_in, out_ratio, "link_pieces")
     dev = G.device("link")
-    if origin is None:
-        org = np.floor(w[0, 0] / 1000.0) * 1000.0 if len(w) else np.zeros(3)
-    else:
-        org = np.asarray(origin, dtype=np.float64).reshape(3)
-    shifted = np.ascontiguousarray(w - org)
+    shifted = np.ascontiguousarray(w - _origin_of(w, origin))
     return _link(dev, torch.from_numpy(shifted).to(dev), fr, piece_cums(shifted), gate, min_in, out_ratio)
 
 
@@ -226,7 +378,7 @@ def _draft_carriers(dev, world, g, line, n_lines, step):
 
 def fuse_unmatched(pieces, piece_pose, poses_xyzq, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATIO,
                    min_pieces=MIN_PIECES, step=F.STEP, min_count=F.MIN_COUNT, max_gap=F.MAX_GAP, origin=None,
-                   return_nodes=False):
+                   return_nodes=False, device_sync=False, return_links=False):
     """Unlabelled refined pieces fused into one map (steps 1-8 of the rule).
 
     pieces (P,M,3), 2 <= M <= 64, piece p in the ego frame of poses_xyzq[piece_pose[p]]; the frame of
@@ -237,7 +389,13 @@ def fuse_unmatched(pieces, piece_pose, poses_xyzq, gate=GATE, min_in=MIN_IN, out
     in the caller's order) plus 'cluster' (P,) the kept cluster of every piece, -1 for pieces of
     dropped clusters, 'sign' (P,), 'offset' (P,), 'g' (P,M), 'kept' (the kept pieces' indices),
     'carriers' [per kept cluster (k,3)], 'links' (link_pieces' dict) and sync_pieces' 'level',
-    'parent' and, as 'clusters_all', its cluster numbers before any was dropped.  Bitwise reproducible."""
+    'parent' and, as 'clusters_all', its cluster numbers before any was dropped, and 'n_candidates'
+    and 'n_edges' (two ints).  Bitwise reproducible.
+
+    device_sync=True runs steps 1-6 through the device path (link_sync's: cum, edges, clusters and the
+    spanning trees on the GPU, the candidates' statistics never copied to the host); arc_positions
+    stays on the host.  'links' is then in the dict only with return_links=True; every other key and
+    the map are bitwise the default's."""
     pc = F._check_pieces(pieces, "fuse_unmatched")
     poses = F._check_poses(poses_xyzq, "fuse_unmatched")
     n_p, m = pc.shape[:2]
@@ -254,9 +412,13 @@ def fuse_unmatched(pieces, piece_pose, poses_xyzq, gate=GATE, min_in=MIN_IN, out
     else:
         world_t = torch.zeros((0, m, 3), dtype=torch.float64, device=dev)
     world = world_t.cpu().numpy()
-    cum = piece_cums(world)
-    links = _link(dev, world_t, pp, cum, gate, min_in, out_ratio)
-    sync = sync_pieces(n_p, links)
+    if device_sync:
+        sync = _link_sync(dev, world_t, pp, gate, min_in, out_ratio, return_links)
+        cum, links = sync["cum"], sync.get("links")
+    else:
+        cum = piece_cums(world)
+        links = _link(dev, world_t, pp, cum, gate, min_in, out_ratio)
+        sync = sync_pieces(n_p, links)
     g, flip = arc_positions(cum, sync)
     size = np.bincount(sync["cluster"], minlength=0)
     big = np.flatnonzero(size >= int(min_pieces))
@@ -282,7 +444,13 @@ def fuse_unmatched(pieces, piece_pose, poses_xyzq, gate=GATE, min_in=MIN_IN, out
     if not return_nodes:
         return fused
     nodes.update(cluster=cluster, sign=sync["sign"], offset=sync["offset"], g=g, kept=kept, carriers=carriers,
-                 links=links, level=sync["level"], parent=sync["parent"], clusters_all=sync["cluster"])
+                 level=sync["level"], parent=sync["parent"], clusters_all=sync["cluster"])
+    if links is not None:
+        nodes["links"] = links
+    if device_sync:
+        nodes.update(n_candidates=sync["candidates"], n_edges=sync["edges"])
+    else:
+        nodes.update(n_candidates=int(len(links["edge"])), n_edges=int(links["edge"].sum()))
     return fused, nodes
 
 
@@ -291,7 +459,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
                        decay_scale=2.0, seed=0, precision=None, segment_len=None, radius=None, max_pose_gap=None,
                        min_tube_points=F.MIN_TUBE_POINTS, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATIO,
                        min_pieces=MIN_PIECES, step=F.STEP, min_count=F.MIN_COUNT, max_gap=F.MAX_GAP, origin=None,
-                       batched=False, support=False, support_radius=None, intensity_floor=0.0):
+                       batched=False, support=False, support_radius=None, intensity_floor=0.0, device_sync=False,
+                       return_links=False):
     """A detector run refined into one drive-frame map, with no GT.
 
     drive_dir holds pose/*.json and merged.pcd; results_json is the detector's output
@@ -302,6 +471,7 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     whose tube held fewer than min_tube_points cloud points is left out and counted; fuse_unmatched
     links and fuses the rest.  batched=True replaces the per-frame loop by one
     io.scene_offsets_ragged call over all frames (fuse.refine_slices_batched), as in refine_drive.
+    device_sync and return_links go to fuse_unmatched: the same map and report, steps 5-6 on the device.
 
     Returns {'fused' [per kept cluster], 'pieces' (P,M,3) float64 ego frame, 'piece_frame' (P,) the
     row of 'poses' each piece was seen from, 'piece_slice' (the same), 'pose_index' (per used frame
@@ -354,12 +524,12 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     pieces = np.stack(pieces) if len(pieces) else np.zeros((0, m, 3))
     piece_frame = np.asarray(piece_frame, dtype=np.int64)
     fused, nodes = fuse_unmatched(pieces, piece_frame, pq, gate, min_in, out_ratio, min_pieces, step, min_count, max_gap,
-                                  origin, return_nodes=True)
+                                  origin, return_nodes=True, device_sync=device_sync, return_links=return_links)
     all_clusters = nodes["clusters_all"]
     report = {"slices": int(len(with_pose)), "pieces": int(len(pieces)), "pieces_sparse": int(sparse),
               "nodes": int(len(nodes["C"])), "nodes_used": int((nodes["C"] >= min_count).sum()),
-              "fused_polylines": int(sum(len(f) for f in fused)), "candidates": int(len(nodes["links"]["edge"])),
-              "edges": int(nodes["links"]["edge"].sum()),
+              "fused_polylines": int(sum(len(f) for f in fused)), "candidates": int(nodes["n_candidates"]),
+              "edges": int(nodes["n_edges"]),
               "clusters": int(all_clusters.max()) + 1 if len(all_clusters) else 0, "clusters_kept": len(fused),
               "pieces_unlinked": int((nodes["cluster"] < 0).sum())}
     res = {"fused": fused, "pieces": pieces, "piece_frame": piece_frame, "piece_slice": piece_frame.copy(),
