@@ -149,7 +149,8 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
                               size_t workspace_bytes, int device, void* stream);
 /* nn.Linear on a bf16 input (context_proj applied to the bf16 `fused`, src/model.py:147,194):
  * y fp32 [rows,n] = act(x W^T + b); backward: dy fp32 -> dx bf16 [rows,k], dw [n,k], db [n]
- * (any may be NULL).  k, n, ldx multiples of 8. */
+ * (any may be NULL).  k, n, ldx multiples of 8.  A workspace smaller than prh_linear_bf16_workspace_bytes
+ * reports is refused (PRH_ERR_WORKSPACE), by these two and by the out16 / dy16 entries below. */
 size_t prh_linear_bf16_workspace_bytes(int rows, int k, int n, int backward);
 int prh_linear_forward_bf16(const uint16_t* x, long ldx, const float* w, const float* b, float* y, int rows, int k,
                             int n, int relu, void* workspace, size_t workspace_bytes, int device, void* stream);

@@ -1189,6 +1189,11 @@ void lin16_carve(Arena& a, Lin16WS& w, int rows, int k, int n, bool backward) {
   w.cslab = a.f(tn16_colsum_floats(rows, n, k));
   w.dy16 = (u16*)a.f(((size_t)rows * (n > k ? n : k) + 1) / 2);      // dy cast, or (dy16 entry) the x cast
 }
+// what an entry point demands of the caller's workspace: present, and no smaller than what
+// prh_linear_bf16_workspace_bytes reports (the carve plus 256 bytes) - one rule for the size and the check
+inline bool lin16_ws_ok(const Arena& a, const void* workspace, size_t workspace_bytes) {
+  return workspace != nullptr && a.ok && workspace_bytes >= a.off + 256;
+}
 }  // namespace
 
 // =======================================================================================
@@ -2076,7 +2081,8 @@ int prh_linear_forward_bf16(const uint16_t* x, long ldx, const float* w, const f
   HIP_TRY(hipSetDevice(device));
   Arena a(workspace, workspace_bytes); Lin16WS lw;
   lin16_carve(a, lw, rows, k, n, false);
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "linear_forward_bf16: workspace too small (%zu bytes)", workspace_bytes);
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "linear_forward_bf16: workspace too small (%zu bytes)", workspace_bytes);
   NTParams p; memset(&p, 0, sizeof(p));
   p.A = f16p(x); p.lda = ldx; p.W = w; p.ldw = k; p.C = y; p.ldc = n; p.M = rows; p.N = n; p.K = k; p.bias = b;
   p.flags = relu ? F_RELU_OUT : 0; p.wprep = lw.wprep;
@@ -2091,7 +2097,8 @@ int prh_linear_backward_bf16(const uint16_t* x, long ldx, const float* w, const 
   hipStream_t st = (hipStream_t)stream;
   Arena a(workspace, workspace_bytes); Lin16WS lw;
   lin16_carve(a, lw, rows, k, n, true);
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "linear_backward_bf16: workspace too small (%zu bytes)", workspace_bytes);
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "linear_backward_bf16: workspace too small (%zu bytes)", workspace_bytes);
   TRY(cast_b16(dy, n, n, lw.dy16, n, n, (size_t)rows, st));      // one operand for both GEMMs
   if (dx != nullptr) {
     TRY(transpose(w, n, k, lw.wT, st));   // wT [k, n]
@@ -2117,7 +2124,8 @@ int prh_linear_forward_out16(const float* x, long ldx, const float* w, const flo
   HIP_TRY(hipSetDevice(device));
   Arena a(workspace, workspace_bytes); Lin16WS lw;
   lin16_carve(a, lw, rows, k, n, false);
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "linear_forward_out16: workspace too small (%zu bytes)", workspace_bytes);
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "linear_forward_out16: workspace too small (%zu bytes)", workspace_bytes);
   NTParams p; memset(&p, 0, sizeof(p));
   p.A = x; p.lda = ldx; p.W = w; p.ldw = k; p.C = f16p(y); p.ldc = n; p.M = rows; p.N = n; p.K = k; p.bias = b;
   p.wprep = lw.wprep;
@@ -2132,7 +2140,8 @@ int prh_linear_backward_dy16(const float* x, long ldx, const float* w, const uin
   hipStream_t st = (hipStream_t)stream;
   Arena a(workspace, workspace_bytes); Lin16WS lw;
   lin16_carve(a, lw, rows, k, n, true);
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "linear_backward_dy16: workspace too small (%zu bytes)", workspace_bytes);
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "linear_backward_dy16: workspace too small (%zu bytes)", workspace_bytes);
   if (dx != nullptr) {
     TRY(transpose(w, n, k, lw.wT, st));   // wT [k, n]
     NTParams p; memset(&p, 0, sizeof(p));

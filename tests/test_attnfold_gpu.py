@@ -113,3 +113,27 @@ def test_posmem_images_match_the_separate_path(B, N):
     assert got.shape == (B * N, 256)
     assert rel_l2(want, got) < 1e-2          # bf16 hidden layer and weights, fp32 accumulation
     assert maxdiff(got, want) < 0.05 * float(want.abs().max())
+
+
+@pytest.mark.parametrize("rows", [1, 17, 4099])
+@pytest.mark.parametrize("ld", [256, 260])
+def test_cast_perm_bf16_is_the_stated_permutation(rows, ld):
+    """prh_cast_perm_bf16 is the oracle of the test above, so its channel order is stated here on its own: position p
+    of every 16-channel group holds the channel whose index is p with bits 2 and 3 swapped (0..3, 8..11, 4..7,
+    12..15), rounded to bf16 - rebuilt in torch and compared bit for bit, from contiguous and from strided rows."""
+    import ctypes as C
+    from pointnet_refine_amd import _lib
+    g = torch.Generator().manual_seed(rows + ld)
+    src = torch.randn(rows, ld, generator=g).cuda()
+    dst = torch.full((rows + 1, 256), float("nan"), dtype=torch.bfloat16, device="cuda")
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert _lib.lib().prh_cast_perm_bf16(C.c_void_p(src.data_ptr()), ld, C.c_void_p(dst.data_ptr()), rows, 0, st) == 0
+    p = torch.arange(16)
+    chan = (p & 3) | ((p & 4) << 1) | ((p & 8) >> 1)
+    assert chan.tolist() == [0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15]
+    index = (torch.arange(0, 256, 16).view(16, 1) + chan.view(1, 16)).reshape(256).cuda()
+    assert torch.equal(dst[:rows], src[:, :256].to(torch.bfloat16)[:, index])
+    assert bool(torch.isnan(dst[rows]).all())                        # nothing past the last row
+    if ld == 256:
+        from pointnet_refine_amd import ops
+        assert torch.equal(ops.cast_perm_bf16(src), dst[:rows])
