@@ -1089,6 +1089,44 @@ int prh_test_gemm_tn_side(const float* a, const float* b, float* c, float* colsu
                           float* amax_out, void* workspace, size_t workspace_bytes, int device,
                           void* stream);
 
+/* Raw second-stage reductions, exported for the unit tests (tests/test_ordered_reductions_gpu.py).
+ * Each goes through the launcher the library itself calls, so a test runs the library's grid.
+ * Every output is an ordered sum: its additions, their order and their precision are a contract
+ * (DESIGN.md section 4), restated in tests/test_ordered_reductions_cpu.py.
+ *   slabs        out[rows,cols] (ld ldout) = sum_s slab[s][rows*cols]; with cslab,
+ *                cout[ccols] = sum_s cslab[s][ccols] in the same launch.  fp64, s = 0..S-1.
+ *   bn_stage1    partials ws_a / ws_b [r][ld] -> out[32 slices][3][n] doubles:
+ *                forward (count, sum, M2 about the slice mean), backward (sum a, sum b, 0).
+ *   partials     out_a[n] = sum_i ws_a[i][n], out_b likewise (ws_b, out_a, out_b may be NULL).
+ *   ln_param_grad      dgamma[256] = sum_i part_g[i][256], dbeta likewise.
+ *   pos_hidden_final   part[nblk][4*hidden] -> dw0[hidden,3], db0[hidden] (either may be NULL).
+ *   partial_rows_final part[nblk][n_el] -> out0[n0], out1[n_el - n0] (either may be NULL).
+ *   act_amax     amax_out[0] = max over columns of max(relu(mx*scale+shift), relu(mn*scale+shift))
+ *                with mx / mn the column maxima / minima of ws_c / ws_d [r][ld].
+ * prh_test_reduce_depth(kind): how many loads a lane of that kernel keeps in flight. */
+enum {
+  PRH_REDUCE_SLABS = 0, PRH_REDUCE_BN_STAGE1 = 1, PRH_REDUCE_PARTIALS = 2, PRH_REDUCE_LN_PARAM_GRAD = 3,
+  PRH_REDUCE_FINAL = 4, PRH_REDUCE_ACT_AMAX = 5
+};
+int prh_test_reduce_depth(int kind);
+int prh_test_reduce_slabs(const float* slab, int s, int rows, int cols, float* out, long ldout,
+                          const float* cslab, int ccols, float* cout, int device, void* stream);
+int prh_test_reduce_bn_stage1(const float* ws_a, const float* ws_b, int r, long ld, int n,
+                              int tile_rows, int p, int forward, double* out, int device,
+                              void* stream);
+int prh_test_reduce_partials(const float* ws_a, const float* ws_b, int r2, int n, float* out_a,
+                             float* out_b, int device, void* stream);
+int prh_test_reduce_ln_param_grad(const float* part_g, const float* part_b, int nb, float* dgamma,
+                                  float* dbeta, int device, void* stream);
+int prh_test_reduce_pos_hidden_final(const float* part, int nblk, int hidden, float* dw0,
+                                     float* db0, int device, void* stream);
+int prh_test_reduce_partial_rows_final(const float* part, int nblk, int n_el, float* out0, int n0,
+                                       float* out1, int device, void* stream);
+size_t prh_test_reduce_act_amax_workspace_bytes(void);
+int prh_test_reduce_act_amax(const float* ws_c, const float* ws_d, int r, long ld, int n,
+                             const float* scale, const float* shift, float* amax_out,
+                             void* workspace, size_t workspace_bytes, int device, void* stream);
+
 /* Diagnostic: which XCD (XCC_ID) and CU (HW_ID) each workgroup of a `blocks` x 512-thread
  * launch with `lds_bytes` of dynamic LDS lands on; out[2*b] = XCC_ID, out[2*b+1] = HW_ID.
  * The GEMM kernels assume workgroup b runs on XCD b % 8 (xcd_remap); this checks it. */

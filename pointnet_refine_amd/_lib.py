@@ -75,6 +75,9 @@ EXPORTS = [
     "prh_mlp_stack_workspace_bytes", "prh_mlp_stack_forward", "prh_mlp_stack_backward",
     "prh_test_gemm_nt", "prh_test_gemm_tn_workspace_bytes", "prh_test_gemm_tn",
     "prh_test_gemm_tn_side_workspace_bytes", "prh_test_gemm_tn_side", "prh_test_xcc_map",
+    "prh_test_reduce_depth", "prh_test_reduce_slabs", "prh_test_reduce_bn_stage1", "prh_test_reduce_partials",
+    "prh_test_reduce_ln_param_grad", "prh_test_reduce_pos_hidden_final", "prh_test_reduce_partial_rows_final",
+    "prh_test_reduce_act_amax_workspace_bytes", "prh_test_reduce_act_amax",
     "prh_profile_enable", "prh_profile_count", "prh_profile_reset", "prh_profile_read",
     "prh_attn_forward", "prh_attn_backward", "prh_attn_backward_ex",
     "prh_context_workspace_bytes", "prh_context_build",
@@ -435,6 +438,26 @@ def _bind(lib):
     lib.prh_test_gemm_tn_side.argtypes = [vp, vp, vp, vp, i, i, i, vp, lg, vp, lg, vp, vp, vp, lg, i, i, vp, vp, sz, i, vp]
     lib.prh_test_xcc_map.restype = i
     lib.prh_test_xcc_map.argtypes = [i, i, vp, i, vp]
+    if not hasattr(lib, "prh_test_reduce_depth"):
+        return lib      # an older build under PRH_LIB_PATH (A/B runs): it has no raw reduction entries
+    lib.prh_test_reduce_depth.restype = i
+    lib.prh_test_reduce_depth.argtypes = [i]
+    lib.prh_test_reduce_slabs.restype = i
+    lib.prh_test_reduce_slabs.argtypes = [vp, i, i, i, vp, lg, vp, i, vp, i, vp]
+    lib.prh_test_reduce_bn_stage1.restype = i
+    lib.prh_test_reduce_bn_stage1.argtypes = [vp, vp, i, lg, i, i, i, i, vp, i, vp]
+    lib.prh_test_reduce_partials.restype = i
+    lib.prh_test_reduce_partials.argtypes = [vp, vp, i, i, vp, vp, i, vp]
+    lib.prh_test_reduce_ln_param_grad.restype = i
+    lib.prh_test_reduce_ln_param_grad.argtypes = [vp, vp, i, vp, vp, i, vp]
+    lib.prh_test_reduce_pos_hidden_final.restype = i
+    lib.prh_test_reduce_pos_hidden_final.argtypes = [vp, i, i, vp, vp, i, vp]
+    lib.prh_test_reduce_partial_rows_final.restype = i
+    lib.prh_test_reduce_partial_rows_final.argtypes = [vp, i, i, vp, i, vp, i, vp]
+    lib.prh_test_reduce_act_amax_workspace_bytes.restype = sz
+    lib.prh_test_reduce_act_amax_workspace_bytes.argtypes = []
+    lib.prh_test_reduce_act_amax.restype = i
+    lib.prh_test_reduce_act_amax.argtypes = [vp, vp, i, lg, i, vp, vp, vp, vp, sz, i, vp]
     return lib
 
 

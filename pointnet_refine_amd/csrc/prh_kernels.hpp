@@ -9,6 +9,80 @@
 namespace prh {
 
 // ---------------------------------------------------------------------------------------
+// Ordered strided sums for the second-stage reductions.  A loop `acc += p[s * stride]` compiles
+// to load, wait, add: one request in flight per wave, so a launch of a few hundred waves runs at
+// one memory latency per term.  These helpers issue D independent loads first and then add them
+// left to right into the one accumulator, so the additions - their order and their precision -
+// are exactly those of the plain loop and the result is bit-identical.  The last partial batch
+// loads its final term again in the unused slots (always in bounds) and skips their additions.
+// Depths: chosen per kernel so that a CU has about 32 KiB of loads in flight at the grids the
+// training step launches (waves per CU x 256 B x D).
+// ---------------------------------------------------------------------------------------
+constexpr int SLAB_D = 32;       // slab_reduce*: one workgroup (4 waves) per CU at 257 workgroups
+constexpr int BN1_D = 32;        // bn_stage1 forward sum; two-stream passes use BN1_D / 2 per stream
+constexpr int PARTIALS_D = 8;    // partials_reduce: 16 waves per CU, two streams
+constexpr int LN_D = 16;         // ln_param_grad: two streams
+constexpr int FINAL_D = 16;      // pos_hidden_final / partial_rows_final (fp32 chains)
+constexpr int AMAX_D = 16;       // act_amax: two streams
+
+// v[k] = p[k * stride], k < D, of a chain with n >= 1 terms left: slots k >= n repeat term n - 1
+template <int D>
+__device__ __forceinline__ void strided_load(float (&v)[D], const float* __restrict__ p, size_t stride, int n) {
+#pragma unroll
+  for (int k = 0; k < D; ++k) v[k] = p[(size_t)(k < n ? k : n - 1) * stride];
+}
+template <int D>
+__device__ __forceinline__ void strided_load(float (&v)[D], const float* __restrict__ p, size_t stride) {
+#pragma unroll
+  for (int k = 0; k < D; ++k) v[k] = p[(size_t)k * stride];
+}
+
+// acc + p[0] + p[stride] + ... + p[(count - 1) * stride], added in that order
+template <int D, typename Acc>
+__device__ __forceinline__ Acc ordered_sum(const float* __restrict__ p, size_t stride, int count, Acc acc) {
+  float v[D];
+  int s = 0;
+  for (; s + D <= count; s += D) {
+    strided_load<D>(v, p + (size_t)s * stride, stride);
+#pragma unroll
+    for (int k = 0; k < D; ++k) acc += (Acc)v[k];
+  }
+  if (s < count) {
+    strided_load<D>(v, p + (size_t)s * stride, stride, count - s);
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+      if (s + k < count) acc += (Acc)v[k];
+  }
+  return acc;
+}
+// two streams with the same stride and count: both batches are loaded before either is added
+template <int D, typename Acc>
+__device__ __forceinline__ void ordered_sum2(const float* __restrict__ pa, const float* __restrict__ pb, size_t stride,
+                                             int count, Acc& a, Acc& b) {
+  float va[D], vb[D];
+  int s = 0;
+  for (; s + D <= count; s += D) {
+    strided_load<D>(va, pa + (size_t)s * stride, stride);
+    strided_load<D>(vb, pb + (size_t)s * stride, stride);
+#pragma unroll
+    for (int k = 0; k < D; ++k) a += (Acc)va[k];
+#pragma unroll
+    for (int k = 0; k < D; ++k) b += (Acc)vb[k];
+  }
+  if (s < count) {
+    strided_load<D>(va, pa + (size_t)s * stride, stride, count - s);
+    strided_load<D>(vb, pb + (size_t)s * stride, stride, count - s);
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+      if (s + k < count) { a += (Acc)va[k]; b += (Acc)vb[k]; }
+  }
+}
+// terms of the chain i = first, first + step, ... below end
+__device__ __forceinline__ int chain_count(int first, int end, int step) {
+  return end > first ? (end - first + step - 1) / step : 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // BatchNorm statistics, two stages.  The GEMM epilogues leave per-wave-tile partials
 // ws_a/ws_b [R][ld] (R = tens of thousands at B=4096).  Stage 1 compresses them into
 // BN_SLICES slices of doubles with enough workgroups to use the chip
@@ -31,17 +105,19 @@ __global__ __launch_bounds__(256) void bn_stage1_kernel(const float* __restrict_
   const int r0 = sl * per, r1 = (r0 + per < R) ? r0 + per : R;
   const bool ok = col < N;
   double a = 0.0, b = 0.0, n = 0.0;
-  if (ok)
-    for (int i = r0 + g; i < r1; i += 8) {
-      a += (double)ws_a[(size_t)i * ld + col];
-      if (forward) {
-        int ni = P - i * tile_rows;
-        ni = ni > tile_rows ? tile_rows : (ni < 0 ? 0 : ni);
-        n += (double)ni;
-      } else {
-        b += (double)ws_b[(size_t)i * ld + col];
-      }
+  // this thread's chain: rows r0 + g, r0 + g + 8, ... below r1 of its column
+  const int cnt = ok ? chain_count(r0 + g, r1, 8) : 0;
+  const size_t first = (size_t)(r0 + g) * ld + col, st8 = (size_t)8 * ld;
+  if (forward) {
+    a = ordered_sum<BN1_D, double>(ws_a + first, st8, cnt, 0.0);
+    for (int i = r0 + g, k = 0; k < cnt; i += 8, ++k) {
+      int ni = P - i * tile_rows;
+      ni = ni > tile_rows ? tile_rows : (ni < 0 ? 0 : ni);
+      n += (double)ni;
     }
+  } else {
+    ordered_sum2<BN1_D / 2, double>(ws_a + first, ws_b + first, st8, cnt, a, b);
+  }
   red[0][g][c] = a; red[1][g][c] = b; red[2][g][c] = n;
   __syncthreads();
   double A = 0.0, Bs = 0.0, Nn = 0.0;
@@ -49,14 +125,21 @@ __global__ __launch_bounds__(256) void bn_stage1_kernel(const float* __restrict_
   if (forward) {
     const double mu = Nn > 0.0 ? A / Nn : 0.0;
     double m2 = 0.0;
-    if (ok)
-      for (int i = r0 + g; i < r1; i += 8) {
-        int ni = P - i * tile_rows;
+    // both loads of a batch of rows first, then the arithmetic of the plain loop row by row
+    for (int s = 0; s < cnt; s += BN1_D / 2) {
+      float va[BN1_D / 2], vb[BN1_D / 2];
+      strided_load<BN1_D / 2>(va, ws_a + first + (size_t)s * st8, st8, cnt - s);
+      strided_load<BN1_D / 2>(vb, ws_b + first + (size_t)s * st8, st8, cnt - s);
+#pragma unroll
+      for (int k = 0; k < BN1_D / 2; ++k) {
+        if (s + k >= cnt) continue;
+        int ni = P - (r0 + g + 8 * (s + k)) * tile_rows;
         ni = ni > tile_rows ? tile_rows : ni;
         if (ni <= 0) continue;
-        const double d = (double)ws_a[(size_t)i * ld + col] / (double)ni - mu;
-        m2 += (double)ws_b[(size_t)i * ld + col] + d * d * (double)ni;
+        const double d = (double)va[k] / (double)ni - mu;
+        m2 += (double)vb[k] + d * d * (double)ni;
       }
+    }
     __syncthreads();
     red[1][g][c] = m2;
     __syncthreads();
@@ -125,9 +208,14 @@ __global__ __launch_bounds__(256) void act_amax_kernel(const float* __restrict__
   // the grid is capped at ABSMAX_MAX_BLOCKS partials: a wider layer takes further column trips
   for (int col = blockIdx.x * 32 + c; col < N; col += gridDim.x * 32) {
     float mx = -3.0e38f, mn = 3.0e38f;
-    for (int i = r0 + g; i < r1; i += 8) {
-      mx = fmaxf(mx, ws_c[(size_t)i * ld + col]);
-      mn = fminf(mn, ws_d[(size_t)i * ld + col]);
+    const int cnt = chain_count(r0 + g, r1, 8);
+    const size_t first = (size_t)(r0 + g) * ld + col, st8 = (size_t)8 * ld;
+    for (int s = 0; s < cnt; s += AMAX_D) {      // a repeated last term does not change a maximum
+      float vc[AMAX_D], vd[AMAX_D];
+      strided_load<AMAX_D>(vc, ws_c + first + (size_t)s * st8, st8, cnt - s);
+      strided_load<AMAX_D>(vd, ws_d + first + (size_t)s * st8, st8, cnt - s);
+#pragma unroll
+      for (int k = 0; k < AMAX_D; ++k) { mx = fmaxf(mx, vc[k]); mn = fminf(mn, vd[k]); }
     }
     if (mx >= mn) {
       const float sc = scale[col], sh = shift[col];
@@ -206,11 +294,10 @@ __global__ __launch_bounds__(1024) void partials_reduce_kernel(
   const int col = blockIdx.x * 32 + c;
   const bool ok = col < N;
   double s1 = 0.0, s2 = 0.0;
-  if (ok)
-    for (int i = g; i < R2; i += 32) {
-      s1 += (double)ws_a[(size_t)i * N + col];
-      if (ws_b != nullptr) s2 += (double)ws_b[(size_t)i * N + col];
-    }
+  const int cnt = ok ? chain_count(g, R2, 32) : 0;
+  const size_t first = (size_t)g * N + col, st32 = (size_t)32 * N;
+  if (ws_b != nullptr) ordered_sum2<PARTIALS_D, double>(ws_a + first, ws_b + first, st32, cnt, s1, s2);
+  else s1 = ordered_sum<2 * PARTIALS_D, double>(ws_a + first, st32, cnt, 0.0);
   red[0][g][c] = s1;
   red[1][g][c] = s2;
   __syncthreads();
@@ -402,31 +489,30 @@ __global__ void transpose_kernel(const float* __restrict__ in, int R, int C, lon
 }
 
 // out[i] = sum_s slab[s][i]  (out may have a leading dimension: [rows][cols] -> ld)
-__global__ void slab_reduce_kernel(const float* __restrict__ slab, int S, int rows, int cols,
-                                   float* out, long ldout) {
+// (slabs s = 0..S-1 added left to right in fp64; blocks of 64 or 256 threads, see reduce_slabs)
+__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, int S, int rows, int cols,
+                                                          float* out, long ldout) {
   const size_t len = (size_t)rows * cols;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= len) return;
-  double acc = 0.0;
-  for (int s = 0; s < S; ++s) acc += (double)slab[(size_t)s * len + i];
+  const double acc = ordered_sum<SLAB_D, double>(slab + i, len, S, 0.0);
   const size_t r = i / cols, c = i - r * cols;
   out[r * ldout + c] = (float)acc;
 }
 
 // the weight-gradient slabs and the bias-gradient (column-sum) slabs of one wgrad in one launch
-__global__ void slab_reduce2_kernel(const float* __restrict__ slab, int S, int rows, int cols, float* out,
-                                    long ldout, const float* __restrict__ cslab, int ccols, float* cout) {
+__global__ __launch_bounds__(256) void slab_reduce2_kernel(const float* __restrict__ slab, int S, int rows, int cols,
+                                                           float* out, long ldout, const float* __restrict__ cslab,
+                                                           int ccols, float* cout) {
   const size_t len = (size_t)rows * cols;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < len) {
-    double acc = 0.0;
-    for (int s = 0; s < S; ++s) acc += (double)slab[(size_t)s * len + i];
+    const double acc = ordered_sum<SLAB_D, double>(slab + i, len, S, 0.0);
     const size_t r = i / cols, c = i - r * cols;
     out[r * ldout + c] = (float)acc;
   } else if (i < len + (size_t)ccols) {
     const size_t j = i - len;
-    double acc = 0.0;
-    for (int s = 0; s < S; ++s) acc += (double)cslab[(size_t)s * ccols + j];
+    const double acc = ordered_sum<SLAB_D, double>(cslab + j, (size_t)ccols, S, 0.0);
     cout[j] = (float)acc;
   }
 }
@@ -719,7 +805,8 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restr
   const int cl = threadIdx.x & 63, sl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
   double a = 0.0, b = 0.0;
-  for (int i = sl; i < nb; i += 4) { a += (double)part_g[(size_t)i * LN_C + c]; b += (double)part_b[(size_t)i * LN_C + c]; }
+  const size_t first = (size_t)sl * LN_C + c;
+  ordered_sum2<LN_D, double>(part_g + first, part_b + first, (size_t)4 * LN_C, chain_count(sl, nb, 4), a, b);
   ra[sl][cl] = a; rb[sl][cl] = b;
   __syncthreads();
   if (sl == 0) {
@@ -857,7 +944,7 @@ __global__ __launch_bounds__(256) void pos_hidden_final_kernel(const float* __re
   const int e = blockIdx.x * 16 + el;
   float s = 0.f;
   if (e < 4 * H)
-    for (int b = sl; b < nblk; b += 16) s += part[(size_t)b * 4 * H + e];
+    s = ordered_sum<FINAL_D, float>(part + (size_t)sl * 4 * H + e, (size_t)16 * 4 * H, chain_count(sl, nblk, 16), 0.f);
   red[threadIdx.x] = s;
   __syncthreads();
   if (sl == 0 && e < 4 * H) {
@@ -967,7 +1054,7 @@ __global__ __launch_bounds__(256) void partial_rows_final_kernel(const float* __
   const int e = blockIdx.x * 16 + el;
   float s = 0.f;
   if (e < n_el)
-    for (int b = sl; b < nblk; b += 16) s += part[(size_t)b * n_el + e];
+    s = ordered_sum<FINAL_D, float>(part + (size_t)sl * n_el + e, (size_t)16 * n_el, chain_count(sl, nblk, 16), 0.f);
   red[threadIdx.x] = s;
   __syncthreads();
   if (sl == 0 && e < n_el) {

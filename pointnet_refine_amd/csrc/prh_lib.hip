@@ -97,6 +97,80 @@ struct ProfScope {
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ------------------------------------------------------------------ second-stage reductions
+// One launcher per reduction kind: it picks the grid, so every call site - and the raw test entry
+// points prh_test_reduce_* - runs the same launch.
+//
+// out[rows, cols] (ld ldout) = sum over S slabs; with cslab, cout[ccols] = sum over S column-sum
+// slabs in the same launch.  An output is one fp64 chain over the slabs, so a short output list
+// cannot be spread over more lanes: it takes 64-thread workgroups, one wave per CU.
+int reduce_slabs(const float* slab, int S, int rows, int cols, float* out, long ldout, const float* cslab,
+                 int ccols, float* cout, hipStream_t st) {
+  const long len = (long)rows * cols + (cslab != nullptr ? ccols : 0);
+  if (len <= 0) return PRH_OK;
+  const int bs = len <= 64 * 256 ? 64 : 256;
+  if (cslab != nullptr)
+    hipLaunchKernelGGL(slab_reduce2_kernel, dim3((unsigned)cdiv(len, bs)), dim3(bs), 0, st, slab, S, rows, cols, out,
+                       ldout, cslab, ccols, cout);
+  else
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)cdiv(len, bs)), dim3(bs), 0, st, slab, S, rows, cols, out,
+                       ldout);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+// the three cases of a wgrad's slabs: weights and column sums in one launch, or either alone
+int reduce_wgrad_slabs(const float* slab, const float* colsum_slab, int S, int Mo, int Ni, float* C, long ldc,
+                       float* colsum_out, hipStream_t st) {
+  if (C != nullptr && colsum_out != nullptr) return reduce_slabs(slab, S, Mo, Ni, C, ldc, colsum_slab, Mo, colsum_out, st);
+  if (C != nullptr) return reduce_slabs(slab, S, Mo, Ni, C, ldc, nullptr, 0, nullptr, st);
+  if (colsum_out != nullptr) return reduce_slabs(colsum_slab, S, 1, Mo, colsum_out, (long)Mo, nullptr, 0, nullptr, st);
+  return PRH_OK;
+}
+// BatchNorm statistics stage 1: partials [R][ld] -> slice records out[BN_SLICES][3][N]
+int reduce_bn_stage1(const float* ws_a, const float* ws_b, int R, long ld, int N, int tile_rows, int P, int forward,
+                     double* out, hipStream_t st) {
+  hipLaunchKernelGGL(bn_stage1_kernel, dim3(cdiv(N, 32), BN_SLICES), dim3(256), 0, st, ws_a, ws_b, R, ld, N, tile_rows,
+                     P, forward, out);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+// out_a[c] = sum_i ws_a[i][c], out_b likewise (ws_b may be null; either output may be null)
+int reduce_partials(const float* ws_a, const float* ws_b, int R2, int N, float* out_a, float* out_b, hipStream_t st) {
+  hipLaunchKernelGGL(partials_reduce_kernel, dim3(cdiv(N, 32)), dim3(1024), 0, st, ws_a, ws_b, R2, N, out_a, out_b);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int reduce_ln_param_grad(const float* part_g, const float* part_b, int nb, float* dgamma, float* dbeta, hipStream_t st) {
+  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(LN_C / 64), dim3(256), 0, st, part_g, part_b, nb, dgamma, dbeta);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int reduce_pos_hidden_final(const float* part, int nblk, int hidden, float* dw0, float* db0, hipStream_t st) {
+  hipLaunchKernelGGL(pos_hidden_final_kernel, dim3((unsigned)cdiv(4 * hidden, 16)), dim3(256), 0, st, part, nblk, hidden,
+                     dw0, db0);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int reduce_partial_rows_final(const float* part, int nblk, int n_el, float* out0, int n0, float* out1, hipStream_t st) {
+  hipLaunchKernelGGL(partial_rows_final_kernel, dim3((unsigned)cdiv(n_el, 16)), dim3(256), 0, st, part, nblk, n_el, out0,
+                     n0, out1);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+// amax_slot[0] = max relu(z * scale + shift) from the column maxima / minima ws_c / ws_d [R][ld];
+// apart: ABSMAX_MAX_BLOCKS floats.  A layer wider than ABSMAX_MAX_BLOCKS / BN_SLICES 32-column
+// blocks has each block walk several column groups.
+int reduce_act_amax(const float* ws_c, const float* ws_d, int R, long ld, int N, const float* scale, const float* shift,
+                    float* apart, float* amax_slot, hipStream_t st) {
+  int gx = cdiv(N, 32);
+  gx = gx > ABSMAX_MAX_BLOCKS / BN_SLICES ? ABSMAX_MAX_BLOCKS / BN_SLICES : gx;
+  hipLaunchKernelGGL(act_amax_kernel, dim3(gx, BN_SLICES), dim3(256), 0, st, ws_c, ws_d, R, ld, N, scale, shift, apart);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, (const float*)apart, gx * BN_SLICES, amax_slot);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
 // bump allocator over the caller's workspace (256-B aligned carves).  With base == nullptr
 // it only measures: the *_workspace_bytes queries run the SAME carve functions as the entry
 // points, so the two can never disagree.
@@ -345,24 +419,7 @@ int launch_tn_b16(TNParams& p, float* slab, float* colsum_slab, float* C, long l
     hipLaunchKernelGGL((gemm_tn_b16_kernel<PROB>), dim3((unsigned)blocks), dim3(512), TB_LDS, st, p);
     LAUNCH_CHECK();
   }
-  if (C != nullptr && colsum_out != nullptr) {
-    const size_t len = (size_t)p.Mo * p.Ni + (size_t)p.Mo;
-    hipLaunchKernelGGL(slab_reduce2_kernel, dim3(cdiv((long)len, 256)), dim3(256), 0, st, slab, pl.splits, p.Mo, p.Ni, C,
-                       ldc, (const float*)colsum_slab, p.Mo, colsum_out);
-    LAUNCH_CHECK();
-    return PRH_OK;
-  }
-  if (C != nullptr) {
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((long)p.Mo * p.Ni, 256)), dim3(256), 0, st, slab, pl.splits, p.Mo,
-                       p.Ni, C, ldc);
-    LAUNCH_CHECK();
-  }
-  if (colsum_out != nullptr) {
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(p.Mo, 256)), dim3(256), 0, st, colsum_slab, pl.splits, 1, p.Mo,
-                       colsum_out, (long)p.Mo);
-    LAUNCH_CHECK();
-  }
-  return PRH_OK;
+  return reduce_wgrad_slabs(slab, colsum_slab, pl.splits, p.Mo, p.Ni, C, ldc, colsum_out, st);
 }
 
 // ------------------------------------------------------------------ small-problem cores
@@ -727,25 +784,8 @@ int launch_tn(Cores c, TNParams& p, float* slab, float* colsum_slab, float* C, l
     }
   }
   LAUNCH_CHECK();
-  if (C != nullptr && colsum_out != nullptr) {      // both reductions of a Linear's wgrad in one launch
-    const size_t len = (size_t)p.Mo * p.Ni + (size_t)p.Mo;
-    hipLaunchKernelGGL(slab_reduce2_kernel, dim3(cdiv((long)len, 256)), dim3(256), 0, st, slab, pl.splits, p.Mo,
-                       p.Ni, C, ldc, (const float*)colsum_slab, p.Mo, colsum_out);
-    LAUNCH_CHECK();
-    return PRH_OK;
-  }
-  if (C != nullptr) {
-    const size_t len = (size_t)p.Mo * p.Ni;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((long)len, 256)), dim3(256), 0, st, slab,
-                       pl.splits, p.Mo, p.Ni, C, ldc);
-    LAUNCH_CHECK();
-  }
-  if (colsum_out != nullptr) {
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(p.Mo, 256)), dim3(256), 0, st, colsum_slab,
-                       pl.splits, 1, p.Mo, colsum_out, (long)p.Mo);
-    LAUNCH_CHECK();
-  }
-  return PRH_OK;
+  // (weights and column sums of a Linear's wgrad go in one launch)
+  return reduce_wgrad_slabs(slab, colsum_slab, pl.splits, p.Mo, p.Ni, C, ldc, colsum_out, st);
 }
 
 int transpose(const float* in, int R, int C, float* out, hipStream_t st) {
@@ -847,24 +887,14 @@ int bn_coeffs(const prh_bn_layer& ly, int P, int training, float momentum, float
               float* rstd, float* scale, float* shift, hipStream_t st, const float* ws_c = nullptr,
               const float* ws_d = nullptr, float* apart = nullptr, float* amax_slot = nullptr) {
   if (training) {
-    hipLaunchKernelGGL(bn_stage1_kernel, dim3(cdiv(ly.cout, 32), BN_SLICES), dim3(256), 0, st, ws_a,
-                       ws_b, si.count, (long)ly.cout, ly.cout, si.rows, P, 1, stat2);
-    LAUNCH_CHECK();
+    TRY_RC(reduce_bn_stage1(ws_a, ws_b, si.count, (long)ly.cout, ly.cout, si.rows, P, 1, stat2, st));
     hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(cdiv(ly.cout, 128)), dim3(128), 0, st, stat2, P,
                        ly.cout, ly.gamma, ly.beta, ly.running_mean, ly.running_var,
                        ly.num_batches_tracked, momentum, eps, mean, rstd, scale, shift);
     if (amax_slot != nullptr && ws_c != nullptr) {
-      // every requested slot is written: its consumers do not measure.  apart holds
-      // ABSMAX_MAX_BLOCKS partials, so a layer wider than that many 32-column blocks per slice
-      // has each block walk several column groups
-      int gx = cdiv(ly.cout, 32);
-      gx = gx > ABSMAX_MAX_BLOCKS / BN_SLICES ? ABSMAX_MAX_BLOCKS / BN_SLICES : gx;
+      // every requested slot is written: its consumers do not measure
       LAUNCH_CHECK();
-      hipLaunchKernelGGL(act_amax_kernel, dim3(gx, BN_SLICES), dim3(256), 0, st, ws_c, ws_d,
-                         si.count, (long)ly.cout, ly.cout, (const float*)scale, (const float*)shift, apart);
-      LAUNCH_CHECK();
-      hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, (const float*)apart,
-                         gx * BN_SLICES, amax_slot);
+      TRY_RC(reduce_act_amax(ws_c, ws_d, si.count, (long)ly.cout, ly.cout, scale, shift, apart, amax_slot, st));
     }
   } else {
     hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3(cdiv(ly.cout, 256)), dim3(256), 0, st, ly.gamma,
@@ -967,10 +997,7 @@ int stack_backward(Cores c, const prh_bn_layer* ly, int L, const float* x, int P
   for (int l = L - 1; l >= 0; --l) {
     const int co = ly[l].cout, o = d.off[l];
     // 1. statistics -> BN-backward coefficients, dgamma, dbeta, dbias
-    hipLaunchKernelGGL(bn_stage1_kernel, dim3(cdiv(co, 32), BN_SLICES), dim3(256), 0, st,
-                       w.ws_a + si.off, w.ws_b + si.off, si.count, si.ld ? si.ld : (long)co, co, 64, P,
-                       0, w.stat2);
-    LAUNCH_CHECK();
+    TRY(reduce_bn_stage1(w.ws_a + si.off, w.ws_b + si.off, si.count, si.ld ? si.ld : (long)co, co, 64, P, 0, w.stat2, st));
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(co, 128)), dim3(128), 0, st, w.stat2, P, co,
                        ly[l].gamma, mean + o, rstd + o, training,
                        sc.ca, sc.cb, sc.cc, gr ? gr[l].dgamma : nullptr, gr ? gr[l].dbeta : nullptr,
@@ -1374,10 +1401,7 @@ int prh_pos_hidden_backward(const float* xyz, long ld, const float* h, const flo
   hipLaunchKernelGGL(dxyz != nullptr ? pos_hidden_bwd_kernel<true> : pos_hidden_bwd_kernel<false>, dim3((unsigned)nb),
                      dim3(256), 0, st, xyz, ld, h, dh, part, rows, hidden, w0, dxyz);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(pos_hidden_final_kernel, dim3((unsigned)cdiv(4 * hidden, 16)), dim3(256), 0, st,
-                     (const float*)part, nb, hidden, dw0, db0);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  return reduce_pos_hidden_final(part, nb, hidden, dw0, db0, st);
 }
 
 // ---- nn.Linear with <= 4 outputs (regression heads' last layer, src/model.py:162-166) ----
@@ -1434,10 +1458,7 @@ int prh_linear_small_backward(const float* x, const float* w, const float* dy, f
     default: hipLaunchKernelGGL(linear_small_bwd_kernel<4>, dim3((unsigned)nb), dim3(256), 0, st, x, w, dy, dx, part, rows, k); break;
   }
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(partial_rows_final_kernel, dim3((unsigned)cdiv(n_el, 16)), dim3(256), 0, st,
-                     (const float*)part, nb, n_el, dw, n * k, db);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  return reduce_partial_rows_final(part, nb, n_el, dw, n * k, db, st);
 }
 
 size_t prh_linear_backward_workspace_bytes(int rows, int k, int n) {
@@ -1741,9 +1762,7 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
                      d_gfeat, sv->argmax, sv->z_fus, sv->gate, sv->bn_scale + cat,
                      sv->bn_shift + cat, P, N, od, dyf, w.ws_a, w.ws_b);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_stage1_kernel, dim3(cdiv(od, 32), BN_SLICES), dim3(256), 0, st, w.ws_a, w.ws_b,
-                     cdiv(P, 64), (long)od, od, 64, P, 0, w.stat2);
-  LAUNCH_CHECK();
+  TRY(reduce_bn_stage1(w.ws_a, w.ws_b, cdiv(P, 64), (long)od, od, 64, P, 0, w.stat2, st));
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(od, 128)), dim3(128), 0, st, w.stat2, P, od,
                      prm->fusion.gamma, sv->bn_mean + cat, sv->bn_rstd + cat,
                      training, sc.ca, sc.cb, sc.cc, gr->fusion.dgamma, gr->fusion.dbeta,
@@ -1813,10 +1832,8 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
     p.flags = F_MASK | F_STATS | F_E1_ROWVEC;
     StatInfo sig;
     TRY((launch_nt<PRO_NONE, EPI_DGRAD>(c, p, st, &sig)));
-    hipLaunchKernelGGL(partials_reduce_kernel, dim3(2), dim3(1024), 0, st, w.ws_a, w.ws_b,
-                       sig.count, 64, gr->d_gate_b1 ? gr->d_gate_b1 : gsum_a,
-                       gr->d_gate_w1 ? gr->d_gate_w1 : gsum_b);
-    LAUNCH_CHECK();
+    TRY(reduce_partials(w.ws_a, w.ws_b, sig.count, 64, gr->d_gate_b1 ? gr->d_gate_b1 : gsum_a,
+                        gr->d_gate_w1 ? gr->d_gate_w1 : gsum_b, st));
     if (d_ctx != nullptr) {
       hipLaunchKernelGGL(gate1_dctx_kernel, dim3(cdiv(P, 4)), dim3(256), 0, st, dU, P, 64,
                          prm->gate_w1, d_ctx, (long)C);
@@ -1962,9 +1979,7 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
                        d_gfeat, sv->argmax, (const u16*)sv->z_fus, (u16*)sv->gate, sv->bn_scale + cat, sv->bn_shift + cat,
                        P, N, od, w.dyf, w.ws_a, w.ws_b);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_stage1_kernel, dim3(cdiv(od, 32), BN_SLICES), dim3(256), 0, st, w.ws_a, w.ws_b, cdiv(P, 64),
-                     (long)od, od, 64, P, 0, w.stat2);
-  LAUNCH_CHECK();
+  TRY(reduce_bn_stage1(w.ws_a, w.ws_b, cdiv(P, 64), (long)od, od, 64, P, 0, w.stat2, st));
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(od, 128)), dim3(128), 0, st, w.stat2, P, od, prm->fusion.gamma,
                      sv->bn_mean + cat, sv->bn_rstd + cat, training, w.ca, w.cb, w.cc, gr->fusion.dgamma,
                      gr->fusion.dbeta, gr->fusion.db);
@@ -1993,9 +2008,7 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
   for (int l = 4; l >= 0; --l) {
     const prh_bn_layer& ly = prm->conv[l];
     const int co = ly.cout, o = d.off[l];
-    hipLaunchKernelGGL(bn_stage1_kernel, dim3(cdiv(co, 32), BN_SLICES), dim3(256), 0, st, w.ws_a + si.off, w.ws_b + si.off,
-                       si.count, si.ld ? si.ld : (long)co, co, 64, P, 0, w.stat2);
-    LAUNCH_CHECK();
+    TRY(reduce_bn_stage1(w.ws_a + si.off, w.ws_b + si.off, si.count, si.ld ? si.ld : (long)co, co, 64, P, 0, w.stat2, st));
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(co, 128)), dim3(128), 0, st, w.stat2, P, co, ly.gamma,
                        sv->bn_mean + o, sv->bn_rstd + o, training, w.ca, w.cb, w.cc, gr->conv[l].dgamma,
                        gr->conv[l].dbeta, gr->conv[l].db);
@@ -2009,9 +2022,7 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
         hipLaunchKernelGGL((conv_in_wgrad_b16_kernel<64>), dim3(nb), dim3(256), 0, st, (const u16*)(w.dy_cat + o), (long)cat,
                            ctx, C, P, rpb, w.c1part);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((long)co * C, 256)), dim3(256), 0, st, (const float*)w.c1part, nb, co, C,
-                           gr->conv[0].dw, (long)C);
-        LAUNCH_CHECK();
+        TRY(reduce_slabs(w.c1part, nb, co, C, gr->conv[0].dw, (long)C, nullptr, 0, nullptr, st));
       } else if (l == 0) {
         t.B = f16p(w.xpad); t.ldb = c0p; t.Ni = c0p;
         float* out = c0p == C ? gr->conv[0].dw : w.wT;        // padded input: reduce into scratch, drop the pad columns
@@ -2058,9 +2069,8 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
     p.flags = F_MASK | F_STATS | F_E1_ROWVEC;
     StatInfo sig;
     TRY((launch_nt_b16<PRO_NONE, EPI_DGRAD, true, false>(p, st, &sig)));
-    hipLaunchKernelGGL(partials_reduce_kernel, dim3(2), dim3(1024), 0, st, w.ws_a, w.ws_b, sig.count, 64,
-                       gr->d_gate_b1 ? gr->d_gate_b1 : w.gsum_a, gr->d_gate_w1 ? gr->d_gate_w1 : w.gsum_b);
-    LAUNCH_CHECK();
+    TRY(reduce_partials(w.ws_a, w.ws_b, sig.count, 64, gr->d_gate_b1 ? gr->d_gate_b1 : w.gsum_a,
+                        gr->d_gate_w1 ? gr->d_gate_w1 : w.gsum_b, st));
     if (d_ctx != nullptr) {
       hipLaunchKernelGGL(gate1_dctx_kernel, dim3(cdiv(P, 4)), dim3(256), 0, st, w.dU, P, 64, prm->gate_w1, d_ctx, (long)C);
       LAUNCH_CHECK();
@@ -2314,10 +2324,7 @@ int prh_add_dropout_layernorm_backward(const float* dy, const float* x, const fl
   hipLaunchKernelGGL(add_dropout_ln_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, st, dy, x, r, gamma, mean, rstd, rows,
                      seed, (const unsigned*)g_seed_src, thresh, 1.f / (1.f - dropout_p), dx, dr, pg, pb);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(LN_C / 64), dim3(256), 0, st, (const float*)pg, (const float*)pb, (int)nb,
-                     dgamma, dbeta);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  return reduce_ln_param_grad(pg, pb, (int)nb, dgamma, dbeta, st);
 }
 
 // ------------------------------------------------------------------ loss + optimiser (row f3)
@@ -3881,6 +3888,70 @@ int prh_test_gemm_tn_side(const float* a, const float* b, float* c, float* colsu
   TRY((launch_tn<PRO_NONE, PRO_NONE>(cores, t, slab, cs, c, (long)ni, colsum, st)));
   HIP_TRY(hipMemcpyAsync(amax_out, hdr, sizeof(float), hipMemcpyDeviceToDevice, st));
   return PRH_OK;
+}
+
+// Raw second-stage reductions: device pointers in, through the launchers the library calls.
+int prh_test_reduce_depth(int kind) {
+  switch (kind) {
+    case PRH_REDUCE_SLABS: return SLAB_D;
+    case PRH_REDUCE_BN_STAGE1: return BN1_D;
+    case PRH_REDUCE_PARTIALS: return PARTIALS_D;
+    case PRH_REDUCE_LN_PARAM_GRAD: return LN_D;
+    case PRH_REDUCE_FINAL: return FINAL_D;
+    case PRH_REDUCE_ACT_AMAX: return AMAX_D;
+    default: return 0;
+  }
+}
+int prh_test_reduce_slabs(const float* slab, int s, int rows, int cols, float* out, long ldout, const float* cslab,
+                          int ccols, float* cout, int device, void* stream) {
+  if (!slab || !out || s < 1 || rows < 1 || cols < 1 || ldout < cols || (cslab != nullptr && (!cout || ccols < 1)))
+    return fail(PRH_ERR_ARG, "test_reduce_slabs: bad argument");
+  HIP_TRY(hipSetDevice(device));
+  return reduce_slabs(slab, s, rows, cols, out, ldout, cslab, ccols, cout, (hipStream_t)stream);
+}
+int prh_test_reduce_bn_stage1(const float* ws_a, const float* ws_b, int r, long ld, int n, int tile_rows, int p,
+                              int forward, double* out, int device, void* stream) {
+  if (!ws_a || !ws_b || !out || r < 1 || n < 1 || ld < n || tile_rows < 1 || p < 1)
+    return fail(PRH_ERR_ARG, "test_reduce_bn_stage1: bad argument");
+  HIP_TRY(hipSetDevice(device));
+  return reduce_bn_stage1(ws_a, ws_b, r, ld, n, tile_rows, p, forward, out, (hipStream_t)stream);
+}
+int prh_test_reduce_partials(const float* ws_a, const float* ws_b, int r2, int n, float* out_a, float* out_b,
+                             int device, void* stream) {
+  if (!ws_a || r2 < 1 || n < 1) return fail(PRH_ERR_ARG, "test_reduce_partials: bad argument");
+  HIP_TRY(hipSetDevice(device));
+  return reduce_partials(ws_a, ws_b, r2, n, out_a, out_b, (hipStream_t)stream);
+}
+int prh_test_reduce_ln_param_grad(const float* part_g, const float* part_b, int nb, float* dgamma, float* dbeta,
+                                  int device, void* stream) {
+  if (!part_g || !part_b || !dgamma || !dbeta || nb < 1) return fail(PRH_ERR_ARG, "test_reduce_ln_param_grad: bad argument");
+  HIP_TRY(hipSetDevice(device));
+  return reduce_ln_param_grad(part_g, part_b, nb, dgamma, dbeta, (hipStream_t)stream);
+}
+int prh_test_reduce_pos_hidden_final(const float* part, int nblk, int hidden, float* dw0, float* db0, int device,
+                                     void* stream) {
+  if (!part || nblk < 1 || hidden < 1) return fail(PRH_ERR_ARG, "test_reduce_pos_hidden_final: bad argument");
+  HIP_TRY(hipSetDevice(device));
+  return reduce_pos_hidden_final(part, nblk, hidden, dw0, db0, (hipStream_t)stream);
+}
+int prh_test_reduce_partial_rows_final(const float* part, int nblk, int n_el, float* out0, int n0, float* out1,
+                                       int device, void* stream) {
+  if (!part || nblk < 1 || n_el < 1 || n0 < 0 || n0 > n_el)
+    return fail(PRH_ERR_ARG, "test_reduce_partial_rows_final: bad argument");
+  HIP_TRY(hipSetDevice(device));
+  return reduce_partial_rows_final(part, nblk, n_el, out0, n0, out1, (hipStream_t)stream);
+}
+size_t prh_test_reduce_act_amax_workspace_bytes(void) { return (size_t)ABSMAX_MAX_BLOCKS * sizeof(float) + 256; }
+int prh_test_reduce_act_amax(const float* ws_c, const float* ws_d, int r, long ld, int n, const float* scale,
+                             const float* shift, float* amax_out, void* workspace, size_t workspace_bytes, int device,
+                             void* stream) {
+  if (!ws_c || !ws_d || !scale || !shift || !amax_out || r < 1 || n < 1 || ld < n)
+    return fail(PRH_ERR_ARG, "test_reduce_act_amax: bad argument");
+  Arena ar(workspace, workspace_bytes);
+  float* apart = ar.f(ABSMAX_MAX_BLOCKS);
+  if (!ar.ok) return fail(PRH_ERR_WORKSPACE, "test_reduce_act_amax: workspace too small");
+  HIP_TRY(hipSetDevice(device));
+  return reduce_act_amax(ws_c, ws_d, r, ld, n, scale, shift, apart, amax_out, (hipStream_t)stream);
 }
 
 }  // extern "C"
