@@ -77,7 +77,8 @@ typedef struct {
 typedef struct {
   float* z_cat;      /* [P, cat]      pre-BN outputs of conv1..5, concatenated by column */
   float* z_fus;      /* [P, out_dim]  pre-BN output of the fusion conv */
-  float* gate;       /* [P, out_dim]  0.5+0.5*sigmoid(.) ; may be NULL when no backward */
+  float* gate;       /* [P, out_dim]  0.5+0.5*sigmoid(.) ; may be NULL in the forward when no backward
+                      * follows or when the backward computes it again (gate_recompute below) */
   float* bn_scale;   /* [cat+out_dim] gamma*rstd            (BN as y = z*scale+shift) */
   float* bn_shift;   /* [cat+out_dim] beta - mean*scale */
   float* bn_mean;    /* [cat+out_dim] */
@@ -89,7 +90,20 @@ typedef struct {
                       * the backward reads them as operand scales of its wgrads instead of
                       * re-measuring.  Pass the same buffer to both calls
                       * (and keep the GEMM mode unchanged in between), or NULL to both. */
+  int gate_recompute; /* prh_encoder_backward only (the forward ignores it).  0: `gate` holds the forward's
+                      * gate.  1: `gate` is uninitialised scratch for dG - the backward runs the gate GEMM again
+                      * and forms the gate in its epilogue, bit for bit the forward's; allowed only where
+                      * prh_encoder_gate_recompute() returns 1 under the GEMM mode of the backward call
+                      * (the forward may then have been called with gate = NULL).  Last field: callers
+                      * that zero-initialise the struct keep the stored-gate path. */
 } prh_encoder_saved;
+
+/* 1 when prh_encoder_backward can compute the intensity gate again instead of reading a stored copy
+ * (4 * out_dim bytes per point neither written by the forward nor read back): no pooled output / gradient
+ * (want_global = 0) and, under the current GEMM mode, the gate launch of this shape runs on the
+ * second-generation split-fp16 core with the vector epilogue (mode 3, out_dim % 4 == 0 and at least 32 tiles
+ * of 256 x 256 with B*N >= 512).  0 otherwise: pass `gate` to the forward and leave gate_recompute 0. */
+int prh_encoder_gate_recompute(int B, int N, int in_channel, int out_dim, int want_global);
 
 /* Bytes of scratch the encoder entry points need for P = B*N points
  * (backward = 0: prh_encoder_forward only; 1: also prh_encoder_backward; 2: prh_encoder_backward with
@@ -110,7 +124,8 @@ int prh_encoder_forward(const prh_encoder_params* prm, const float* ctx, int B, 
  *   d_fused [B,N,out_dim] or NULL, d_gfeat [B,2*out_dim] or NULL (at least one)
  *   d_ctx   [B,N,C] or NULL
  *   training must equal the forward's flag.
- * d_gfeat is read only; saved.gate is consumed (overwritten in place).  d_fused is read only unless
+ * d_gfeat is read only; saved.gate is consumed (overwritten in place by dG; with saved.gate_recompute = 1 it
+ * is only written).  d_fused is read only unless
  * d_fused_scratch = 1 (needs d_fused != NULL and d_gfeat == NULL - the path LineRefineNet takes): then the
  * library turns the caller's d_fused buffer into the fusion layer's gradient scratch (dy_f, then dz_f, in place)
  * instead of carving one from the workspace - 17 GB less at 4.19 M points; its content is undefined afterwards. */
@@ -1076,6 +1091,15 @@ int prh_set_dropout_seed_source(const unsigned* device_word);
 int prh_test_gemm_nt(const float* a, const float* w, float* c, int m, int n, int k,
                      void* workspace, size_t workspace_bytes, int device, void* stream);
 size_t prh_test_gemm_tn_workspace_bytes(int p, int mo, int ni);
+/* Step (1) of prh_encoder_backward on its own (tests/test_gate_recompute_gpu.py), without a pooled gradient:
+ * d_fused [P, out_dim] becomes dy_f in place, gate [P, out_dim] (recompute == 0: the forward's gate on entry;
+ * != 0: uninitialised) becomes dG, ws_a / ws_b [ceil(P/64), out_dim] take the BatchNorm-backward partials
+ * (sum dy, sum dy * z_fus per 64-row block).  bn_scale / bn_shift [out_dim]: the fusion BatchNorm. */
+size_t prh_test_gate_backward_workspace_bytes(int out_dim);
+int prh_test_gate_backward(const float* ctx, int B, int N, int in_channel, int out_dim, const float* gate_w1,
+                           const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* z_fus,
+                           const float* bn_scale, const float* bn_shift, float* d_fused, float* gate, int recompute,
+                           float* ws_a, float* ws_b, void* workspace, size_t workspace_bytes, int device, void* stream);
 int prh_test_gemm_tn(const float* a, const float* b, float* c, float* colsum, int p, int mo,
                      int ni, void* workspace, size_t workspace_bytes, int device, void* stream);
 /* The tn core with a BatchNorm-backward apply pass, dy[rows,cols] <- ka*dy + kb*z + kc in place:

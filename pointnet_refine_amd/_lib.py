@@ -49,7 +49,8 @@ class EncoderGrads(C.Structure):
 class EncoderSaved(C.Structure):
     _fields_ = [("z_cat", C.c_void_p), ("z_fus", C.c_void_p), ("gate", C.c_void_p),
                 ("bn_scale", C.c_void_p), ("bn_shift", C.c_void_p), ("bn_mean", C.c_void_p),
-                ("bn_rstd", C.c_void_p), ("argmax", C.c_void_p), ("op_amax", C.c_void_p)]
+                ("bn_rstd", C.c_void_p), ("argmax", C.c_void_p), ("op_amax", C.c_void_p),
+                ("gate_recompute", C.c_int)]      # trailing, 0 by default: the stored-gate backward
 
 
 class EncoderSavedBf16(C.Structure):
@@ -59,7 +60,7 @@ class EncoderSavedBf16(C.Structure):
 
 
 EXPORTS = [
-    "prh_encoder_workspace_bytes", "prh_encoder_forward", "prh_encoder_backward",
+    "prh_encoder_workspace_bytes", "prh_encoder_gate_recompute", "prh_encoder_forward", "prh_encoder_backward",
     "prh_encoder_bf16_workspace_bytes", "prh_encoder_forward_bf16", "prh_encoder_backward_bf16",
     "prh_linear_bf16_workspace_bytes", "prh_linear_forward_bf16", "prh_linear_backward_bf16",
     "prh_linear_forward_out16", "prh_linear_backward_dy16", "prh_attn_forward_kv16", "prh_attn_backward_kv16",
@@ -74,6 +75,7 @@ EXPORTS = [
     "prh_linear_backward_workspace_bytes", "prh_linear_backward", "prh_linear_backward_ex",
     "prh_mlp_stack_workspace_bytes", "prh_mlp_stack_forward", "prh_mlp_stack_backward",
     "prh_test_gemm_nt", "prh_test_gemm_tn_workspace_bytes", "prh_test_gemm_tn",
+    "prh_test_gate_backward_workspace_bytes", "prh_test_gate_backward",
     "prh_test_gemm_tn_side_workspace_bytes", "prh_test_gemm_tn_side", "prh_test_xcc_map",
     "prh_test_reduce_depth", "prh_test_reduce_slabs", "prh_test_reduce_bn_stage1", "prh_test_reduce_partials",
     "prh_test_reduce_ln_param_grad", "prh_test_reduce_pos_hidden_final", "prh_test_reduce_partial_rows_final",
@@ -141,6 +143,8 @@ def _bind(lib):
     lib.prh_version.restype = C.c_char_p
     lib.prh_encoder_workspace_bytes.restype = sz
     lib.prh_encoder_workspace_bytes.argtypes = [i, i, i, i, i]
+    lib.prh_encoder_gate_recompute.restype = i
+    lib.prh_encoder_gate_recompute.argtypes = [i, i, i, i, i]
     lib.prh_encoder_forward.restype = i
     lib.prh_encoder_forward.argtypes = [C.POINTER(EncoderParams), vp, i, i, i, f, f, vp, vp,
                                         C.POINTER(EncoderSaved), vp, sz, i, vp]
@@ -428,6 +432,10 @@ def _bind(lib):
                                      C.POINTER(C.c_double)]
     lib.prh_test_gemm_nt.restype = i
     lib.prh_test_gemm_nt.argtypes = [vp, vp, vp, i, i, i, vp, sz, i, vp]
+    lib.prh_test_gate_backward_workspace_bytes.restype = sz
+    lib.prh_test_gate_backward_workspace_bytes.argtypes = [i]
+    lib.prh_test_gate_backward.restype = i
+    lib.prh_test_gate_backward.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, sz, i, vp]
     lib.prh_test_gemm_tn_workspace_bytes.restype = sz
     lib.prh_test_gemm_tn_workspace_bytes.argtypes = [i, i, i]
     lib.prh_test_gemm_tn.restype = i

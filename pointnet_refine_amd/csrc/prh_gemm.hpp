@@ -30,7 +30,7 @@ namespace prh {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum { PRO_NONE = 0, PRO_BNRELU = 1, PRO_BNBWD = 2, PRO_GATE1 = 3 };
-enum { EPI_BIAS = 0, EPI_BIAS_STATS = 1, EPI_GATE = 2, EPI_DGRAD = 3 };
+enum { EPI_BIAS = 0, EPI_BIAS_STATS = 1, EPI_GATE = 2, EPI_DGRAD = 3, EPI_GATE_BWD = 4 };
 
 // flags
 enum {
@@ -61,7 +61,7 @@ struct NTParams {
   const float* pa; const float* pb; const float* pc;   // prologue vectors over K
   const float* E1; long lde1;    // epilogue operand [M,N] (zf for GATE, z for DGRAD mask)
   const float* es; const float* et;  // epilogue per-column scale/shift
-  float* C2;       long ldc2;    // EPI_GATE second output
+  float* C2;       long ldc2;    // EPI_GATE second output (the gate); EPI_GATE_BWD: dG
   float* ws_a; float* ws_b;      // stats partials [2*row_tiles][N]
   float* ws_c; float* ws_d;      // EPI_BIAS_STATS: per-column max / min of the outputs per row block
                                  //   (null: not produced) - the exact maximum of relu(bn(z)) follows
@@ -127,6 +127,20 @@ __device__ __forceinline__ float4 pro_apply(float4 a, float4 a2, float4 ka, floa
 
 __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
+// Intensity gate m = 0.5 + 0.5*sigmoid(a), a = accumulator + gate_b2 (src/model.py:54-55).  One expression for
+// the forward epilogues (EPI_GATE) and the backward that computes the gate again (EPI_GATE_BWD): same bits.
+__device__ __forceinline__ float gate_m(float a) { return 0.5f + 0.5f / (1.f + __expf(-a)); }
+__device__ __forceinline__ float4 gate_m4(float4 a) { return make_float4(gate_m(a.x), gate_m(a.y), gate_m(a.z), gate_m(a.w)); }
+// Backward of F = relu(z*sc+sh) * m for one element, d = dL/dF: dy = dL/d(relu input's BN output), dg = dL/d(gate
+// pre-activation) with sig = 2m-1.  Shared by combine_bwd_kernel (stored gate) and EPI_GATE_BWD (recomputed gate).
+__device__ __forceinline__ void gate_bwd_elem(float d, float z, float m, float sc, float sh, float& dy, float& dg) {
+  const float pre = fmaf(z, sc, sh);
+  const float r = fmaxf(pre, 0.f);
+  const float sig = 2.f * m - 1.f;
+  dy = pre > 0.f ? d * m : 0.f;
+  dg = d * r * 0.5f * sig * (1.f - sig);
+}
 
 // ---------------------------------------------------------------------------------------
 // Shared epilogue over a wave's accumulator tile acc[MT][NT] of 32x32 MFMA blocks
@@ -214,7 +228,7 @@ __device__ __forceinline__ void nt_epilogue(f32x16 (&acc)[MT][NT], const NTParam
           const int lr = mt * 32 + crow(r, half);
           if (lr < mrows && cok) {
             const float g = acc[mt][nt][r] + bias;
-            const float m = 0.5f + 0.5f / (1.f + __expf(-g));
+            const float m = gate_m(g);
             const float zf = Eb[lr * lde1 + col];
             const float rl = fmaxf(fmaf(zf, es, et), 0.f);
             Cb[lr * ldc + col] = rl * m;
@@ -456,10 +470,13 @@ template <int EPI, int MT, class ACC, bool C16, bool AMAX = false>
 __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, int rbase_,
                                                 int cbase, int rb, int lane, float* scratch,
                                                 bool bias_done = false,      // bias already in acc
-                                                float* wave_amax = nullptr) {
+                                                float* wave_amax = nullptr,
+                                                float* zscr = nullptr) {     // EPI_GATE_BWD: 16 * EPI_LDW floats, wave-private
   static_assert(!AMAX || (EPI == EPI_BIAS && !C16), "output maximum: EPI_BIAS with fp32 storage");
-  typedef typename std::conditional<AMAX, char*, epi_wptr_r>::type wptr;
-  typedef typename std::conditional<AMAX, const char*, epi_rptr_r>::type rptr;
+  static_assert(EPI != EPI_GATE_BWD || !C16, "gate backward: fp32 storage");
+  // EPI_GATE_BWD turns C (d_fused) into dy in place, like AMAX with E1 = C: same lane loads and stores an element
+  typedef typename std::conditional<AMAX || EPI == EPI_GATE_BWD, char*, epi_wptr_r>::type wptr;
+  typedef typename std::conditional<AMAX || EPI == EPI_GATE_BWD, const char*, epi_rptr_r>::type rptr;
   const int rbase = __builtin_amdgcn_readfirstlane(rbase_);
   const float* biasp = bias_done ? nullptr : p.bias;
   constexpr int ES = C16 ? 2 : 4;
@@ -475,12 +492,12 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
   float4 bias4 = zero4(), es4 = zero4(), et4 = zero4();
   if (c4ok) {
     if (biasp != nullptr) bias4 = ldg4(biasp + col4);
-    if ((EPI == EPI_DGRAD && (p.flags & F_MASK) != 0) || EPI == EPI_GATE) {
+    if ((EPI == EPI_DGRAD && (p.flags & F_MASK) != 0) || EPI == EPI_GATE || EPI == EPI_GATE_BWD) {
       es4 = ldg4(p.es + col4);
       et4 = ldg4(p.et + col4);
     }
   }
-  char* __restrict__ C2b = (EPI == EPI_GATE && p.C2 != nullptr) ? reinterpret_cast<char*>(p.C2) + (size_t)rbase * p.ldc2 * ES : nullptr;
+  char* __restrict__ C2b = ((EPI == EPI_GATE || EPI == EPI_GATE_BWD) && p.C2 != nullptr) ? reinterpret_cast<char*>(p.C2) + (size_t)rbase * p.ldc2 * ES : nullptr;
   const int ldc2 = (int)p.ldc2;
 
   // statistics straight from the accumulators (column on the lane): sum, then centred M2
@@ -490,7 +507,7 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
   const bool stats = EPI == EPI_DGRAD && (p.flags & F_STATS) != 0;
   const bool resid = EPI == EPI_BIAS && (p.flags & F_RESID) != 0;
   const unsigned dseed = (EPI == EPI_BIAS && (p.flags & F_DROPOUT) != 0) ? epi_seed(p) : 0u;
-  const bool need_z = (EPI == EPI_DGRAD && (mask || stats)) || EPI == EPI_GATE || resid;
+  const bool need_z = (EPI == EPI_DGRAD && (mask || stats)) || EPI == EPI_GATE || EPI == EPI_GATE_BWD || resid;
   float4 s1 = zero4(), s2 = zero4();
   const bool pool = EPI == EPI_GATE && (p.flags & F_POOL) != 0;
   float pmx[4] = {-1.f, -1.f, -1.f, -1.f}, psm[4] = {0.f, 0.f, 0.f, 0.f};     // outputs are >= 0
@@ -505,8 +522,9 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
   // load bases: a wave tile entirely below the matrix reads (and discards) row 0 instead
   rptr Cl = mrows > 0 ? Cb : reinterpret_cast<const char*>(p.C);
   rptr El = mrows > 0 ? Eb : reinterpret_cast<const char*>(p.E1);
-  const bool acc_old = EPI == EPI_DGRAD && accum;
+  const bool acc_old = (EPI == EPI_DGRAD && accum) || EPI == EPI_GATE_BWD;
   float amx = 0.f;      // AMAX: largest |v| this lane stored
+  float t1 = 0.f, t2 = 0.f;      // EPI_GATE_BWD: BatchNorm-backward partials of the current 64-row block (column = lane)
   // Batches of 4 row groups (two per 32-row block), software-pipelined one deep: batch b+1's
   // operand loads are issued before batch b is processed.  (Measured against the unpipelined
   // order on one box: fusion dgrad 49.6 vs 50.0 ms - the wave sharing the SIMD already covers
@@ -578,9 +596,7 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
         s2.z = fmaf(q.z, z.z, s2.z); s2.w = fmaf(q.w, z.w, s2.w);
       } else if (EPI == EPI_GATE) {
         // F = relu(zf*s+t) * m,  m = 0.5 + 0.5*sigmoid(acc + b)     (src/model.py:51,54-55)
-        float4 m;
-        m.x = 0.5f + 0.5f / (1.f + __expf(-v.x)); m.y = 0.5f + 0.5f / (1.f + __expf(-v.y));
-        m.z = 0.5f + 0.5f / (1.f + __expf(-v.z)); m.w = 0.5f + 0.5f / (1.f + __expf(-v.w));
+        const float4 m = gate_m4(v);
         v.x = fmaxf(fmaf(z.x, es4.x, et4.x), 0.f) * m.x; v.y = fmaxf(fmaf(z.y, es4.y, et4.y), 0.f) * m.y;
         v.z = fmaxf(fmaf(z.z, es4.z, et4.z), 0.f) * m.z; v.w = fmaxf(fmaf(z.w, es4.w, et4.w), 0.f) * m.w;
         if (ok && (p.flags & F_STORE_GATE) != 0) st4e<C16>(C2b, lr * ldc2 + col4, m);
@@ -593,6 +609,19 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
             psm[e] += vv[e];
           }
         }
+      } else if (EPI == EPI_GATE_BWD) {
+        // the forward's gate again (same core, same bits), then combine_bwd_kernel's arithmetic on d = old C:
+        // C <- dy, C2 <- dG.  dy and z stay in wave-private LDS for the ordered partial sums below: dy takes
+        // the scratch slot this lane has just read, z the matching row of zscr.
+        const float4 m = gate_m4(v);
+        float4 dg;
+        gate_bwd_elem(o.x, z.x, m.x, es4.x, et4.x, v.x, dg.x);
+        gate_bwd_elem(o.y, z.y, m.y, es4.y, et4.y, v.y, dg.y);
+        gate_bwd_elem(o.z, z.z, m.z, es4.z, et4.z, v.z, dg.z);
+        gate_bwd_elem(o.w, z.w, m.w, es4.w, et4.w, v.w, dg.w);
+        if (ok) st4e<C16>(C2b, lr * ldc2 + col4, dg);
+        *reinterpret_cast<float4*>(scratch + lrow * EPI_LDW + c4) = v;
+        *reinterpret_cast<float4*>(zscr + (i * 4 + rr) * EPI_LDW + c4) = z;
       } else {
         if (resid) { v.x += z.x; v.y += z.y; v.z += z.z; v.w += z.w; }
         if ((p.flags & F_RELU_OUT) != 0) {
@@ -614,6 +643,44 @@ __device__ __forceinline__ void nt_epilogue_vec_r2(ACC& acc, const NTParams& p, 
     // 9 GB of scratch writes per fusion-dgrad launch at B=4096)
     if (EPI == EPI_DGRAD)
       asm volatile("" : "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(s1.w), "+v"(s2.x), "+v"(s2.y), "+v"(s2.z), "+v"(s2.w));
+    if constexpr (EPI == EPI_GATE_BWD) {
+      // BatchNorm-backward partials in combine_bwd_kernel's layout and order: ws_a / ws_b [cdiv(M,64)][N]; per
+      // 64-row block and column four chains over 16 consecutive rows each (s1 += dy, s2 = fma(dy, z, s2), rows
+      // ascending, rows >= M skipped), combined ((c0 + c1) + c2) + c3.  A batch is exactly one chain (the wave
+      // tile starts on a multiple of 128 rows), but its rows are interleaved over the lanes (rr), so the lane
+      // sums of F_STATS give another order: walk the batch out of LDS instead, column = lane.
+      const int nv = mrows - (mt * 32 + hb * 16);      // rows of this chain that exist
+      float c1 = 0.f, c2 = 0.f;
+      if (nv >= 16) {      // wave-uniform
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const float dyj = scratch[(hb * 16 + j) * EPI_LDW + lane];
+          c1 += dyj;
+          c2 = fmaf(dyj, zscr[j * EPI_LDW + lane], c2);
+        }
+      } else {
+        // ragged chain: the bound sits in a VGPR so that each row's test is made where it is used (as scalar
+        // tests the compiler hoists all 128 of a tile to the top and spills SGPRs)
+        int nvv = nv;
+        asm volatile("" : "+v"(nvv));
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const float dyj = scratch[(hb * 16 + j) * EPI_LDW + lane];
+          const float zj = zscr[j * EPI_LDW + lane];
+          c1 = j < nvv ? c1 + dyj : c1;
+          c2 = j < nvv ? fmaf(dyj, zj, c2) : c2;
+        }
+      }
+      if ((b & 3) == 0) { t1 = c1; t2 = c2; }
+      else { t1 += c1; t2 += c2; }
+      if ((b & 3) == 3) {
+        const int kb = (rbase >> 6) + (b >> 2);
+        if ((long)kb * 64 < p.M && cbase + lane < p.N) {
+          p.ws_a[(size_t)kb * p.N + cbase + lane] = t1;
+          p.ws_b[(size_t)kb * p.N + cbase + lane] = t2;
+        }
+      }
+    }
   }
   if (pool) {
     // combine the 4 row groups (lane bits 4, 5): larger value wins, ties go to the smaller row
@@ -654,11 +721,13 @@ template <int EPI, int MT, class ACC, bool C16 = false, bool AMAX = false>
 __device__ __forceinline__ void nt_epilogue_vec(ACC& acc, const NTParams& p, int rbase_,
                                                 int cbase, int rb, int lane, float* scratch,
                                                 bool bias_done = false,      // bias already in acc
-                                                float* wave_amax = nullptr) {
+                                                float* wave_amax = nullptr,
+                                                float* zscr = nullptr) {     // EPI_GATE_BWD (fp32 storage only)
   if constexpr (!C16) {
-    nt_epilogue_vec_r2<EPI, MT, ACC, false, AMAX>(acc, p, rbase_, cbase, rb, lane, scratch, bias_done, wave_amax);
+    nt_epilogue_vec_r2<EPI, MT, ACC, false, AMAX>(acc, p, rbase_, cbase, rb, lane, scratch, bias_done, wave_amax, zscr);
     return;
   }
+  static_assert(EPI != EPI_GATE_BWD || !C16, "gate backward: fp32 storage");
   const int rbase = __builtin_amdgcn_readfirstlane(rbase_);
   const float* biasp = bias_done ? nullptr : p.bias;
   constexpr int ES = C16 ? 2 : 4;
@@ -798,9 +867,7 @@ __device__ __forceinline__ void nt_epilogue_vec(ACC& acc, const NTParams& p, int
         s2.z = fmaf(q.z, z.z, s2.z); s2.w = fmaf(q.w, z.w, s2.w);
       } else if (EPI == EPI_GATE) {
         // F = relu(zf*s+t) * m,  m = 0.5 + 0.5*sigmoid(acc + b)     (src/model.py:51,54-55)
-        float4 m;
-        m.x = 0.5f + 0.5f / (1.f + __expf(-v.x)); m.y = 0.5f + 0.5f / (1.f + __expf(-v.y));
-        m.z = 0.5f + 0.5f / (1.f + __expf(-v.z)); m.w = 0.5f + 0.5f / (1.f + __expf(-v.w));
+        const float4 m = gate_m4(v);
         v.x = fmaxf(fmaf(z.x, es4.x, et4.x), 0.f) * m.x; v.y = fmaxf(fmaf(z.y, es4.y, et4.y), 0.f) * m.y;
         v.z = fmaxf(fmaf(z.z, es4.z, et4.z), 0.f) * m.z; v.w = fmaxf(fmaf(z.w, es4.w, et4.w), 0.f) * m.w;
         if ((p.flags & F_STORE_GATE) != 0) ev_store(rsC2, lr * rowC2 + vC, m);

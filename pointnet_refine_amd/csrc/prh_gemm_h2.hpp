@@ -389,6 +389,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_h2_kernel(const NTParams p,
     if (tid == 0)
       p.ws_a[blockIdx.x] = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])),
                                  fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));
+  } else if constexpr (EPI == EPI_GATE_BWD) {
+    // the z rows of the ordered partial sums live behind the eight waves' accumulator scratch (the stages are free)
+    static_assert(8 * (32 + 16) * EPI_LDW * 4 <= H2_LDS, "gate-backward scratch must fit in the stage buffers");
+    nt_epilogue_vec<EPI, 4>(acc, p, m0 + wm, n0 + wn, tile_m * 2 + (wave >> 2), lane,
+                            reinterpret_cast<float*>(smem) + wave * (32 * EPI_LDW), false, nullptr,
+                            reinterpret_cast<float*>(smem) + 8 * (32 * EPI_LDW) + wave * (16 * EPI_LDW));
   } else {
     nt_epilogue_vec<EPI, 4>(acc, p, m0 + wm, n0 + wn, tile_m * 2 + (wave >> 2), lane,
                             reinterpret_cast<float*>(smem) + wave * (32 * EPI_LDW));

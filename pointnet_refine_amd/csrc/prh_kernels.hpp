@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "prh_gemm.hpp"         // gate_bwd_elem
+
 namespace prh {
 
 // ---------------------------------------------------------------------------------------
@@ -401,11 +403,9 @@ __global__ __launch_bounds__(256) void combine_bwd_kernel(
         if (argmax[(size_t)b * C + col] == n) d += d_gfeat[(size_t)b * 2 * C + col];
       }
       const float z = zf[off], m = gate[off];
-      const float pre = fmaf(z, sc, sh);
-      const float r = fmaxf(pre, 0.f);
-      const float sig = 2.f * m - 1.f;
-      const float dy = pre > 0.f ? d * m : 0.f;
-      gate[off] = d * r * 0.5f * sig * (1.f - sig);
+      float dy, dg;
+      gate_bwd_elem(d, z, m, sc, sh, dy, dg);      // shared with the recomputing epilogue (EPI_GATE_BWD)
+      gate[off] = dg;
       dy_out[off] = dy;
       s1 += dy;
       s2 = fmaf(dy, z, s2);

@@ -261,6 +261,12 @@ inline bool nt_use_s3(Cores c, int M, int N, int K) {
   return c.split() && K >= 64 && K <= 4096 && N >= 128 && M >= 512 &&
          (long)cdiv(M, S3_BM) * cdiv(N, S3_BN) >= 32;
 }
+// Does the intensity-gate launch <PRO_GATE1, EPI_GATE> over [P, od] (K = 64) land on the second-generation
+// split-fp16 core with the vector epilogue?  Only there can the backward compute the gate again
+// (<PRO_GATE1, EPI_GATE_BWD>) with the forward's bits; mirrors the conditions of launch_nt_core.
+inline bool gate_on_h2(Cores c, int P, int od, int in_channel) {
+  return c.mode == 3 && c.core == 3 && nt_use_s3(c, P, od, 64) && (od & 3) == 0 && in_channel <= 65536;
+}
 inline bool tn_use_s3(Cores c, int P, int Mo, int Ni) { return c.split() && Mo >= 128 && Ni >= 64 && P >= 8192; }
 
 // dy <- dz in place (split-fp16 mode), largest |dz| into hdr[0]; hdr: S3_HDR_FLOATS floats
@@ -491,11 +497,11 @@ int launch_nt_core(Cores c, NTParams& p, hipStream_t st, StatInfo* si, float* am
   char nm[64];
   // algorithmic traffic: A (+A2) read once, C written once (+E1/C_old reads), W read once
   const double by = 4.0 * ((double)p.M * p.K * (PRO == PRO_BNBWD ? 2 : (PRO == PRO_GATE1 ? 0 : 1)) +
-                           (double)p.M * p.N * (EPI == EPI_GATE ? 3 : (EPI == EPI_DGRAD ? 2 : 1)) +
+                           (double)p.M * p.N * (EPI == EPI_GATE_BWD ? 4 : (EPI == EPI_GATE ? 3 : (EPI == EPI_DGRAD ? 2 : 1))) +
                            (double)p.N * p.K);
   {
     if (p.wprep != nullptr && nt_use_s3(c, p.M, p.N, p.K) && p.lda <= 65536 && p.lda2 <= 65536 &&
-        !(EPI == EPI_GATE && ((p.N | (int)p.ldc | (int)p.lde1 | (int)p.ldc2) & 3) != 0)) {
+        !((EPI == EPI_GATE || EPI == EPI_GATE_BWD) && ((p.N | (int)p.ldc | (int)p.lde1 | (int)p.ldc2) & 3) != 0)) {
       const int KT = cdiv(p.K, S3_BK), NTl = cdiv(p.N, S3_BN);
       const long th = (long)NTl * 256 * KT * 2;
       float* hdr = reinterpret_cast<float*>(p.wprep);
@@ -551,40 +557,48 @@ int launch_nt_core(Cores c, NTParams& p, hipStream_t st, StatInfo* si, float* am
           return PRH_OK;
         }
       }
-      hipLaunchKernelGGL(prep_weights_s3_kernel, dim3((unsigned)cdiv(th, 256)), dim3(256), 0, st,
-                         p.W, p.N, p.K, p.ldw, 0, p.wprep + S3_WHDR, c.core == 3 ? p.amaxW : nullptr);
-      LAUNCH_CHECK();
-      p.tiles_n = NTl;
-      const long tiles = (long)NTl * cdiv(p.M, S3_BM);
-      static const int attr_rc = allow_big_lds(gemm_nt_s3_kernel<PRO, EPI, 3>, gemm_nt_s3_kernel<PRO, EPI, 1>,
-                                               gemm_nt_s3_kernel<PRO, EPI, 2>);
-      if (attr_rc != PRH_OK) return attr_rc;
-      snprintf(nm, sizeof(nm), "gemm_nt_%s<%d,%d> K=%d N=%d", c.core == 3 ? "h2g1" : c.tag(), PRO, EPI, p.K, p.N);
-      ProfScope ps(nm, 2.0 * p.M * (double)p.N * p.K, by, st);
-      switch (c.core) {
-        case 2: launch_nt_s3<PRO, EPI, 1>(p, tiles, img, st); break;
-        case 3: launch_nt_s3<PRO, EPI, 2>(p, tiles, img, st); break;
-        default: launch_nt_s3<PRO, EPI, 3>(p, tiles, img, st);
+      if constexpr (EPI != EPI_GATE_BWD) {
+        hipLaunchKernelGGL(prep_weights_s3_kernel, dim3((unsigned)cdiv(th, 256)), dim3(256), 0, st,
+                           p.W, p.N, p.K, p.ldw, 0, p.wprep + S3_WHDR, c.core == 3 ? p.amaxW : nullptr);
+        LAUNCH_CHECK();
+        p.tiles_n = NTl;
+        const long tiles = (long)NTl * cdiv(p.M, S3_BM);
+        static const int attr_rc = allow_big_lds(gemm_nt_s3_kernel<PRO, EPI, 3>, gemm_nt_s3_kernel<PRO, EPI, 1>,
+                                                 gemm_nt_s3_kernel<PRO, EPI, 2>);
+        if (attr_rc != PRH_OK) return attr_rc;
+        snprintf(nm, sizeof(nm), "gemm_nt_%s<%d,%d> K=%d N=%d", c.core == 3 ? "h2g1" : c.tag(), PRO, EPI, p.K, p.N);
+        ProfScope ps(nm, 2.0 * p.M * (double)p.N * p.K, by, st);
+        switch (c.core) {
+          case 2: launch_nt_s3<PRO, EPI, 1>(p, tiles, img, st); break;
+          case 3: launch_nt_s3<PRO, EPI, 2>(p, tiles, img, st); break;
+          default: launch_nt_s3<PRO, EPI, 3>(p, tiles, img, st);
+        }
+        LAUNCH_CHECK();
+        if (si) { si->count = 2 * cdiv(p.M, S3_BM); si->rows = 128; }
+        return PRH_OK;
       }
-      LAUNCH_CHECK();
-      if (si) { si->count = 2 * cdiv(p.M, S3_BM); si->rows = 128; }
-      return PRH_OK;
     }
   }
-  if constexpr (PRO == PRO_NONE && EPI == EPI_BIAS) {
-    if (small_nt_ok(p, false)) return launch_small<false>(p, st);
+  // the gate backward exists on the second-generation split-fp16 core only (gate_on_h2 says when): its
+  // caller runs combine_bwd_kernel on a stored gate everywhere else
+  if constexpr (EPI == EPI_GATE_BWD) {
+    return fail(PRH_ERR_ARG, "gemm_nt: the gate-recompute backward needs the split-fp16 core (M=%d N=%d)", p.M, p.N);
+  } else {
+    if constexpr (PRO == PRO_NONE && EPI == EPI_BIAS) {
+      if (small_nt_ok(p, false)) return launch_small<false>(p, st);
+    }
+    p.tiles_n = cdiv(p.N, BN);
+    const long tiles = (long)p.tiles_n * cdiv(p.M, BM);
+    snprintf(nm, sizeof(nm), "gemm_nt<%d,%d> K=%d N=%d", PRO, EPI, p.K, p.N);
+    ProfScope ps(nm, 2.0 * p.M * (double)p.N * p.K, by, st);
+    if (p.N <= 64)      // one column tile: 64 x 32 wave tiles
+      hipLaunchKernelGGL((gemm_nt_kernel<PRO, EPI, true>), dim3((unsigned)tiles), dim3(256), 0, st, p);
+    else
+      hipLaunchKernelGGL((gemm_nt_kernel<PRO, EPI>), dim3((unsigned)tiles), dim3(256), 0, st, p);
+    LAUNCH_CHECK();
+    if (si) { si->count = 2 * cdiv(p.M, BM); si->rows = 64; }
+    return PRH_OK;
   }
-  p.tiles_n = cdiv(p.N, BN);
-  const long tiles = (long)p.tiles_n * cdiv(p.M, BM);
-  snprintf(nm, sizeof(nm), "gemm_nt<%d,%d> K=%d N=%d", PRO, EPI, p.K, p.N);
-  ProfScope ps(nm, 2.0 * p.M * (double)p.N * p.K, by, st);
-  if (p.N <= 64)      // one column tile: 64 x 32 wave tiles
-    hipLaunchKernelGGL((gemm_nt_kernel<PRO, EPI, true>), dim3((unsigned)tiles), dim3(256), 0, st, p);
-  else
-    hipLaunchKernelGGL((gemm_nt_kernel<PRO, EPI>), dim3((unsigned)tiles), dim3(256), 0, st, p);
-  LAUNCH_CHECK();
-  if (si) { si->count = 2 * cdiv(p.M, BM); si->rows = 64; }
-  return PRH_OK;
 }
 
 // amax_out: the largest |C| of the launch is valid there on return - from the epilogue where the core has that
@@ -1648,6 +1662,41 @@ static int check_encoder(const prh_encoder_params* prm) {
   return PRH_OK;
 }
 
+// Step (1) of the encoder backward, through F = relu(bn(zf)) * m and the pooling: dy_f -> dyf (may be d_fused
+// itself), dG -> gate, BatchNorm-backward partials [cdiv(P,64)][od] -> ws_a / ws_b.
+//   recompute == 0: `gate` holds the forward's m; combine_bwd_kernel reads it and writes dG over it.
+//   recompute != 0: `gate` holds nothing.  The forward's gate launch runs again with the backward epilogue, which
+//     forms m from the accumulators (same core, weight image and operand scales: same bits), turns dyf from d
+//     into dy_f in place, writes dG and combine_bwd_kernel's partials in its order.  Needs gate_on_h2() and no
+//     pooled gradient.
+int gate_combine_backward(Cores c, const float* inten, int C, int B, int N, int od, const float* gate_w1,
+                          const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* z_fus,
+                          const float* es, const float* et, const float* d_fused, const float* d_gfeat,
+                          const int32_t* argmax, float* gate, int recompute, float* dyf, float* ws_a, float* ws_b,
+                          char* wprep, hipStream_t st) {
+  const int P = B * N;
+  if (!recompute) {
+    hipLaunchKernelGGL(combine_bwd_kernel, dim3(cdiv(P, 64), cdiv(od, 64)), dim3(256), 0, st, d_fused, d_gfeat,
+                       argmax, z_fus, gate, es, et, P, N, od, dyf, ws_a, ws_b);
+    LAUNCH_CHECK();
+    return PRH_OK;
+  }
+  if (dyf != d_fused)
+    HIP_TRY(hipMemcpyAsync(dyf, d_fused, (size_t)P * od * sizeof(float), hipMemcpyDeviceToDevice, st));
+  NTParams p; memset(&p, 0, sizeof(p));
+  p.A = inten; p.lda = C; p.pa = gate_w1; p.pb = gate_b1;
+  p.W = gate_w2; p.ldw = 64; p.K = 64; p.M = P; p.N = od; p.bias = gate_b2;
+  p.E1 = z_fus; p.lde1 = od; p.es = es; p.et = et;
+  p.C = dyf; p.ldc = od; p.C2 = gate; p.ldc2 = od;
+  p.ws_a = ws_a; p.ws_b = ws_b; p.wprep = wprep;
+  return launch_nt<PRO_GATE1, EPI_GATE_BWD>(c, p, st);
+}
+
+int prh_encoder_gate_recompute(int B, int N, int in_channel, int out_dim, int want_global) {
+  if (B <= 0 || N <= 0 || in_channel < 4 || out_dim <= 0 || (long)B * N > 2000000000L) return 0;
+  return (!want_global && gate_on_h2(cores_of(gemm_mode()), B * N, out_dim, in_channel)) ? 1 : 0;
+}
+
 int prh_encoder_forward(const prh_encoder_params* prm, const float* ctx, int B, int N,
                         int training, float momentum, float eps, float* fused, float* gfeat,
                         const prh_encoder_saved* sv, void* workspace, size_t workspace_bytes,
@@ -1758,10 +1807,12 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
 
   // (1) through F = relu(bn(zf)) * m and the pooling: dy_f -> dyf (workspace),
   //     dG -> saved.gate (in place), fusion-BN backward partials
-  hipLaunchKernelGGL(combine_bwd_kernel, dim3(cdiv(P, 64), cdiv(od, 64)), dim3(256), 0, st, d_fused,
-                     d_gfeat, sv->argmax, sv->z_fus, sv->gate, sv->bn_scale + cat,
-                     sv->bn_shift + cat, P, N, od, dyf, w.ws_a, w.ws_b);
-  LAUNCH_CHECK();
+  if (sv->gate_recompute && (d_gfeat != nullptr || !gate_on_h2(c, P, od, C)))
+    return fail(PRH_ERR_ARG, "encoder_backward: saved.gate_recompute without prh_encoder_gate_recompute() "
+                             "(pooled gradient, GEMM mode or shape)");
+  TRY(gate_combine_backward(c, ctx + 3, C, B, N, od, prm->gate_w1, prm->gate_b1, prm->gate_w2, prm->gate_b2, sv->z_fus,
+                            sv->bn_scale + cat, sv->bn_shift + cat, d_fused, d_gfeat, sv->argmax, sv->gate,
+                            sv->gate_recompute, dyf, w.ws_a, w.ws_b, w.wprep, st));
   TRY(reduce_bn_stage1(w.ws_a, w.ws_b, cdiv(P, 64), (long)od, od, 64, P, 0, w.stat2, st));
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(od, 128)), dim3(128), 0, st, w.stat2, P, od,
                      prm->fusion.gamma, sv->bn_mean + cat, sv->bn_rstd + cat,
@@ -3825,6 +3876,25 @@ int prh_test_gemm_nt(const float* a, const float* w, float* c, int m, int n, int
   if (workspace != nullptr && workspace_bytes >= s3_weight_bytes(n, k) + 256)
     p.wprep = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   return launch_nt<PRO_NONE, EPI_BIAS>(cores_of(gemm_mode()), p, (hipStream_t)stream);
+}
+size_t prh_test_gate_backward_workspace_bytes(int out_dim) { return s3_weight_bytes(out_dim, 64) + 512; }
+int prh_test_gate_backward(const float* ctx, int B, int N, int in_channel, int out_dim, const float* gate_w1,
+                           const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* z_fus,
+                           const float* bn_scale, const float* bn_shift, float* d_fused, float* gate, int recompute,
+                           float* ws_a, float* ws_b, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  HIP_TRY(hipSetDevice(device));
+  if (!ctx || !gate_w1 || !gate_b1 || !gate_w2 || !gate_b2 || !z_fus || !bn_scale || !bn_shift || !d_fused || !gate ||
+      !ws_a || !ws_b || B <= 0 || N <= 0 || in_channel < 4 || out_dim <= 0 || (long)B * N > 2000000000L)
+    return fail(PRH_ERR_ARG, "test_gate_backward: bad argument");
+  const Cores c = cores_of(gemm_mode());
+  if (recompute && !gate_on_h2(c, B * N, out_dim, in_channel))
+    return fail(PRH_ERR_ARG, "test_gate_backward: recompute without prh_encoder_gate_recompute()");
+  if (workspace == nullptr || workspace_bytes < prh_test_gate_backward_workspace_bytes(out_dim))
+    return fail(PRH_ERR_WORKSPACE, "test_gate_backward: workspace too small");
+  char* wprep = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  return gate_combine_backward(c, ctx + 3, in_channel, B, N, out_dim, gate_w1, gate_b1, gate_w2, gate_b2, z_fus, bn_scale,
+                               bn_shift, d_fused, nullptr, nullptr, gate, recompute, d_fused, ws_a, ws_b, wprep,
+                               (hipStream_t)stream);
 }
 int prh_test_xcc_map(int blocks, int lds_bytes, int* out, int device, void* stream) {
   HIP_TRY(hipSetDevice(device));

@@ -817,7 +817,10 @@ class EncoderFn(torch.autograd.Function):
             return EncoderFn._forward_bf16(ctx, x, want_global, training, momentum, eps, buffers, params, p2, need_bwd)
         z_cat = torch.empty((P, cat), dtype=torch.float32, device=dev)
         z_fus = torch.empty((P, out_dim), dtype=torch.float32, device=dev)
-        gate = torch.empty((P, out_dim), dtype=torch.float32, device=dev) if need_bwd else None
+        # the backward computes the gate again where the library can (GATE_RECOMPUTE): nothing to store then
+        recompute = bool(need_bwd and GATE_RECOMPUTE and
+                         L.lib().prh_encoder_gate_recompute(B, N, Cin, out_dim, int(bool(want_global))))
+        gate = torch.empty((P, out_dim), dtype=torch.float32, device=dev) if (need_bwd and not recompute) else None
         coef = torch.empty((5, cat + out_dim), dtype=torch.float32, device=dev)   # row 4: operand maxima
         fused = torch.empty((B, N, out_dim), dtype=torch.float32, device=dev)
         gfeat = torch.empty((B, 2 * out_dim), dtype=torch.float32, device=dev) if want_global else None
@@ -833,8 +836,10 @@ class EncoderFn(torch.autograd.Function):
                                             ws.numel(), dev.index, _stream(dev)),
                 "prh_encoder_forward")
         if need_bwd:
-            ctx.save_for_backward(x, z_cat, z_fus, gate, coef, argmax if argmax is not None else coef, *p2)
+            ctx.save_for_backward(x, z_cat, z_fus, gate if gate is not None else coef, coef,
+                                  argmax if argmax is not None else coef, *p2)
             ctx.has_argmax = argmax is not None
+            ctx.gate_recompute = recompute
             ctx.training = int(training)
             ctx.gemm_mode = gemm_mode
             ctx.pshapes = [t.shape for t in params]
@@ -929,12 +934,17 @@ class EncoderFn(torch.autograd.Function):
             return EncoderFn._backward_bf16(ctx, d_gfeat, d_fused)
         saved = ctx.saved_tensors
         x, z_cat, z_fus, gate, coef, argmax = saved[:6]
-        if ENCODER_RETAIN_GRAPH:
-            gate = gate.clone()          # the only saved buffer the backward writes (dG in place)
         p2 = list(saved[6:])
         dev = x.device
         B, N, Cin = x.shape
         out_dim = p2[8].shape[0]
+        if ctx.gate_recompute:
+            if d_gfeat is not None or not L.lib().prh_encoder_gate_recompute(B, N, Cin, out_dim, 0):
+                raise RuntimeError("encoder backward: the forward kept no gate buffer (ops.GATE_RECOMPUTE) and the "
+                                   "GEMM mode has changed since; keep the mode, or set ops.GATE_RECOMPUTE = False")
+            gate = torch.empty((B * N, out_dim), dtype=torch.float32, device=dev)     # dG only
+        elif ENCODER_RETAIN_GRAPH:
+            gate = gate.clone()          # the only saved buffer the backward writes (dG in place)
         # the incoming d_fused (LineRefineNet: context_proj's dgrad output, which nobody else holds) becomes the
         # fusion layer's gradient scratch instead of 4 KB per point of workspace - unless it is a view, the
         # pooled gradient is there as well, or a second backward was asked for
@@ -951,7 +961,7 @@ class EncoderFn(torch.autograd.Function):
         same_mode = ctx.training and ctx.gemm_mode == L.lib().prh_get_gemm_mode()
         sv = L.EncoderSaved(_p(z_cat), _p(z_fus), _p(gate), _p(coef[0]), _p(coef[1]), _p(coef[2]),
                             _p(coef[3]), _p(argmax) if ctx.has_argmax else None,
-                            _p(coef[4]) if same_mode else None)
+                            _p(coef[4]) if same_mode else None, int(ctx.gate_recompute))
         gb = [_grad_buf(ctx.sinks[i], t.shape, dev) for i, t in enumerate(p2)]
         g = [b_[0] for b_ in gb]
         gr = L.EncoderGrads()
@@ -972,6 +982,10 @@ class EncoderFn(torch.autograd.Function):
 
 
 ENCODER_RETAIN_GRAPH = False
+# The encoder backward computes the intensity gate again (the forward's gate GEMM with a backward epilogue, bit
+# for bit the forward's gate) instead of keeping it from the forward: 4 KB per point neither written nor read
+# back, where the library says it can (prh_encoder_gate_recompute).  False: the stored-gate path everywhere.
+GATE_RECOMPUTE = True
 
 
 def allow_encoder_retain_graph(flag: bool = True):
