@@ -350,7 +350,9 @@ int prh_linear_backward_amax(const float* x, long ldx, const float* w, const flo
 
 /* Stack of <= PRH_MAX_LAYERS shared-MLP layers applied to x [P,cin0]:
  * LineRefineNet.point_mlp, src/model.py:150-159,200-201 (relu_last = 0).
- *   z_cat [P, sum(cout)] pre-BN outputs (kept for backward), y [P, cout_last]. */
+ *   z_cat [P, sum(cout)] pre-BN outputs (kept for backward), y [P, cout_last].
+ * A workspace that is NULL or smaller than prh_mlp_stack_workspace_bytes reports is refused
+ * (PRH_ERR_WORKSPACE) by both entry points. */
 size_t prh_mlp_stack_workspace_bytes(int P, int n_layers, const prh_bn_layer* layers);
 int prh_mlp_stack_forward(const prh_bn_layer* layers, int n_layers, int relu_last,
                           const float* x, int P, int training, float momentum, float eps,

@@ -1579,7 +1579,9 @@ int prh_mlp_stack_forward(const prh_bn_layer* layers, int n_layers, int relu_las
   Arena a(workspace, workspace_bytes);
   MlpWS m;
   mlp_carve(c, a, m, P, layers, n_layers);
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "mlp_stack_forward: workspace too small (%zu bytes)", workspace_bytes);
+  // present, and no smaller than prh_mlp_stack_workspace_bytes reports (the carve plus 256 bytes): lin16_ws_ok's rule
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "mlp_stack_forward: workspace too small (%zu bytes)", workspace_bytes);
   StackWS& w = m.w;
   const long ldz = d.off[n_layers];
   TRY(stack_forward(c, layers, n_layers, x, P, training, momentum, eps, z_cat, ldz, bn_scale,
@@ -1612,7 +1614,8 @@ int prh_mlp_stack_backward(const prh_bn_layer* layers, int n_layers, int relu_la
   StackBwdScratch& sc = m.sc;
   const long ldz = d.off[L];
   float* dy_cat = m.dy_cat;
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "mlp_stack_backward: workspace too small (%zu bytes)", workspace_bytes);
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "mlp_stack_backward: workspace too small (%zu bytes)", workspace_bytes);
   if (d.cin0p != d.cin0) {
     TRY(copy_cols(x, d.cin0, d.cin0, w.xpad, d.cin0p, d.cin0p, (size_t)P, st));
     TRY(copy_cols(layers[0].w, d.cin0, d.cin0, w.w0pad, d.cin0p, d.cin0p, (size_t)layers[0].cout, st));
