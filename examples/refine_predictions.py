@@ -5,7 +5,7 @@ frames into lanes and fused into one polyline per lane in the drive frame
 
     python examples/refine_predictions.py DRIVE_DIR RESULTS_JSON --checkpoint CKPT --out MAP.json
                                           [--gt GT_JSON] [--png DIR] [--batched] [--device-sync]
-                                          [--support [--intensity-floor F]]
+                                          [--support [--intensity-floor F]] [--lift [--lift-radius R]]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; RESULTS_JSON is the detector's output
 (predictions.load_results); MAP.json gets the fused map in the drive file layout
@@ -19,6 +19,9 @@ intensity first) and the markings counted by type; every cluster's figures and i
 dashed / none) go into MAP.json's attributes.
 --device-sync runs the linking's edges, clusters and arc synchronisation on the GPU as well
 (link.link_sync): the same map, without copying the candidate pairs' statistics to the host.
+--lift puts the detector's lines (z = 0) on the road before they are refined: the road height under
+every metre of every line is read from the frame's own cloud points within --lift-radius R
+(pointnet_refine_amd/ground.py), and one GROUND LIFT line says how many lines and stations found ground.
 --png DIR draws the fused map over a BEV intensity map of the merged cloud (bev.py).
 
 Without --checkpoint the model carries deterministic procedural weights (the run then exercises the
@@ -81,14 +84,20 @@ def main():
     ap.add_argument("--device-sync", action="store_true", help="piece linking steps 5-6 on the GPU (the same map)")
     ap.add_argument("--support", action="store_true", help="score the map against the cloud (no GT needed)")
     ap.add_argument("--intensity-floor", type=float, default=0.0)
+    ap.add_argument("--lift", action="store_true", help="put the detector's lines on the road read from the cloud")
+    ap.add_argument("--lift-radius", type=float, default=0.5)
     args = ap.parse_args()
 
     from pointnet_refine_amd import drive, fuse, link
     res = link.refine_predictions(load_model(args.checkpoint), args.drive_dir, args.results_json, seed=args.seed,
                                   step=args.step, gate=args.gate, min_pieces=args.min_pieces, batched=args.batched,
                                   support=args.support, intensity_floor=args.intensity_floor,
-                                  device_sync=args.device_sync)
+                                  device_sync=args.device_sync, lift=args.lift, lift_radius=args.lift_radius)
     rep = res["report"]
+    if args.lift:
+        print(f"GROUND LIFT  {rep['lift_lines_lifted']} of {rep['lift_lines']} lines lifted "
+              f"({rep['lift_lines_unlifted']} left at the detector's z)   {rep['lift_stations_without_ground']} of "
+              f"{rep['lift_stations']} stations without ground")
     print(f"{rep['slices']} frames, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['candidates']} candidate pairs, {rep['edges']} edges, {rep['clusters']} clusters, "
           f"{rep['clusters_kept']} kept ({rep['pieces_unlinked']} pieces unlinked), "

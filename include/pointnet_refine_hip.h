@@ -1017,6 +1017,89 @@ int prh_support_accumulate(const float* cloud, long long n_points, double origin
                            int n_lines, const long long* node_offsets, long long n_nodes, double step, double r2,
                            double intensity_floor, long long* acc, int device, void* stream);
 
+/* Ground lift - the rule.
+ * The height of the road surface under an xy, read from the cloud: the detector's lines come with
+ * z = 0 (tools/generate_inference_data_vma.py:262), the context builder's tube is 3-D, so a line
+ * has to be put on the road before the tube can hold anything.  The conventions are those of "Map
+ * fusion - the rule" and "Cloud support - the rule": fp64 throughout, one rounding per operation,
+ * no contraction, and every constant that decides membership is computed once on the host and
+ * passed in; the same bits go to the device and to the oracle (tests/_ground_oracle.py).
+ * Inputs.  points [T,4] = x y z intensity in the ego frame of their slice, float64 (is_double != 0,
+ * what drive.slice_cloud returns) or float32; a float32 coordinate is converted to fp64 first, which
+ * is exact.  slice_offsets [S+1] int64: slice s owns rows slice_offsets[s] .. slice_offsets[s+1],
+ * fewer than 2^31 of them.  queries [Q,2] fp64 xy, finite, |coordinate| <= 1e6, with query_offsets
+ * [S+1] int64: the queries are grouped by slice and a query sees only its own slice's points.
+ * Parameters.  radius (default 0.5 m, 0 < radius <= 4) enters as r2 = radius * radius; z_lo
+ * (default -8) and bin (default 0.0625, exact in binary) and n_bins (default 256, 1 <= n_bins <=
+ * prh_ground_max_bins() = 256) lay the height histogram over [z_lo, z_lo + n_bins * bin), which
+ * must lie inside [-256, 256]; min_points (default 5, >= 1); peak_num / peak_den (default 1 / 2,
+ * integers, 1 <= peak_num <= peak_den <= 65536).
+ * Per (query, point of the same slice).  A point with a non-finite x, y or z is skipped.  dx = x -
+ * qx, dy = y - qy, d2 = dx * dx + dy * dy; the pair is a hit iff d2 <= r2: there is no sqrt.  The
+ * hit's bin is b = (long long)floor((z - z_lo) / bin); whether 0 <= b < n_bins is decided on the
+ * floor in fp64, before the conversion.  A hit with b < 0 or b >= n_bins counts in `hits` and
+ * nowhere else.
+ * Per query.
+ * 1. hist[b] = the hits of bin b, 0 <= b < n_bins.
+ * 2. c3[b] = hist[b-1] + hist[b] + hist[b+1], a neighbour outside 0 .. n_bins - 1 taken as 0.
+ * 3. peak = max c3.
+ * 4. If peak < min_points there is no ground: height = NaN (the quiet NaN 0x7ff8000000000000), bin
+ *    = -1, count = 0.
+ * 5. Otherwise thr = max(min_points, ceil(peak * peak_num / peak_den)), in integers.
+ * 6. g = the lowest b with c3[b] >= thr.
+ * 7. While g + 1 < n_bins and c3[g+1] > c3[g]: g = g + 1.
+ * 8. That is the lowest mode that holds at least peak_num / peak_den of the strongest one: the road
+ *    under a vehicle, a sign gantry or a bridge wins unless the thing above returns more than
+ *    peak_den / peak_num times the road's points.
+ * 9. Over the hits with max(g - 1, 0) <= b <= min(g + 1, n_bins - 1): qz = (long long)rint(z *
+ *    65536) (half to even), sum = the sum of qz and n = their number, both in integers; height =
+ *    ((double)sum / (double)n) / 65536.0.  n = c3[g] >= 1.
+ * 10. Outputs per query: height fp64, count = n int32, hits int32 (every hit, binned or not), bin =
+ *    g int32.
+ * All sums are integers, so the result does not depend on the order of the points, on how they are
+ * binned into cells or on the launch shape: it is bitwise reproducible by construction.  Overflow:
+ * a summed z lies inside [-256, 256], so |qz| <= 2^24 = 2^20 * 16, and n < 2^31, so |sum| < 2^55.
+ *
+ * The grid changes the cost, never the result.  reach = radius + 1e-6, computed on the host, covers
+ * the rounding of d2: a hit has |x - qx| <= reach and |y - qy| <= reach as real numbers (|q| <=
+ * 1e6, so an endpoint's rounding is below 1.2e-10).  Slice s has a uniform grid of square cells,
+ * `cell` metres wide (cell >= radius, one value for the call): grid_origin [S,2] fp64 = x0 y0 =
+ * (min qx - reach, min qy - reach) over the slice's queries, grid_shape [S,2] int32 = nx ny with nx
+ * = floor(((max qx + reach) - x0) / cell) + 1 (a slice without a query: 0 0), cell_base [S] int64:
+ * cell (ix, iy) of slice s is number cell_base[s] + iy * nx + ix of n_cells < 2^31 in all.  ix =
+ * floor((x - x0) / cell) in fp64, the same monotone expression on host and device.
+ *   prh_ground_bin_count  cell_counts [n_cells] int32: the points of each cell.  A point outside its
+ *                         slice's grid, or with a non-finite x, y or z, is dropped: it can be no hit.
+ *   prh_ground_bin_write  rows [capacity] int32: with cell_offsets [n_cells+1] int64 the exclusive
+ *                         prefix of cell_counts (the caller scans), rows[cell_offsets[c] ..
+ *                         cell_offsets[c+1]] are the rows, counted from the slice's first, of the
+ *                         points of cell c, in the order of arrival (an atomic cursor in the
+ *                         workspace: the rule does not see the order).  Same arguments as the count.
+ *   prh_ground_query      one wave per query: it walks the cells from floor(((q - reach) - x0) /
+ *                         cell) to floor(((q + reach) - x0) / cell) in x and y, clipped to the grid -
+ *                         by monotonicity every hit's cell is among them; 3 x 3 cells when cell >=
+ *                         radius + 1e-6, at most 4 x 4 down to cell = radius - twice: once for the
+ *                         histogram (integer LDS atomics), once for sum and n.  No float atomics.
+ * points must be aligned to two coordinates (16 bytes for fp64, 8 for float32).  PRH_ERR_ARG for a
+ * parameter outside the limits above; PRH_ERR_WORKSPACE below prh_ground_bin_workspace_bytes. */
+int prh_ground_max_bins(void);
+size_t prh_ground_bin_workspace_bytes(long long n_cells);
+int prh_ground_bin_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                         long long n_points, const double* grid_origin, const int* grid_shape,
+                         const long long* cell_base, long long n_cells, double cell, int* cell_counts, int device,
+                         void* stream);
+int prh_ground_bin_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                         long long n_points, const double* grid_origin, const int* grid_shape,
+                         const long long* cell_base, long long n_cells, double cell, const long long* cell_offsets,
+                         int* rows, long long capacity, void* workspace, size_t workspace_bytes, int device,
+                         void* stream);
+int prh_ground_query(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long n_points,
+                     const double* queries, const long long* query_offsets, long long n_queries,
+                     const double* grid_origin, const int* grid_shape, const long long* cell_base, long long n_cells,
+                     double cell, const long long* cell_offsets, const int* rows, long long n_rows, double r2,
+                     double reach, double z_lo, double bin, int n_bins, int min_points, int peak_num, int peak_den,
+                     double* height, int* count, int* hits, int* bin_index, int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

@@ -8,9 +8,11 @@ from .model import (DetrTransformerDecoderLayer, LineRefineNet, MultiScalePointN
 from .metrics import (calibrate_alignment, calibrate_alignments, evaluate_scene, evaluate_scenes,  # noqa: F401
                       line_metrics, shift_sweep, shift_sweep_ragged)
 from .support import map_support, marking_attributes, node_support  # noqa: F401
+from .ground import ground_heights, lift_lines, line_stations  # noqa: F401
 
 __all__ = ["LineRefineNet", "MultiScalePointNetEncoder", "PositionalEncoding",
            "DetrTransformerDecoderLayer",
            "line_metrics", "shift_sweep", "calibrate_alignment", "evaluate_scene",
            "shift_sweep_ragged", "calibrate_alignments", "evaluate_scenes",
-           "node_support", "map_support", "marking_attributes"]
+           "node_support", "map_support", "marking_attributes",
+           "ground_heights", "line_stations", "lift_lines"]

@@ -103,6 +103,8 @@ EXPORTS = [
     "prh_link_cum", "prh_link_edges_blocks", "prh_link_edges", "prh_link_edges_compact", "prh_link_label_round",
     "prh_link_tree_init", "prh_link_tree_level",
     "prh_support_max_cells", "prh_support_accumulate",
+    "prh_ground_max_bins", "prh_ground_bin_workspace_bytes", "prh_ground_bin_count", "prh_ground_bin_write",
+    "prh_ground_query",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -466,6 +468,19 @@ def _bind(lib):
     lib.prh_test_reduce_act_amax_workspace_bytes.argtypes = []
     lib.prh_test_reduce_act_amax.restype = i
     lib.prh_test_reduce_act_amax.argtypes = [vp, vp, i, lg, i, vp, vp, vp, vp, sz, i, vp]
+    if not hasattr(lib, "prh_ground_query"):
+        return lib      # an older build under PRH_LIB_PATH (A/B runs): it has no ground lift
+    lib.prh_ground_max_bins.restype = i
+    lib.prh_ground_max_bins.argtypes = []
+    lib.prh_ground_bin_workspace_bytes.restype = sz
+    lib.prh_ground_bin_workspace_bytes.argtypes = [ll]
+    lib.prh_ground_bin_count.restype = i
+    lib.prh_ground_bin_count.argtypes = [vp, i, vp, i, ll, vp, vp, vp, ll, dbl, vp, i, vp]
+    lib.prh_ground_bin_write.restype = i
+    lib.prh_ground_bin_write.argtypes = [vp, i, vp, i, ll, vp, vp, vp, ll, dbl, vp, vp, ll, vp, sz, i, vp]
+    lib.prh_ground_query.restype = i
+    lib.prh_ground_query.argtypes = [vp, i, vp, i, ll, vp, vp, ll, vp, vp, vp, ll, dbl, vp, vp, ll, dbl, dbl, dbl, dbl, i, i,
+                                     i, i, vp, vp, vp, vp, i, vp]
     return lib
 
 

@@ -33,6 +33,7 @@
 #include "prh_link.hpp"
 #include "prh_link_sync.hpp"
 #include "prh_support.hpp"
+#include "prh_ground.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
@@ -3631,6 +3632,113 @@ int prh_support_accumulate(const float* cloud, long long n_points, double origin
                      dim3(SUPPORT_THREADS), 0, (hipStream_t)stream, (const float4*)cloud, n_points, origin_x, origin_y,
                      origin_z, grid, cell_offsets, (const int2*)cell_entries, line_vertices, line_offsets, line_cum,
                      node_offsets, n_lines, step, r2, intensity_floor, (unsigned long long*)acc);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ ground lift
+int prh_ground_max_bins(void) { return GROUND_MAX_BINS; }
+size_t prh_ground_bin_workspace_bytes(long long n_cells) {
+  return n_cells < 0 ? 0 : align_up((size_t)n_cells * sizeof(int), 256);
+}
+static int ground_check_grid(const char* what, const void* points, int is_double, const long long* slice_offsets,
+                             int n_slices, long long n_points, const double* grid_origin, const int* grid_shape,
+                             const long long* cell_base, long long n_cells, double cell) {
+  if (n_slices < 0 || n_points < 0 || n_cells < 0 || n_cells > 0x7fffffffll || n_points >= 256ll * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "%s: bad argument (at most 2^31 - 1 cells)", what);
+  if (!(cell > 0.0) || !(cell < 1e300)) return fail(PRH_ERR_ARG, "%s: cell must be positive and finite", what);
+  if (n_slices > 0 && (!slice_offsets || !grid_origin || !grid_shape || !cell_base))
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if (n_points > 0 && (!points || n_slices == 0)) return fail(PRH_ERR_ARG, "%s: points without a slice", what);
+  if (((uintptr_t)points & (is_double ? 15 : 7)) != 0)
+    return fail(PRH_ERR_ARG, "%s: points must be aligned to two coordinates (%d bytes)", what, is_double ? 16 : 8);
+  return PRH_OK;
+}
+int prh_ground_bin_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                         long long n_points, const double* grid_origin, const int* grid_shape,
+                         const long long* cell_base, long long n_cells, double cell, int* cell_counts, int device,
+                         void* stream) {
+  TRY_RC(ground_check_grid("ground_bin_count", points, is_double, slice_offsets, n_slices, n_points, grid_origin,
+                           grid_shape, cell_base, n_cells, cell));
+  if (n_cells == 0) return PRH_OK;
+  if (!cell_counts) return fail(PRH_ERR_ARG, "ground_bin_count: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(cell_counts, 0, (size_t)n_cells * sizeof(int), st));
+  if (n_points == 0) return PRH_OK;
+  const unsigned nblk = (unsigned)((n_points + GROUND_THREADS - 1) / GROUND_THREADS);
+  if (is_double)
+    hipLaunchKernelGGL((ground_bin_kernel<double, false>), dim3(nblk), dim3(GROUND_THREADS), 0, st, (const double*)points,
+                       slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell, cell_counts,
+                       (const long long*)nullptr, (int*)nullptr, 0ll);
+  else
+    hipLaunchKernelGGL((ground_bin_kernel<float, false>), dim3(nblk), dim3(GROUND_THREADS), 0, st, (const float*)points,
+                       slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell, cell_counts,
+                       (const long long*)nullptr, (int*)nullptr, 0ll);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_ground_bin_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                         long long n_points, const double* grid_origin, const int* grid_shape,
+                         const long long* cell_base, long long n_cells, double cell, const long long* cell_offsets,
+                         int* rows, long long capacity, void* workspace, size_t workspace_bytes, int device,
+                         void* stream) {
+  TRY_RC(ground_check_grid("ground_bin_write", points, is_double, slice_offsets, n_slices, n_points, grid_origin,
+                           grid_shape, cell_base, n_cells, cell));
+  if (capacity < 0) return fail(PRH_ERR_ARG, "ground_bin_write: bad capacity");
+  if (n_cells == 0 || n_points == 0 || capacity == 0) return PRH_OK;
+  if (!cell_offsets || !rows) return fail(PRH_ERR_ARG, "ground_bin_write: null pointer");
+  if (!workspace || workspace_bytes < prh_ground_bin_workspace_bytes(n_cells))
+    return fail(PRH_ERR_WORKSPACE, "ground_bin_write: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* cursor = (int*)workspace;
+  HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)n_cells * sizeof(int), st));
+  const unsigned nblk = (unsigned)((n_points + GROUND_THREADS - 1) / GROUND_THREADS);
+  if (is_double)
+    hipLaunchKernelGGL((ground_bin_kernel<double, true>), dim3(nblk), dim3(GROUND_THREADS), 0, st, (const double*)points,
+                       slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell, cursor,
+                       cell_offsets, rows, capacity);
+  else
+    hipLaunchKernelGGL((ground_bin_kernel<float, true>), dim3(nblk), dim3(GROUND_THREADS), 0, st, (const float*)points,
+                       slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell, cursor,
+                       cell_offsets, rows, capacity);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_ground_query(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long n_points,
+                     const double* queries, const long long* query_offsets, long long n_queries,
+                     const double* grid_origin, const int* grid_shape, const long long* cell_base, long long n_cells,
+                     double cell, const long long* cell_offsets, const int* rows, long long n_rows, double r2,
+                     double reach, double z_lo, double bin, int n_bins, int min_points, int peak_num, int peak_den,
+                     double* height, int* count, int* hits, int* bin_index, int device, void* stream) {
+  TRY_RC(ground_check_grid("ground_query", points, is_double, slice_offsets, n_slices, n_points, grid_origin, grid_shape,
+                           cell_base, n_cells, cell));
+  if (n_queries < 0 || n_queries >= 4ll * 0x7fffffff || n_rows < 0 || n_rows > n_points)
+    return fail(PRH_ERR_ARG, "ground_query: bad argument");
+  if (!(r2 > 0.0) || !(r2 <= 16.0) || !(reach > 0.0) || !(reach * reach >= r2) || !(reach <= 8.0))
+    return fail(PRH_ERR_ARG, "ground_query: 0 < radius <= 4 and radius <= reach <= 8");
+  if (n_bins < 1 || n_bins > GROUND_MAX_BINS || !(bin > 0.0) || !(z_lo >= -256.0) || !(z_lo + n_bins * bin <= 256.0))
+    return fail(PRH_ERR_ARG, "ground_query: 1 <= n_bins <= %d, bin > 0 and the histogram inside [-256, 256]",
+                GROUND_MAX_BINS);
+  if (min_points < 1 || peak_num < 1 || peak_num > peak_den || peak_den > 65536)
+    return fail(PRH_ERR_ARG, "ground_query: min_points >= 1 and 1 <= peak_num <= peak_den <= 65536");
+  if (n_queries == 0) return PRH_OK;
+  if (!queries || !query_offsets || n_slices == 0 || !height || !count || !hits || !bin_index ||
+      (n_cells > 0 && !cell_offsets) || (n_rows > 0 && !rows))
+    return fail(PRH_ERR_ARG, "ground_query: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  GroundParams prm{r2, reach, cell, z_lo, bin, n_bins, min_points, peak_num, peak_den};
+  const unsigned nblk = (unsigned)((n_queries + GROUND_WAVES - 1) / GROUND_WAVES);
+  if (is_double)
+    hipLaunchKernelGGL(ground_query_kernel<double>, dim3(nblk), dim3(GROUND_THREADS), 0, st, (const double*)points,
+                       slice_offsets, n_slices, queries, query_offsets, n_queries, grid_origin, grid_shape, cell_base,
+                       cell_offsets, rows, n_rows, n_cells, prm, height, count, hits, bin_index);
+  else
+    hipLaunchKernelGGL(ground_query_kernel<float>, dim3(nblk), dim3(GROUND_THREADS), 0, st, (const float*)points,
+                       slice_offsets, n_slices, queries, query_offsets, n_queries, grid_origin, grid_shape, cell_base,
+                       cell_offsets, rows, n_rows, n_cells, prm, height, count, hits, bin_index);
   LAUNCH_CHECK();
   return PRH_OK;
 }

@@ -460,7 +460,7 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
                        min_tube_points=F.MIN_TUBE_POINTS, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATIO,
                        min_pieces=MIN_PIECES, step=F.STEP, min_count=F.MIN_COUNT, max_gap=F.MAX_GAP, origin=None,
                        batched=False, support=False, support_radius=None, intensity_floor=0.0, device_sync=False,
-                       return_links=False):
+                       return_links=False, lift=False, lift_radius=0.5, lift_step=1.0):
     """A detector run refined into one drive-frame map, with no GT.
 
     drive_dir holds pose/*.json and merged.pcd; results_json is the detector's output
@@ -472,6 +472,10 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     links and fuses the rest.  batched=True replaces the per-frame loop by one
     io.scene_offsets_ragged call over all frames (fuse.refine_slices_batched), as in refine_drive.
     device_sync and return_links go to fuse_unmatched: the same map and report, steps 5-6 on the device.
+    lift=True puts the pixel_to_ego lines (z = 0) on the road first: one ground.lift_lines call over
+    all frames' slices (stations every lift_step metres, cloud points within lift_radius in xy), and
+    the lifted lines are the candidates; the report gains 'lift_lines', 'lift_lines_lifted',
+    'lift_lines_unlifted', 'lift_stations' and 'lift_stations_without_ground'.
 
     Returns {'fused' [per kept cluster], 'pieces' (P,M,3) float64 ego frame, 'piece_frame' (P,) the
     row of 'poses' each piece was seen from, 'piece_slice' (the same), 'pose_index' (per used frame
@@ -494,18 +498,23 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     pq = D.poses_xyzq(poses, chosen[with_pose]) if len(with_pose) else np.zeros((0, 7))
     pieces, piece_frame, sparse = [], [], 0
     cloud = None
+    lift_report = {"lines": 0, "lines_lifted": 0, "lines_unlifted": 0, "stations": 0, "stations_without_ground": 0}
     if len(with_pose):
         cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
         points, offsets, _ = D.slice_cloud(np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4), pq, segment_len,
                                            PR.RADIUS if radius is None else radius)
         off = offsets.cpu().numpy()
+        cands_all = [[PR.pixel_to_ego(px) for px in frames[n]["pixels"]] for n in with_pose]
+        if lift:
+            from . import ground as GR
+            cands_all, lift_report = GR.lift_lines(points, off, cands_all, step=lift_step, radius=lift_radius)
         if batched:
             pieces, piece_frame, _, sparse = F.refine_slices_batched(
-                model, points, off, [[PR.pixel_to_ego(px) for px in frames[n]["pixels"]] for n in with_pose], m,
-                num_context_points, crop_radius, decay_scale, seed, precision, min_tube_points)
+                model, points, off, cands_all, m, num_context_points, crop_radius, decay_scale, seed, precision,
+                min_tube_points)
         else:
-            for si, n in enumerate(with_pose):
-                cands = [PR.pixel_to_ego(px) for px in frames[n]["pixels"]]
+            for si in range(len(with_pose)):
+                cands = cands_all[si]
                 if not cands:
                     continue
                 if off[si + 1] == off[si]:
@@ -532,6 +541,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
               "edges": int(nodes["n_edges"]),
               "clusters": int(all_clusters.max()) + 1 if len(all_clusters) else 0, "clusters_kept": len(fused),
               "pieces_unlinked": int((nodes["cluster"] < 0).sum())}
+    if lift:
+        report.update({"lift_" + k: v for k, v in lift_report.items()})
     res = {"fused": fused, "pieces": pieces, "piece_frame": piece_frame, "piece_slice": piece_frame.copy(),
            "pose_index": [int(c) for c in chosen[with_pose]], "poses": pq, "nodes": nodes, "report": report}
     if support:

@@ -270,7 +270,7 @@ def match_predictions(pred_lines_per_frame, gt_lines_per_frame, threshold=MATCH_
 
 
 def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segment_len=SEGMENT_LEN, radius=RADIUS,
-                          max_pose_gap=MAX_POSE_GAP_NS, threshold=MATCH_THRESHOLD, verbose=True):
+                          max_pose_gap=MAX_POSE_GAP_NS, threshold=MATCH_THRESHOLD, verbose=True, lift=False):
     """The tool's main() (:317-490) for one drive: drive_dir holds pose/*.json and merged.pcd, gt_json
     the GT polylines, results_json the detector's output.  One slice_cloud, one clip_lines_frames and
     one match_predictions call serve every frame that found a pose.  A frame is skipped when no pose
@@ -278,6 +278,9 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
     prediction one item: category 'lane_line', attributes {'score'}, position = the matched clipped
     GT or [], noisy_candidates = [the prediction], context_lines = every clipped GT of the frame.
     With out_dir, TS.pcd / TS.json (TS = the result timestamp) are written for the frames kept.
+    lift=True gives the noisy_candidates the z of the road under them (ground.lift_lines over the
+    frames' slices, its defaults) instead of the detector's z = 0, and adds 'lift': lift_lines'
+    report; matching stays on xy and is unchanged.
     Returns {'frames' [result ts], 'pose_index' (per frame, -1: none), 'pose_ts', 'points' (T,4) CUDA
     and 'offsets' over the frames with a pose (row 'slice' of each frame, -1: none), 'slice',
     'items' [per frame list of item dicts, [] for a skipped frame], 'matches', 'costs', 'gt_index'
@@ -302,6 +305,9 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
     clipped = clip_lines_frames([it["points"] for it in gt_items], pq, segment_len)
     preds = [[pixel_to_ego(px) for px in frames[n]["pixels"]] for n in with_pose]
     matched = match_predictions(preds, [[v for _, v in c] for c in clipped], threshold)
+    if lift:
+        from .ground import lift_lines
+        preds, res["lift"] = lift_lines(points, offsets, preds)
     off = offsets.cpu().numpy()
     pcd_paths = [None] * (len(off) - 1)
     if out_dir is not None:
