@@ -107,7 +107,9 @@ int prh_encoder_gate_recompute(int B, int N, int in_channel, int out_dim, int wa
 
 /* Bytes of scratch the encoder entry points need for P = B*N points
  * (backward = 0: prh_encoder_forward only; 1: also prh_encoder_backward; 2: prh_encoder_backward with
- * d_fused_scratch = 1, which needs 4 * out_dim bytes per point less). */
+ * d_fused_scratch = 1, which needs 4 * out_dim bytes per point less).  prh_encoder_forward and
+ * prh_encoder_backward refuse a NULL workspace, and one smaller than this reports for their call, with
+ * PRH_ERR_WORKSPACE before they touch the device. */
 size_t prh_encoder_workspace_bytes(int B, int N, int in_channel, int out_dim, int backward);
 
 /* MultiScalePointNetEncoder.forward, src/model.py:39-62.
@@ -151,6 +153,8 @@ typedef struct {
   float* bn_rstd;
   int32_t* argmax;   /* [B, out_dim] or NULL */
 } prh_encoder_saved_bf16;
+/* backward = 0: prh_encoder_forward_bf16 only; 1: also prh_encoder_backward_bf16.  A NULL workspace, or one smaller
+ * than this reports, is refused (PRH_ERR_WORKSPACE) before the device is touched. */
 size_t prh_encoder_bf16_workspace_bytes(int B, int N, int in_channel, int out_dim, int backward);
 /* fused [B,N,out_dim] bf16; everything else as prh_encoder_forward */
 int prh_encoder_forward_bf16(const prh_encoder_params* prm, const float* ctx, int B, int N, int training,

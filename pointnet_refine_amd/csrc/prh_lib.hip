@@ -1712,14 +1712,17 @@ int prh_encoder_forward(const prh_encoder_params* prm, const float* ctx, int B, 
   if ((long)B * N > 2000000000L) return fail(PRH_ERR_ARG, "encoder_forward: B*N too large");
   const int P = B * N;
   if (training && P < 2) return fail(PRH_ERR_ARG, "Expected more than 1 value per channel when training");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
   const int cat = enc_cat(prm), od = prm->out_dim, C = prm->in_channel;
   const Cores c = cores_of(gemm_mode());
   Arena a(workspace, workspace_bytes);
   EncWS ews;
   enc_carve(c, a, ews, P, prm->conv, cat, od, 0);
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "encoder_forward: workspace too small (%zu bytes)", workspace_bytes);
+  // present, and no smaller than prh_encoder_workspace_bytes reports (the carve plus 256 bytes): lin16_ws_ok's rule,
+  // before the device is touched
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "encoder_forward: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
   StackWS& w = ews.w;
 
   // conv1..5 (+bn, relu applied on load by the consumer)           src/model.py:43-47
@@ -1788,8 +1791,6 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
     return fail(PRH_ERR_ARG, "encoder_backward: bad argument (a gradient and saved.gate are required)");
   if (d_gfeat && !sv->argmax) return fail(PRH_ERR_ARG, "encoder_backward: d_gfeat needs saved.argmax");
   const int P = B * N;
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
   const int cat = enc_cat(prm), od = prm->out_dim, C = prm->in_channel;
   const Cores c = cores_of(gemm_mode());
   Arena a(workspace, workspace_bytes);
@@ -1802,7 +1803,11 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
   // combine_bwd_kernel reads dF[i] and writes dy[i] from the same thread: dy_f may live in the caller's d_fused
   float *fslab = ews.fslab, *fcslab = ews.fcslab, *dy_cat = ews.dy_cat, *dU = ews.dU, *dyf = d_fused_scratch ? d_fused : ews.dyf;
   float *gsum_a = ews.gsum_a, *gsum_b = ews.gsum_b;
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "encoder_backward: workspace too small (%zu bytes)", workspace_bytes);
+  // lin16_ws_ok's rule against prh_encoder_workspace_bytes(.., d_fused_scratch ? 2 : 1), before the device is touched
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "encoder_backward: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
   StackDims d = stack_dims(prm->conv, 5);
   if (d.cin0p != d.cin0) {
     TRY(copy_cols(ctx, d.cin0, d.cin0, w.xpad, d.cin0p, d.cin0p, (size_t)P, st));
@@ -1923,14 +1928,16 @@ int prh_encoder_forward_bf16(const prh_encoder_params* prm, const float* ctx, in
   for (int l = 0; l < 5; ++l)
     if (prm->conv[l].cout % 8) return fail(PRH_ERR_ARG, "encoder_forward_bf16: channel widths must be multiples of 8");
   if (prm->out_dim % 8) return fail(PRH_ERR_ARG, "encoder_forward_bf16: out_dim must be a multiple of 8");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
   const int cat = enc_cat(prm), od = prm->out_dim, C = prm->in_channel, c0p = cin_pad8(C);
   const int ch[6] = {C, prm->conv[0].cout, prm->conv[1].cout, prm->conv[2].cout, prm->conv[3].cout, od};
   Arena a(workspace, workspace_bytes);
   Enc16WS w;
   enc16_carve(a, w, P, ch, cat, od, false);
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "encoder_forward_bf16: workspace too small (%zu bytes)", workspace_bytes);
+  // lin16_ws_ok's rule against prh_encoder_bf16_workspace_bytes, before the device is touched
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "encoder_forward_bf16: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
   StackDims d = stack_dims(prm->conv, 5);
   u16* z_cat = sv->z_cat;
   // conv1 on fp32 operands (VALU, K = in_channel): x, y, z in metres and the raw intensity are never
@@ -2010,14 +2017,15 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
     return fail(PRH_ERR_ARG, "encoder_backward_bf16: bad argument (a gradient and saved.gate are required)");
   if (d_gfeat && !sv->argmax) return fail(PRH_ERR_ARG, "encoder_backward_bf16: d_gfeat needs saved.argmax");
   const int P = B * N;
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
   const int cat = enc_cat(prm), od = prm->out_dim, C = prm->in_channel, c0p = cin_pad8(C);
   const int ch[6] = {C, prm->conv[0].cout, prm->conv[1].cout, prm->conv[2].cout, prm->conv[3].cout, od};
   Arena a(workspace, workspace_bytes);
   Enc16WS w;
   enc16_carve(a, w, P, ch, cat, od, true);
-  if (!a.ok) return fail(PRH_ERR_WORKSPACE, "encoder_backward_bf16: workspace too small (%zu bytes)", workspace_bytes);
+  if (!lin16_ws_ok(a, workspace, workspace_bytes))
+    return fail(PRH_ERR_WORKSPACE, "encoder_backward_bf16: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
   StackDims d = stack_dims(prm->conv, 5);
   const u16* z_cat = sv->z_cat;
   const bool c1_fp32 = conv_in_fp32_ok(C, prm->conv[0].cout);
