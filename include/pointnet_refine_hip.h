@@ -1104,6 +1104,112 @@ int prh_ground_query(const void* points, int is_double, const long long* slice_o
                      double reach, double z_lo, double bin, int n_bins, int min_points, int peak_num, int peak_den,
                      double* height, int* count, int* hits, int* bin_index, int device, void* stream);
 
+/* Paint alignment - the rule.
+ * The xy shift that puts the detector's lines on the paint, read from the cloud without GT: camera
+ * lines reach the ego frame through an extrinsic and a nearest-pose match, so a few tenths of a
+ * metre of offset are normal, and beyond the context builder's 0.3 m tube the model refines against
+ * bare asphalt.  It is the xy twin of the ground lift.  The conventions are those of "Cloud support -
+ * the rule" and "Ground lift - the rule": fp64 throughout, one rounding per operation, no
+ * contraction, a 3-vector dot is (p0 * q0 + p1 * q1) + p2 * q2, every constant that decides
+ * membership is computed once on the host and passed in; the same bits go to the device and to the
+ * oracle (tests/_align_oracle.py).
+ * Inputs.  points [T,4] = x y z intensity in the ego frame of their slice, float64 (is_double != 0,
+ * what drive.slice_cloud returns) or float32, converted to fp64 first, which is exact.
+ * slice_offsets [S+1] int64.  The lines of every slice in CSR form: line_vertices [V,3] fp64,
+ * finite, |coordinate| <= 1e6, line_offsets [L+1] int64, slice_line_offsets [S+1] int64: slice s
+ * owns lines slice_line_offsets[s] .. slice_line_offsets[s+1] and sees no other.  shifts [K,2] fp64
+ * = dx dy with shift_offsets [S+1] int64: every slice has its own table (slices may hold the same
+ * values), |component| <= 4, at most prh_align_max_shifts() = 4096 rows per slice.  radius (default
+ * 0.15 m, 0 < radius <= 1) enters as r2 = radius * radius; intensity_floor (default 0).  The host
+ * raises OverflowError when a slice has 2^31 or more (candidate, line) pairs.
+ * Per (slice s, shift k = (dx, dy), point p of s, line l of s).
+ * 1. A point with a non-finite x, y or z is skipped.  wI = min(max((double)I - intensity_floor, 0),
+ *    4096), qi = (long long)rint(wI * 256) (half to even); a non-finite I gives qi = 0; a point with
+ *    qi == 0 is skipped.
+ * 2. The shifted point is w = (x - dx, y - dy, z): moving the point by -shift is moving the line by
+ *    +shift.
+ * 3. Projection, exactly fusion step 2 as support's step 1 computes it: segments k = (a, b) with e
+ *    = b - a and L2 = e.e > 0 are usable; u = clamp(((w - a).e) / L2, 0, 1), c = a + u e, h = w - c,
+ *    d2 = |h|^2.  d2min is the minimum of d2 over the line's usable segments: a minimum has no
+ *    order, so tiling the segments never shows.  A line without a usable segment has no hit.
+ * 4. The pair is a hit iff d2min <= r2.  Its taper is qk = (long long)rint((1.0 - d2min / r2) *
+ *    1024.0), 0 <= qk <= 1024: it peaks on the line, so a tube wider than the paint still has one
+ *    best position.
+ * 5. score[s,k] += qi * qk, hits[s,k] += 1, both int64.  A point inside the tubes of two lines
+ *    counts for both.  An addend is at most 2^20 * 2^10 = 2^30 and a slice has fewer than 2^31
+ *    pairs, so a sum stays below 2^61.
+ * Per slice, on the host (align.pick_shift).
+ * 6. The table must hold the shift (0, 0); k0 is its first row.
+ * 7. best = max score.  If best == 0, or hits at the first best row is below min_points (default
+ *    32), the shift is (0, 0) and the slice is "unaligned".
+ * 8. Near-best: the rows with score * keep_den >= best * keep_num in exact integers (default keep =
+ *    63 / 64); of these the one with the smallest dx * dx + dy * dy in fp64, ties to the lowest
+ *    row.  On straight lanes the along-lane component is unobservable: a plain arg-max returns an
+ *    arbitrary one, the shortest near-best shift returns none.
+ * 9. Bias.  For a paint band of half-width w <= r / 2 the expected score falls with the lateral
+ *    error e as (e / r)^2 / (1 - w^2 / (3 r^2)), so keep = 63 / 64 moves the pick by at most 0.13 r
+ *    towards zero: 0.02 m at the default radius, below one fine step.
+ * 10. Gain: the row is accepted iff score[row] * gain_den > score[k0] * gain_num (default gain = 5
+ *    / 4); otherwise the shift is (0, 0), "unaligned".
+ * Grids.  shift_grid(centre, half, step) = centre + j * step for j = -n .. n, n = round(half /
+ * step), x outer, y inner.  Coarse: centre (0, 0), half = max_shift (default 1.0), step 0.1.  Fine:
+ * centred on the coarse pick, half 0.1, step 0.02, the row (0, 0) appended; the final pick runs over
+ * the fine table.  scope = 'drive': one table for all slices, the slices' integer tables added up
+ * (exact, order-free), steps 7-10 once on the sums, in both stages.
+ * All sums are integers, so the result does not depend on the order of the points, on the filter,
+ * on the tiles or on the launch shape: it is bitwise reproducible by construction.
+ *
+ * The filter changes the cost, never the result: any superset of the true hitters gives the same
+ * sums.  reach [S] fp64 = radius + max_k max(|dx|, |dy|) + 1e-6 per slice, computed on the host: a
+ * hit at any shift of the slice lies, in x and in y, within reach of the box of the segment it
+ * hits (the 1e-6 covers the rounding of d2 for |coordinate| <= 1e6).  Slice s has a grid of square
+ * cells, `cell` metres wide (about 1 m): grid_origin [S,2] = (min x - reach, min y - reach) over
+ * the slice's vertices, grid_shape [S,2] int32 = nx ny (a slice without a vertex: 0 0), cell_base
+ * [S] int64: cell (ix, iy) of slice s is bit (c & 31) of bitmap[c >> 5], c = cell_base[s] + iy * nx
+ * + ix < n_cells < 2^31.  ix = floor((x - x0) / cell) in fp64, the same monotone expression on host
+ * and device; the host sets every cell from floor(((lo - reach) - x0) / cell) to floor(((hi +
+ * reach) - x0) / cell) of every segment's box, so by monotonicity a hitter's cell is set.
+ *   prh_align_select_count  one thread per point: one aligned load, step 1, one bitmap lookup;
+ *                           slice_counts [S] int32 (zeroed here): the survivors of each slice.
+ *   prh_align_select_write  records [capacity] of 32 bytes (x y z fp64, qi int64): with cand_offsets
+ *                           [S+1] int64 the exclusive prefix of slice_counts (the caller scans),
+ *                           rows cand_offsets[s] .. cand_offsets[s+1] are slice s's survivors in
+ *                           the order of arrival (ballot / popcount and an atomic cursor in the
+ *                           workspace: the rule does not see the order).
+ *   prh_align_score         one block per work item; items [n_items,3] int64 = (slice, first
+ *                           candidate row, first shift row), the host's plan of (slice, tile of 256
+ *                           candidates, tile of 16 shifts).  A thread holds one candidate; the
+ *                           slice's vertices go through LDS prh_align_tile() = 512 at a time, each
+ *                           slot holding the segment that starts at its vertex and the line id;
+ *                           d2min is carried across tiles and a line's hit is flushed when the line
+ *                           id changes or the list ends.  Before the projection a candidate is
+ *                           compared with the segment's reach-expanded box (cost only).  Per shift:
+ *                           integer wave reduction, LDS, one 64-bit integer atomicAdd per (block,
+ *                           shift, column) into acc [K,2] int64 = score, hits, which the caller
+ *                           zeroes.  No float atomics, no sort.
+ * points and records must be 16-byte aligned.  PRH_ERR_ARG for a scalar parameter outside the limits
+ * above (radius, cell, intensity_floor, the sizes); the limits on the shift tables and the vertices
+ * concern device data and are the caller's to check (align.paint_scores raises ValueError); a work
+ * item that does not fit the offsets is skipped by its block.  PRH_ERR_WORKSPACE below
+ * prh_align_select_workspace_bytes. */
+int prh_align_tile(void);
+int prh_align_max_shifts(void);
+size_t prh_align_select_workspace_bytes(int n_slices);
+int prh_align_select_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                           long long n_points, const double* grid_origin, const int* grid_shape,
+                           const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                           double intensity_floor, int* slice_counts, int device, void* stream);
+int prh_align_select_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                           long long n_points, const double* grid_origin, const int* grid_shape,
+                           const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                           double intensity_floor, const long long* cand_offsets, void* records, long long capacity,
+                           void* workspace, size_t workspace_bytes, int device, void* stream);
+int prh_align_score(const void* records, const long long* cand_offsets, long long n_candidates,
+                    const double* line_vertices, long long n_vertices, const long long* line_offsets, int n_lines,
+                    const long long* slice_line_offsets, const double* shifts, const long long* shift_offsets,
+                    long long n_shifts, const double* reach, int n_slices, const long long* items, long long n_items,
+                    double r2, long long* acc, int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

@@ -105,6 +105,8 @@ EXPORTS = [
     "prh_support_max_cells", "prh_support_accumulate",
     "prh_ground_max_bins", "prh_ground_bin_workspace_bytes", "prh_ground_bin_count", "prh_ground_bin_write",
     "prh_ground_query",
+    "prh_align_tile", "prh_align_max_shifts", "prh_align_select_workspace_bytes", "prh_align_select_count",
+    "prh_align_select_write", "prh_align_score",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -481,6 +483,20 @@ def _bind(lib):
     lib.prh_ground_query.restype = i
     lib.prh_ground_query.argtypes = [vp, i, vp, i, ll, vp, vp, ll, vp, vp, vp, ll, dbl, vp, vp, ll, dbl, dbl, dbl, dbl, i, i,
                                      i, i, vp, vp, vp, vp, i, vp]
+    if not hasattr(lib, "prh_align_score"):
+        return lib      # an older build under PRH_LIB_PATH (A/B runs): it has no paint alignment
+    lib.prh_align_tile.restype = i
+    lib.prh_align_tile.argtypes = []
+    lib.prh_align_max_shifts.restype = i
+    lib.prh_align_max_shifts.argtypes = []
+    lib.prh_align_select_workspace_bytes.restype = sz
+    lib.prh_align_select_workspace_bytes.argtypes = [i]
+    lib.prh_align_select_count.restype = i
+    lib.prh_align_select_count.argtypes = [vp, i, vp, i, ll, vp, vp, vp, vp, ll, dbl, dbl, vp, i, vp]
+    lib.prh_align_select_write.restype = i
+    lib.prh_align_select_write.argtypes = [vp, i, vp, i, ll, vp, vp, vp, vp, ll, dbl, dbl, vp, vp, ll, vp, sz, i, vp]
+    lib.prh_align_score.restype = i
+    lib.prh_align_score.argtypes = [vp, vp, ll, vp, ll, vp, i, vp, vp, vp, ll, vp, i, vp, ll, dbl, vp, i, vp]
     return lib
 
 

@@ -1,0 +1,381 @@
+"""Paint alignment: the xy shift that puts the detector's lines on the paint, read from the cloud.
+
+The detector's lines reach the ego frame through a camera-lidar extrinsic and a nearest-pose match
+(``predictions.match_poses``), so a few tenths of a metre of systematic offset are normal; the
+context builder's tube is 0.3 m wide, and beyond it the model refines against bare asphalt.
+``metrics.calibrate_alignment`` finds such a shift only against GT.  This module finds it from the
+frame's own slice of the cloud: for every (slice, shift) of a brute-force grid the sum, over (bright
+point, line) pairs, of the point's intensity weight times a taper of its distance to the shifted
+line, in integers (``csrc/prh_align.hpp``; the rule is in ``include/pointnet_refine_hip.h``, "Paint
+alignment - the rule", and restated in ``tests/_align_oracle.py``).  It is the xy twin of
+``ground.lift_lines`` and plugs into the same places.
+
+  shift_grid       host: one grid of shifts around a centre, x outer, y inner (numpy)
+  segment_bitmaps  host: per slice the cells a reach-expanded segment box touches (numpy)
+  paint_scores     HIP: candidate filter (count, scan, write), then the score sweep: per (slice,
+                   shift) the int64 score and hit count
+  pick_shift       host: the shortest shift among the near-best rows, the min_points and gain tests
+  align_lines      a coarse and a fine paint_scores call with their picks: x y of every vertex moved
+                   by its slice's (or the drive's) shift
+
+    shifted, report = align_lines(points, offsets, [[pixel_to_ego(px) for px in frame] for frame in frames])
+
+paint_scores and align_lines have no CPU fallback: without a GPU they raise RuntimeError.
+"""
+import numpy as np
+import torch
+
+from . import _gpu as G
+from . import _lib as L
+from .ground import _host, _offsets, _points
+
+RADIUS = 0.15                # metres: the tube around a shifted line
+MAX_RADIUS = 1.0
+GUARD = 1e-6                 # metres added to the reach (rounding of d2)
+MAX_COORD = 1e6              # |vertex coordinate| the guard is sized for
+MAX_SHIFT = 4.0              # |shift component|
+MAX_SHIFTS = 4096            # prh_align_max_shifts(): rows of one slice's table
+CELL = 1.0                   # metres: the bitmap's cell
+MAX_CELLS = 1 << 26          # the cell is doubled until all bitmaps together fit: cost only, never the result
+MIN_POINTS = 32
+KEEP = (63, 64)
+GAIN = (5, 4)
+COARSE_HALF, COARSE_STEP = 1.0, 0.1
+FINE_HALF, FINE_STEP = 0.1, 0.02
+CANDIDATES, SHIFTS = 256, 16     # a work item of prh_align_score
+
+
+# ------------------------------------------------------------------ host side
+def shift_grid(centre=(0.0, 0.0), half=COARSE_HALF, step=COARSE_STEP):
+    """((2n+1)^2, 2) float64: centre + j * step for j = -n .. n with n = round(half / step), x outer
+    and y inner (metrics._grid's order)."""
+    half, step = float(half), float(step)
+    if not (step > 0.0 and np.isfinite(step) and half >= 0.0 and np.isfinite(half)):
+        raise ValueError("shift_grid: step > 0 and half >= 0")
+    n = int(round(half / step))
+    j = np.arange(-n, n + 1, dtype=np.float64) * step
+    xs, ys = float(centre[0]) + j, float(centre[1]) + j
+    return np.stack([np.repeat(xs, len(ys)), np.tile(ys, len(xs))], axis=1).astype(np.float64).reshape(-1, 2)
+
+
+def lines_csr(lines_per_slice, what="paint_scores"):
+    """The lines of every slice as CSR: (vertices (V,3) float64, line_offsets (L+1,) int64,
+    slice_line_offsets (S+1,) int64).  A vertex must be finite and within MAX_COORD of the origin."""
+    flat = [np.asarray(v, dtype=np.float64).reshape(-1, 3) for ls in lines_per_slice for v in ls]
+    per_slice = np.array([len(ls) for ls in lines_per_slice], dtype=np.int64)
+    sl_off = np.zeros(len(per_slice) + 1, dtype=np.int64)
+    sl_off[1:] = np.cumsum(per_slice)
+    l_off = np.zeros(len(flat) + 1, dtype=np.int64)
+    l_off[1:] = np.cumsum([len(v) for v in flat])
+    verts = np.ascontiguousarray(np.concatenate(flat)) if l_off[-1] > 0 else np.zeros((0, 3))
+    if not (np.isfinite(verts).all() and (len(verts) == 0 or np.abs(verts).max() <= MAX_COORD)):
+        raise ValueError(f"{what}: line vertices must be finite and within {MAX_COORD:g} m of the slice's origin")
+    return verts, l_off, sl_off
+
+
+def slice_reach(shifts, shift_offsets, radius):
+    """(S,) float64: radius + max_k max(|dx|, |dy|) + GUARD over every slice's own table (a slice
+    without a shift: radius + GUARD)."""
+    sh = np.asarray(shifts, dtype=np.float64).reshape(-1, 2)
+    off = np.asarray(shift_offsets, dtype=np.int64).reshape(-1)
+    big = np.zeros(len(off) - 1)
+    used = np.flatnonzero(np.diff(off) > 0)
+    if len(used):
+        big[used] = np.maximum.reduceat(np.abs(sh).max(axis=1), off[:-1][used])
+    return float(radius) + big + GUARD
+
+
+def segment_bitmaps(vertices, line_offsets, slice_line_offsets, reach, cell=CELL):
+    """The bitmaps prh_align_select_* look a point up in ("Paint alignment - the rule").  Per slice
+    a uniform xy grid, cell metres wide, over the box of its vertices expanded by reach[s]; cell
+    index floor((x - x0) / cell) in fp64, the kernels' expression.  A cell is set when the xy box of
+    a segment (two consecutive vertices of one line), expanded by reach[s], touches it.  cell is
+    doubled until all grids together have at most MAX_CELLS cells.  Returns {'origin' (S,2)
+    float64, 'shape' (S,2) int32 = nx ny (0 0 for a slice without a vertex), 'cell_base' (S,)
+    int64, 'n_cells', 'cell', 'bitmap' (ceil(n_cells / 32),) uint32: cell c is bit c & 31 of word
+    c >> 5}."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    l_off = np.asarray(line_offsets, dtype=np.int64).reshape(-1)
+    sl_off = np.asarray(slice_line_offsets, dtype=np.int64).reshape(-1)
+    reach = np.asarray(reach, dtype=np.float64).reshape(-1)
+    cell = float(cell)
+    n_s = len(sl_off) - 1
+    v_off = l_off[sl_off]                                   # the vertices of every slice
+    origin = np.zeros((n_s, 2))
+    shape = np.zeros((n_s, 2), dtype=np.int64)
+    used = np.flatnonzero(np.diff(v_off) > 0)
+    if len(used):
+        start = v_off[:-1][used]
+        lo = np.stack([np.minimum.reduceat(v[:, c], start) for c in (0, 1)], 1) - reach[used, None]
+        hi = np.stack([np.maximum.reduceat(v[:, c], start) for c in (0, 1)], 1) + reach[used, None]
+        origin[used] = lo
+        while True:
+            n = np.floor((hi - lo) / cell).astype(np.int64) + 1
+            if int((n[:, 0] * n[:, 1]).sum()) <= MAX_CELLS:
+                break
+            cell *= 2.0
+        shape[used] = n
+    base = np.zeros(n_s, dtype=np.int64)
+    cells = shape[:, 0] * shape[:, 1]
+    if n_s:
+        base[1:] = np.cumsum(cells)[:-1]
+    n_cells = int(cells.sum())
+    bits = np.zeros(n_cells, dtype=bool)
+    # segments: vertex k and k + 1 of one line
+    is_a = np.ones(len(v), dtype=bool)
+    is_a[l_off[1:][l_off[1:] > 0] - 1] = False               # a line's last vertex starts no segment
+    a = np.flatnonzero(is_a)
+    if len(a):
+        s_of = np.searchsorted(v_off, a, side="right") - 1
+        r = reach[s_of]
+        lo = np.minimum(v[a, :2], v[a + 1, :2]) - r[:, None]
+        hi = np.maximum(v[a, :2], v[a + 1, :2]) + r[:, None]
+        i0 = np.floor((lo - origin[s_of]) / cell).astype(np.int64)
+        i1 = np.floor((hi - origin[s_of]) / cell).astype(np.int64)
+        i0 = np.maximum(i0, 0)
+        i1 = np.minimum(i1, shape[s_of] - 1)
+        nxy = np.maximum(i1 - i0 + 1, 0)
+        cnt = nxy[:, 0] * nxy[:, 1]
+        seg = np.repeat(np.arange(len(a)), cnt)
+        k = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        ix = i0[seg, 0] + k % np.maximum(nxy[seg, 0], 1)
+        iy = i0[seg, 1] + k // np.maximum(nxy[seg, 0], 1)
+        bits[base[s_of[seg]] + iy * shape[s_of[seg], 0] + ix] = True
+    packed = np.packbits(bits, bitorder="little")
+    words = np.zeros(((n_cells + 31) // 32) * 4, dtype=np.uint8)
+    words[:len(packed)] = packed
+    return {"origin": origin, "shape": shape.astype(np.int32), "cell_base": base, "n_cells": n_cells, "cell": cell,
+            "bitmap": words.view("<u4").astype(np.uint32)}
+
+
+def _ratio(pair, what, name, allow_above_one):
+    try:
+        num, den = pair
+        ok = int(num) == num and int(den) == den and int(num) >= 1 and int(den) >= 1
+        ok = ok and (allow_above_one or int(num) <= int(den)) and max(int(num), int(den)) <= 65536
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: {name} = (num, den), positive integers up to 65536")
+    return int(num), int(den)
+
+
+def pick_shift(shifts, score, hits, min_points=MIN_POINTS, keep=KEEP, gain=GAIN):
+    """Steps 6-10 of the rule over one table.  shifts (K,2) float64, score and hits (K,) integers.
+    Returns {'shift' (2,) float64, 'row' (the accepted row, or k0), 'aligned' bool, 'score_zero',
+    'score_best' (Python ints: the score at (0, 0) and at the near-best row)}."""
+    what = "pick_shift"
+    sh = np.asarray(shifts, dtype=np.float64).reshape(-1, 2)
+    sc = [int(x) for x in np.asarray(score).reshape(-1)]
+    ht = [int(x) for x in np.asarray(hits).reshape(-1)]
+    if not (len(sh) == len(sc) == len(ht)):
+        raise ValueError(f"{what}: one score and one hit count per shift")
+    keep_num, keep_den = _ratio(keep, what, "keep", False)
+    gain_num, gain_den = _ratio(gain, what, "gain", True)
+    if int(min_points) != min_points or int(min_points) < 1:
+        raise ValueError(f"{what}: min_points must be an integer >= 1")
+    zero = np.flatnonzero((sh[:, 0] == 0.0) & (sh[:, 1] == 0.0))
+    if len(zero) == 0:
+        raise ValueError(f"{what}: the table must contain the shift (0, 0)")
+    k0 = int(zero[0])
+    none = {"shift": np.zeros(2), "row": k0, "aligned": False, "score_zero": sc[k0], "score_best": sc[k0]}
+    best = max(sc)
+    if best == 0 or ht[sc.index(best)] < int(min_points):
+        return none
+    near = [k for k in range(len(sc)) if sc[k] * keep_den >= best * keep_num]
+    n2 = sh[near, 0] * sh[near, 0] + sh[near, 1] * sh[near, 1]
+    row = near[int(np.argmin(n2))]                           # argmin: the first of equal values, the lowest row
+    none["score_best"] = sc[row]
+    if not sc[row] * gain_den > sc[k0] * gain_num:
+        return none
+    return {"shift": sh[row].copy(), "row": row, "aligned": True, "score_zero": sc[k0], "score_best": sc[row]}
+
+
+def work_items(cand_offsets, shift_offsets, slice_vertices):
+    """The plan of prh_align_score: (W,3) int64 = (slice, first candidate row, first shift row), one
+    item per (slice, tile of CANDIDATES candidates, tile of SHIFTS shifts), the candidate tile
+    running fastest; slices without a candidate, a shift or a vertex have none."""
+    c_off = np.asarray(cand_offsets, dtype=np.int64)
+    k_off = np.asarray(shift_offsets, dtype=np.int64)
+    nc, nk = np.diff(c_off), np.diff(k_off)
+    nct, nkt = (nc + CANDIDATES - 1) // CANDIDATES, (nk + SHIFTS - 1) // SHIFTS
+    per = np.where(np.asarray(slice_vertices) > 0, nct * nkt, 0)
+    s = np.repeat(np.arange(len(nc), dtype=np.int64), per)
+    r = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    div = np.maximum(nct[s], 1)
+    return np.ascontiguousarray(np.stack([s, c_off[s] + (r % div) * CANDIDATES, k_off[s] + (r // div) * SHIFTS], 1))
+
+
+# ------------------------------------------------------------------ GPU side
+def _params(radius, intensity_floor, cell, what):
+    radius, intensity_floor, cell = float(radius), float(intensity_floor), float(cell)
+    if not 0.0 < radius <= MAX_RADIUS:
+        raise ValueError(f"{what}: 0 < radius <= {MAX_RADIUS}")
+    if not np.isfinite(intensity_floor):
+        raise ValueError(f"{what}: intensity_floor must be finite")
+    if not (np.isfinite(cell) and cell > 0.0):
+        raise ValueError(f"{what}: cell must be positive and finite")
+    return radius, intensity_floor, cell
+
+
+def prepare(points, slice_offsets, lines_per_slice, shifts, shift_offsets, radius, intensity_floor, cell, what):
+    """Validation and the host side of one paint_scores call: the points on the device, the lines as
+    CSR, every slice's reach and bitmap.  Returns the dict select_candidates and score_candidates take."""
+    radius, intensity_floor, cell = _params(radius, intensity_floor, cell, what)
+    dev = G.device("align", points.device if torch.is_tensor(points) and points.is_cuda else None)
+    pts = _points(points, dev, what)
+    off = _offsets(slice_offsets, pts.shape[0], what, "slice_offsets")
+    n_s = len(off) - 1
+    if len(lines_per_slice) != n_s:
+        raise ValueError(f"{what}: one list of lines per slice ({n_s}), got {len(lines_per_slice)}")
+    verts, l_off, sl_off = lines_csr(lines_per_slice, what)
+    shape = tuple(shifts.shape) if torch.is_tensor(shifts) else np.shape(shifts)
+    if len(shape) != 2 or shape[1] != 2:
+        raise ValueError(f"{what}: shifts must be (K,2) dx dy, got {shape}")
+    sh = np.ascontiguousarray(_host(shifts, np.float64).reshape(-1, 2))
+    if not (np.isfinite(sh).all() and (len(sh) == 0 or np.abs(sh).max() <= MAX_SHIFT)):
+        raise ValueError(f"{what}: shifts must be finite with |component| <= {MAX_SHIFT:g}")
+    k_off = _offsets(shift_offsets, len(sh), what, "shift_offsets")
+    if len(k_off) != len(off):
+        raise ValueError(f"{what}: slice_offsets and shift_offsets must describe the same slices")
+    if n_s and int(np.diff(k_off).max()) > MAX_SHIFTS:
+        raise ValueError(f"{what}: at most {MAX_SHIFTS} shifts per slice")
+    reach = slice_reach(sh, k_off, radius)
+    maps = segment_bitmaps(verts, l_off, sl_off, reach, cell)
+    return {"dev": dev, "pts": pts, "off": off, "n_s": n_s, "verts": verts, "l_off": l_off, "sl_off": sl_off, "sh": sh,
+            "k_off": k_off, "reach": reach, "maps": maps, "radius": radius, "intensity_floor": intensity_floor, "what": what}
+
+
+def select_candidates(p):
+    """prh_align_select_count, the scan, prh_align_select_write: (records (C,4) float64 CUDA - x y z
+    and the bits of qi -, cand_offsets (S+1,) int64 CUDA, the same offsets as numpy)."""
+    lib, dev, pts, maps, n_s = L.lib(), p["dev"], p["pts"], p["maps"], p["n_s"]
+    if n_s == 0 or pts.shape[0] == 0 or maps["n_cells"] == 0:
+        return torch.empty((0, 4), dtype=torch.float64, device=dev), None, np.zeros(n_s + 1, dtype=np.int64)
+    counts = torch.zeros((n_s,), dtype=torch.int32, device=dev)
+    off_t = torch.from_numpy(p["off"]).to(dev)
+    g_t = tuple(torch.from_numpy(np.ascontiguousarray(maps[k])).to(dev) for k in ("origin", "shape", "cell_base"))
+    bitmap = torch.from_numpy(maps["bitmap"].view(np.int32)).to(dev)
+    args = (G.ptr(pts), 1 if pts.dtype == torch.float64 else 0, G.ptr(off_t), n_s, pts.shape[0], G.ptr(g_t[0]), G.ptr(g_t[1]),
+            G.ptr(g_t[2]), G.ptr(bitmap), maps["n_cells"], maps["cell"], p["intensity_floor"])
+    L.check(lib.prh_align_select_count(*args, G.ptr(counts), dev.index, G.stream(dev)), "prh_align_select_count")
+    cand_off = G.exclusive_scan(counts)
+    c_off = cand_off.cpu().numpy()
+    total = int(c_off[-1])
+    rec = torch.empty((total, 4), dtype=torch.float64, device=dev)
+    if total:
+        nb = lib.prh_align_select_workspace_bytes(n_s)
+        ws = G.workspace(nb, dev)
+        L.check(lib.prh_align_select_write(*args, G.ptr(cand_off), G.ptr(rec), total, G.ptr(ws), nb, dev.index,
+                                           G.stream(dev)), "prh_align_select_write")
+    return rec, cand_off, c_off
+
+
+def score_candidates(p, rec, cand_off, c_off):
+    """The plan and prh_align_score over the selected candidates: acc (K,2) int64 CUDA = score, hits."""
+    dev, sh = p["dev"], p["sh"]
+    acc = torch.zeros((len(sh), 2), dtype=torch.int64, device=dev)
+    if p["n_s"] and int((np.diff(c_off) * np.diff(p["sl_off"])).max()) >= 2 ** 31:
+        raise OverflowError(f"{p['what']}: a slice has 2^31 or more (candidate, line) pairs")
+    items = work_items(c_off, p["k_off"], np.diff(p["l_off"][p["sl_off"]]))
+    if rec.shape[0] == 0 or len(items) == 0:
+        return acc
+    up = [torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+          for x in (p["verts"], p["l_off"], p["sl_off"], sh, p["k_off"], p["reach"], items)]
+    L.check(L.lib().prh_align_score(G.ptr(rec), G.ptr(cand_off), rec.shape[0], G.ptr(up[0]), len(p["verts"]), G.ptr(up[1]),
+                                    len(p["l_off"]) - 1, G.ptr(up[2]), G.ptr(up[3]), G.ptr(up[4]), len(sh), G.ptr(up[5]),
+                                    p["n_s"], G.ptr(up[6]), len(items), p["radius"] * p["radius"], G.ptr(acc), dev.index,
+                                    G.stream(dev)), "prh_align_score")
+    return acc
+
+
+def _scores(points, slice_offsets, lines_per_slice, shifts, shift_offsets, radius, intensity_floor, cell, what):
+    p = prepare(points, slice_offsets, lines_per_slice, shifts, shift_offsets, radius, intensity_floor, cell, what)
+    rec, cand_off, c_off = select_candidates(p)
+    acc = score_candidates(p, rec, cand_off, c_off)
+    return {"score": acc[:, 0], "hits": acc[:, 1], "candidates": np.diff(c_off)}
+
+
+def paint_scores(points, slice_offsets, lines_per_slice, shifts, shift_offsets, radius=RADIUS, intensity_floor=0.0,
+                 cell=CELL):
+    """The paint score of every (slice, shift) ("Paint alignment - the rule", steps 1-5).
+
+    points (T,4) float64 or float32 x y z intensity, every slice in its own frame, with slice_offsets
+    (S+1,) - what drive.slice_cloud returns (CUDA tensors are used where they are, numpy is
+    uploaded); lines_per_slice: per slice the list of (n,3) polylines in that slice's frame; shifts
+    (K,2) float64 dx dy grouped by slice with shift_offsets (S+1,).  A point weighs rint(256 *
+    clamp(I - intensity_floor, 0, 4096)); a (point, line) pair within radius of each other once the
+    line is moved by the shift adds weight * rint(1024 * (1 - d2 / radius^2)) to the shift's score
+    and 1 to its hits.  cell is the width of the filter's bitmap cells: cost only.  Returns a dict of
+    CUDA tensors 'score' (K,) int64 and 'hits' (K,) int64.  Bitwise reproducible, whatever the order
+    of the points."""
+    res = _scores(points, slice_offsets, lines_per_slice, shifts, shift_offsets, radius, intensity_floor, cell,
+                  "paint_scores")
+    return {"score": res["score"], "hits": res["hits"]}
+
+
+def _stage(points, off, lines, tables, scope, radius, intensity_floor, pick_kw, what):
+    """One paint_scores call over per-slice tables and the picks: per slice under scope 'frame', once
+    on the summed tables under scope 'drive' (every slice's table is then the same)."""
+    n_s = len(lines)
+    if n_s == 0:
+        return [], np.zeros(0, dtype=np.int64)
+    k_off = np.zeros(n_s + 1, dtype=np.int64)
+    k_off[1:] = np.cumsum([len(t) for t in tables])
+    res = _scores(points, off, lines, np.concatenate(tables) if n_s else np.zeros((0, 2)), k_off, radius, intensity_floor,
+                  CELL, what)
+    score, hits = res["score"].cpu().numpy(), res["hits"].cpu().numpy()
+    if scope == "drive":
+        k = len(tables[0])
+        one = pick_shift(tables[0], [int(x) for x in score.reshape(n_s, k).astype(object).sum(axis=0)],
+                         [int(x) for x in hits.reshape(n_s, k).astype(object).sum(axis=0)], **pick_kw)
+        picks = [one] * n_s
+    else:
+        picks = [pick_shift(tables[s], score[k_off[s]:k_off[s + 1]], hits[k_off[s]:k_off[s + 1]], **pick_kw)
+                 for s in range(n_s)]
+    return picks, res["candidates"]
+
+
+def align_lines(points, slice_offsets, lines_per_slice, max_shift=COARSE_HALF, radius=RADIUS, intensity_floor=0.0,
+                scope="frame", min_points=MIN_POINTS, keep=KEEP, gain=GAIN):
+    """Put every line on the paint of its own slice.
+
+    points, slice_offsets: as paint_scores takes them; lines_per_slice: per slice the list of (n,3)
+    polylines in that slice's frame.  A coarse paint_scores call over shift_grid((0, 0), max_shift,
+    0.1) and its picks, a fine one over shift_grid(coarse pick, 0.1, 0.02) with the row (0, 0)
+    appended, and the final picks over the fine tables (pick_shift: min_points, keep, gain).
+    scope='frame' picks per slice; scope='drive' adds the slices' tables up and picks once, in both
+    stages, so every slice gets the same shift.  x and y of every vertex move by the slice's shift;
+    z never changes.  Returns (the shifted (n,3) float64 lines in the same nesting, report
+    {'frames', 'frames_aligned', 'frames_unaligned', 'shifts' (S,2) float64, 'score_zero' and
+    'score_best' (S,) int64: the final table's score at (0, 0) and at the near-best row (the summed
+    table's under scope='drive'), 'candidates': the points the final sweep kept})."""
+    what = "align_lines"
+    G.device("align")
+    if scope not in ("frame", "drive"):
+        raise ValueError(f"{what}: scope must be 'frame' or 'drive'")
+    max_shift = float(max_shift)
+    if not (np.isfinite(max_shift) and 0.0 < max_shift <= MAX_SHIFT - FINE_HALF):
+        raise ValueError(f"{what}: 0 < max_shift <= {MAX_SHIFT - FINE_HALF}")
+    coarse = shift_grid((0.0, 0.0), max_shift, COARSE_STEP)
+    if len(coarse) > MAX_SHIFTS:
+        raise ValueError(f"{what}: max_shift gives {len(coarse)} coarse shifts, at most {MAX_SHIFTS}")
+    pick_kw = {"min_points": min_points, "keep": keep, "gain": gain}
+    pick_shift(np.zeros((1, 2)), [0], [0], **pick_kw)         # validates min_points, keep and gain
+    lines = [[np.array(v, dtype=np.float64).reshape(-1, 3) for v in ls] for ls in lines_per_slice]
+    n_s = len(lines)
+    off = _host(slice_offsets, np.int64).reshape(-1)
+    first, _ = _stage(points, off, lines, [coarse] * n_s, scope, radius, intensity_floor, pick_kw, what)
+    fine = [np.concatenate([shift_grid(p["shift"], FINE_HALF, FINE_STEP), np.zeros((1, 2))]) for p in first]
+    picks, cands = _stage(points, off, lines, fine, scope, radius, intensity_floor, pick_kw, what)
+    shifts = np.array([p["shift"] for p in picks], dtype=np.float64).reshape(n_s, 2)
+    for s, ls in enumerate(lines):
+        for v in ls:
+            v[:, 0] = v[:, 0] + shifts[s, 0]
+            v[:, 1] = v[:, 1] + shifts[s, 1]
+    aligned = int(sum(1 for p in picks if p["aligned"]))
+    report = {"frames": n_s, "frames_aligned": aligned, "frames_unaligned": n_s - aligned, "shifts": shifts,
+              "score_zero": np.array([p["score_zero"] for p in picks], dtype=np.int64),
+              "score_best": np.array([p["score_best"] for p in picks], dtype=np.int64),
+              "candidates": int(np.sum(cands))}
+    return lines, report

@@ -34,6 +34,7 @@
 #include "prh_link_sync.hpp"
 #include "prh_support.hpp"
 #include "prh_ground.hpp"
+#include "prh_align.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
@@ -3747,6 +3748,106 @@ int prh_ground_query(const void* points, int is_double, const long long* slice_o
     hipLaunchKernelGGL(ground_query_kernel<float>, dim3(nblk), dim3(GROUND_THREADS), 0, st, (const float*)points,
                        slice_offsets, n_slices, queries, query_offsets, n_queries, grid_origin, grid_shape, cell_base,
                        cell_offsets, rows, n_rows, n_cells, prm, height, count, hits, bin_index);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ paint alignment
+int prh_align_tile(void) { return ALIGN_TILE; }
+int prh_align_max_shifts(void) { return ALIGN_MAX_SHIFTS; }
+size_t prh_align_select_workspace_bytes(int n_slices) {
+  return n_slices < 0 ? 0 : align_up((size_t)n_slices * sizeof(int), 256);
+}
+static int align_check_select(const char* what, const void* points, int is_double, const long long* slice_offsets,
+                              int n_slices, long long n_points, const double* grid_origin, const int* grid_shape,
+                              const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                              double intensity_floor) {
+  if (n_slices < 0 || n_points < 0 || n_cells < 0 || n_cells > 0x7fffffffll || n_points >= 256ll * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "%s: bad argument (at most 2^31 - 1 cells)", what);
+  if (!(cell > 0.0) || !(cell < 1e300)) return fail(PRH_ERR_ARG, "%s: cell must be positive and finite", what);
+  if (!(intensity_floor == intensity_floor) || !(intensity_floor > -1e300) || !(intensity_floor < 1e300))
+    return fail(PRH_ERR_ARG, "%s: intensity_floor must be finite", what);
+  if (n_slices > 0 && (!slice_offsets || !grid_origin || !grid_shape || !cell_base))
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if (n_cells > 0 && !bitmap) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if (n_points > 0 && (!points || n_slices == 0)) return fail(PRH_ERR_ARG, "%s: points without a slice", what);
+  if (((uintptr_t)points & 15) != 0) return fail(PRH_ERR_ARG, "%s: points must be 16-byte aligned", what);
+  return PRH_OK;
+}
+int prh_align_select_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                           long long n_points, const double* grid_origin, const int* grid_shape,
+                           const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                           double intensity_floor, int* slice_counts, int device, void* stream) {
+  TRY_RC(align_check_select("align_select_count", points, is_double, slice_offsets, n_slices, n_points, grid_origin,
+                            grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor));
+  if (n_slices == 0) return PRH_OK;
+  if (!slice_counts) return fail(PRH_ERR_ARG, "align_select_count: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(slice_counts, 0, (size_t)n_slices * sizeof(int), st));
+  if (n_points == 0 || n_cells == 0) return PRH_OK;
+  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
+  if (is_double)
+    hipLaunchKernelGGL((align_select_kernel<double, false>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
+                       (const double*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                       bitmap, n_cells, cell, intensity_floor, slice_counts, (const long long*)nullptr,
+                       (AlignRecord*)nullptr, 0ll);
+  else
+    hipLaunchKernelGGL((align_select_kernel<float, false>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
+                       (const float*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                       bitmap, n_cells, cell, intensity_floor, slice_counts, (const long long*)nullptr,
+                       (AlignRecord*)nullptr, 0ll);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_align_select_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                           long long n_points, const double* grid_origin, const int* grid_shape,
+                           const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                           double intensity_floor, const long long* cand_offsets, void* records, long long capacity,
+                           void* workspace, size_t workspace_bytes, int device, void* stream) {
+  TRY_RC(align_check_select("align_select_write", points, is_double, slice_offsets, n_slices, n_points, grid_origin,
+                            grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor));
+  if (capacity < 0) return fail(PRH_ERR_ARG, "align_select_write: bad capacity");
+  if (n_slices == 0 || n_points == 0 || n_cells == 0 || capacity == 0) return PRH_OK;
+  if (!cand_offsets || !records) return fail(PRH_ERR_ARG, "align_select_write: null pointer");
+  if (((uintptr_t)records & 15) != 0) return fail(PRH_ERR_ARG, "align_select_write: records must be 16-byte aligned");
+  if (!workspace || workspace_bytes < prh_align_select_workspace_bytes(n_slices))
+    return fail(PRH_ERR_WORKSPACE, "align_select_write: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* cursor = (int*)workspace;
+  HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)n_slices * sizeof(int), st));
+  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
+  if (is_double)
+    hipLaunchKernelGGL((align_select_kernel<double, true>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
+                       (const double*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                       bitmap, n_cells, cell, intensity_floor, cursor, cand_offsets, (AlignRecord*)records, capacity);
+  else
+    hipLaunchKernelGGL((align_select_kernel<float, true>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
+                       (const float*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                       bitmap, n_cells, cell, intensity_floor, cursor, cand_offsets, (AlignRecord*)records, capacity);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_align_score(const void* records, const long long* cand_offsets, long long n_candidates,
+                    const double* line_vertices, long long n_vertices, const long long* line_offsets, int n_lines,
+                    const long long* slice_line_offsets, const double* shifts, const long long* shift_offsets,
+                    long long n_shifts, const double* reach, int n_slices, const long long* items, long long n_items,
+                    double r2, long long* acc, int device, void* stream) {
+  if (n_candidates < 0 || n_vertices < 0 || n_lines < 0 || n_shifts < 0 || n_slices < 0 || n_items < 0 ||
+      n_items > 0x7fffffffll)
+    return fail(PRH_ERR_ARG, "align_score: bad argument (at most 2^31 - 1 work items)");
+  if (!(r2 > 0.0) || !(r2 <= 1.0)) return fail(PRH_ERR_ARG, "align_score: 0 < radius <= 1");
+  if (n_items == 0) return PRH_OK;
+  if (!records || !cand_offsets || !line_vertices || !line_offsets || !slice_line_offsets || !shifts || !shift_offsets ||
+      !reach || !items || !acc || n_slices == 0)
+    return fail(PRH_ERR_ARG, "align_score: null pointer");
+  if (((uintptr_t)records & 15) != 0) return fail(PRH_ERR_ARG, "align_score: records must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(align_score_kernel, dim3((unsigned)n_items), dim3(ALIGN_THREADS), 0, (hipStream_t)stream,
+                     (const AlignRecord*)records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets,
+                     n_lines, slice_line_offsets, shifts, shift_offsets, n_shifts, reach, n_slices, items, r2,
+                     (unsigned long long*)acc);
   LAUNCH_CHECK();
   return PRH_OK;
 }

@@ -460,7 +460,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
                        min_tube_points=F.MIN_TUBE_POINTS, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATIO,
                        min_pieces=MIN_PIECES, step=F.STEP, min_count=F.MIN_COUNT, max_gap=F.MAX_GAP, origin=None,
                        batched=False, support=False, support_radius=None, intensity_floor=0.0, device_sync=False,
-                       return_links=False, lift=False, lift_radius=0.5, lift_step=1.0):
+                       return_links=False, lift=False, lift_radius=0.5, lift_step=1.0, align=False, align_max_shift=1.0,
+                       align_radius=0.15, align_scope="frame"):
     """A detector run refined into one drive-frame map, with no GT.
 
     drive_dir holds pose/*.json and merged.pcd; results_json is the detector's output
@@ -476,6 +477,12 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     all frames' slices (stations every lift_step metres, cloud points within lift_radius in xy), and
     the lifted lines are the candidates; the report gains 'lift_lines', 'lift_lines_lifted',
     'lift_lines_unlifted', 'lift_stations' and 'lift_stations_without_ground'.
+    align=True then moves every frame's lines in x y onto the paint: one align.align_lines call over
+    all frames' slices (shifts up to align_max_shift per component, cloud points within align_radius
+    of a shifted line, one shift per frame or - align_scope='drive' - one for the drive); it runs
+    after the lift, because its distances are 3-D, and before the candidates are refined; the report
+    gains 'align_frames', 'align_frames_aligned', 'align_frames_unaligned', 'align_shifts' (S,2),
+    'align_score_zero', 'align_score_best' and 'align_candidates'.
 
     Returns {'fused' [per kept cluster], 'pieces' (P,M,3) float64 ego frame, 'piece_frame' (P,) the
     row of 'poses' each piece was seen from, 'piece_slice' (the same), 'pose_index' (per used frame
@@ -499,6 +506,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     pieces, piece_frame, sparse = [], [], 0
     cloud = None
     lift_report = {"lines": 0, "lines_lifted": 0, "lines_unlifted": 0, "stations": 0, "stations_without_ground": 0}
+    align_report = {"frames": 0, "frames_aligned": 0, "frames_unaligned": 0, "shifts": np.zeros((0, 2)),
+                    "score_zero": np.zeros(0, dtype=np.int64), "score_best": np.zeros(0, dtype=np.int64), "candidates": 0}
     if len(with_pose):
         cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
         points, offsets, _ = D.slice_cloud(np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4), pq, segment_len,
@@ -508,6 +517,10 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
         if lift:
             from . import ground as GR
             cands_all, lift_report = GR.lift_lines(points, off, cands_all, step=lift_step, radius=lift_radius)
+        if align:
+            from . import align as AL
+            cands_all, align_report = AL.align_lines(points, off, cands_all, max_shift=align_max_shift,
+                                                     radius=align_radius, scope=align_scope)
         if batched:
             pieces, piece_frame, _, sparse = F.refine_slices_batched(
                 model, points, off, cands_all, m, num_context_points, crop_radius, decay_scale, seed, precision,
@@ -543,6 +556,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
               "pieces_unlinked": int((nodes["cluster"] < 0).sum())}
     if lift:
         report.update({"lift_" + k: v for k, v in lift_report.items()})
+    if align:
+        report.update({"align_" + k: v for k, v in align_report.items()})
     res = {"fused": fused, "pieces": pieces, "piece_frame": piece_frame, "piece_slice": piece_frame.copy(),
            "pose_index": [int(c) for c in chosen[with_pose]], "poses": pq, "nodes": nodes, "report": report}
     if support:
