@@ -6,7 +6,7 @@ examples/evaluate_scenes.py reads.  Every frame of the drive goes through one sl
 cost and one assignment launch on the GPU.
 
     python examples/predictions_to_scenes.py DRIVE_DIR GT_JSON RESULTS_JSON OUT_DIR [--evaluate CHECKPOINT [--batched]]
-                                             [--lift] [--align]
+                                             [--lift] [--align [--align-max-yaw RAD]]
 
 --evaluate CHECKPOINT scores what was written with metrics.evaluate_scene (CHECKPOINT: a
 LineRefineNet state_dict, or "procedural" for deterministic weights that exercise the path only)
@@ -16,6 +16,8 @@ every written frame with one metrics.evaluate_scenes call (clouds parsed on the 
 (pointnet_refine_amd/ground.py), instead of the detector's z = 0.
 --align writes the candidates with their x y moved onto the paint of each frame's own cloud
 (pointnet_refine_amd/align.py); the matches and everything else in the files stay as they are.
+--align-max-yaw RAD also sweeps a yaw of up to RAD radians about each frame's ego origin, for the
+heading error a shift cannot take out; the PAINT ALIGN line then carries the median and largest yaw.
 """
 import argparse
 import os
@@ -37,17 +39,23 @@ def main():
     ap.add_argument("--batched", action="store_true", help="--evaluate: one metrics.evaluate_scenes call for all frames")
     ap.add_argument("--lift", action="store_true", help="candidates carry the road height read from the cloud")
     ap.add_argument("--align", action="store_true", help="candidates are moved in x y onto the paint read from the cloud")
+    ap.add_argument("--align-max-yaw", type=float, default=0.0, metavar="RAD",
+                    help="with --align: also sweep a yaw of up to RAD radians about each frame's ego origin")
     args = ap.parse_args()
     from pointnet_refine_amd import io, metrics, predictions
     res = predictions.predictions_to_scenes(args.drive_dir, args.gt_json, args.results_json, args.out_dir, lift=args.lift,
-                                            align=args.align)
+                                            align=args.align, align_max_yaw=args.align_max_yaw)
     if args.lift and "lift" in res:
         rep = res["lift"]
         print(f"GROUND LIFT  {rep['lines_lifted']} of {rep['lines']} lines lifted   {rep['stations_without_ground']} of "
               f"{rep['stations']} stations without ground")
     if args.align and "align" in res:
         rep = res["align"]
-        print(f"PAINT ALIGN  {rep['frames_aligned']} of {rep['frames']} frames aligned")
+        yaw = ""
+        if args.align_max_yaw > 0.0:
+            a = np.abs(rep["yaws"]) if rep["frames"] else np.zeros(1)
+            yaw = f"   |yaw| median {float(np.median(a)) * 1e3:.1f} mrad   max {float(a.max()) * 1e3:.1f} mrad"
+        print(f"PAINT ALIGN  {rep['frames_aligned']} of {rep['frames']} frames aligned{yaw}")
     if args.evaluate is None:
         return
     import torch

@@ -6,7 +6,7 @@ frames into lanes and fused into one polyline per lane in the drive frame
     python examples/refine_predictions.py DRIVE_DIR RESULTS_JSON --checkpoint CKPT --out MAP.json
                                           [--gt GT_JSON] [--png DIR] [--batched] [--device-sync]
                                           [--support [--intensity-floor F]] [--lift [--lift-radius R]]
-                                          [--align [--align-max-shift M] [--align-scope frame|drive]]
+                                          [--align [--align-max-shift M] [--align-scope frame|drive] [--align-max-yaw RAD]]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; RESULTS_JSON is the detector's output
 (predictions.load_results); MAP.json gets the fused map in the drive file layout
@@ -27,6 +27,9 @@ every metre of every line is read from the frame's own cloud points within --lif
 component, under which the frame's bright cloud points lie closest to the lines
 (pointnet_refine_amd/align.py), per frame or - --align-scope drive - one for the whole drive; one
 PAINT ALIGN line says how many frames were aligned and the median and largest shift.
+--align-max-yaw RAD sweeps a yaw of up to RAD radians about each frame's ego origin together with the
+shift (a heading error of the extrinsic turns the lines about the sensor, and no shift takes that
+out); the PAINT ALIGN line then carries the median and largest yaw as well.
 --png DIR draws the fused map over a BEV intensity map of the merged cloud (bev.py).
 
 Without --checkpoint the model carries deterministic procedural weights (the run then exercises the
@@ -94,6 +97,8 @@ def main():
     ap.add_argument("--align", action="store_true", help="move the detector's lines in x y onto the paint of the cloud")
     ap.add_argument("--align-max-shift", type=float, default=1.0)
     ap.add_argument("--align-scope", choices=("frame", "drive"), default="frame")
+    ap.add_argument("--align-max-yaw", type=float, default=0.0, metavar="RAD",
+                    help="with --align: also sweep a yaw of up to RAD radians about each frame's ego origin")
     args = ap.parse_args()
 
     from pointnet_refine_amd import drive, fuse, link
@@ -101,7 +106,8 @@ def main():
                                   step=args.step, gate=args.gate, min_pieces=args.min_pieces, batched=args.batched,
                                   support=args.support, intensity_floor=args.intensity_floor,
                                   device_sync=args.device_sync, lift=args.lift, lift_radius=args.lift_radius,
-                                  align=args.align, align_max_shift=args.align_max_shift, align_scope=args.align_scope)
+                                  align=args.align, align_max_shift=args.align_max_shift, align_scope=args.align_scope,
+                                  align_max_yaw=args.align_max_yaw)
     rep = res["report"]
     if args.lift:
         print(f"GROUND LIFT  {rep['lift_lines_lifted']} of {rep['lift_lines']} lines lifted "
@@ -109,8 +115,12 @@ def main():
               f"{rep['lift_stations']} stations without ground")
     if args.align:
         norm = np.hypot(rep["align_shifts"][:, 0], rep["align_shifts"][:, 1]) if rep["align_frames"] else np.zeros(1)
+        yaw = ""
+        if args.align_max_yaw > 0.0:
+            a = np.abs(rep["align_yaws"]) if rep["align_frames"] else np.zeros(1)
+            yaw = f"   |yaw| median {float(np.median(a)) * 1e3:.1f} mrad   max {float(a.max()) * 1e3:.1f} mrad"
         print(f"PAINT ALIGN  {rep['align_frames_aligned']} of {rep['align_frames']} frames aligned   |shift| median "
-              f"{float(np.median(norm)):.3f} m   max {float(norm.max()):.3f} m   ({rep['align_candidates']} bright points)")
+              f"{float(np.median(norm)):.3f} m   max {float(norm.max()):.3f} m{yaw}   ({rep['align_candidates']} bright points)")
     print(f"{rep['slices']} frames, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['candidates']} candidate pairs, {rep['edges']} edges, {rep['clusters']} clusters, "
           f"{rep['clusters_kept']} kept ({rep['pieces_unlinked']} pieces unlinked), "

@@ -1210,6 +1210,91 @@ int prh_align_score(const void* records, const long long* cand_offsets, long lon
                     long long n_shifts, const double* reach, int n_slices, const long long* items, long long n_items,
                     double r2, long long* acc, int device, void* stream);
 
+/* Rigid paint alignment - the rule.
+ * A shift cannot take out a rotation: a heading error of the camera-lidar extrinsic, or of the
+ * matched pose, turns every line of a frame about the sensor, and at 15 mrad a line end 24 m out
+ * lies 0.36 m beside the paint.  This rule extends "Paint alignment - the rule" from shifts to poses
+ * (yaw about z plus an xy shift); its steps 1 and 3-5 hold verbatim (qi, the projection, d2min, qk,
+ * the int64 score and hits), and so do its conventions.  tests/_align_rigid_oracle.py restates it.
+ * Pose.  A pose row is (dx, dy, theta).  It moves a line vertex p to R(theta)(p - pivot) + pivot +
+ * (dx, dy); z never changes.  pivots [S,2] fp64, one per slice, default (0, 0): the sensor, which is
+ * where an extrinsic heading error turns the lines.  c = cos(theta) and s = sin(theta) are computed
+ * once on the host and go to the device and to the oracle as the same bits, in the table poses
+ * [K,4] fp64 = dx dy c s with pose_offsets [S+1] int64: the device never evaluates a sine.
+ * Limits: |theta| <= 0.1 rad, |dx|, |dy| <= 4, |pivot component| <= 1e6, at most
+ * prh_align_max_poses() = 32768 rows per slice (the default coarse table has 4851).
+ * 2'. Step 2 becomes: the point is moved by the inverse pose, one rounding per operation,
+ *       gx = (x - dx) - px            gy = (y - dy) - py
+ *       wx = (c * gx + s * gy) + px   wy = (c * gy - s * gx) + py        w = (wx, wy, z).
+ *    With pivot (0, 0), c = 1 and s = 0 this is w = (x - dx, y - dy, z) up to the sign of a zero,
+ *    which no later step sees: a table whose rows all have theta = 0 gives exactly
+ *    prh_align_score's integers.
+ * Per slice, on the host (align.pick_pose): steps 6-10 with three changes.
+ * 6'. The table must hold the pose (0, 0, 0); k0 is its first row.
+ * 8'. Of the near-best rows (keep = 63 / 64, exact integers) the one with the smallest dx * dx + dy *
+ *    dy + (lever * theta) * (lever * theta) in fp64, summed left to right, ties to the lowest row.
+ *    lever (default 25 m, the half length of a slice) turns a yaw into the lateral move of a line end.
+ * 9'. Bias.  With a lateral offset e0 and a yaw error phi a point at arc position t of a line (t
+ *    from the pivot, uniform over |t| <= lever) lies e0 + phi t beside the paint; the mean of its
+ *    square is e0^2 + phi^2 lever^2 / 3, so step 9's fall of the score reads (e0^2 + phi^2 lever^2 /
+ *    3) / r^2 / (1 - w^2 / (3 r^2)) and keep = 63 / 64 bounds it by 1 / 64: |e0| <= 0.13 r as
+ *    before and |phi| <= 0.13 r sqrt(3) / lever, 1.35 mrad at the defaults (r = 0.15, lever = 25),
+ *    just above one fine yaw step.  Both pull towards zero.  At a line end 24 m out the residual is
+ *    at most 0.13 r + 24 * 0.13 r sqrt(3) / lever + 24 * (half a fine yaw step) = 0.0195 + 0.0324 +
+ *    0.012 = 0.064 m.
+ * min_points (step 7) and gain (step 10) are unchanged.
+ * Grids (align.pose_grid: the yaw index outer, then shift_grid's x outer, y inner).  Coarse:
+ * shift_grid((0, 0), max_shift, 0.1) crossed with theta = j * 0.004, |theta| <= max_yaw (default
+ * 0.02: 441 x 11 = 4851 rows).  Fine: shift_grid(coarse pick, 0.1, 0.02) crossed with coarse theta
+ * + j * 0.001, |j| <= 4, the row (0, 0, 0) appended (1090 rows).  max_yaw = 0 gives the yaw grid {0}
+ * in both stages, and the whole procedure is then align_lines' bit for bit.  scope = 'drive' as in
+ * the shift rule.
+ * Applying the pick (align.apply_pose), with gx = x - px, gy = y - py:
+ *       x' = ((c * gx - s * gy) + px) + dx      y' = ((s * gx + c * gy) + py) + dy.
+ * Reach (cost only, but conservative).  reach [S] fp64 = ((radius + m) + a * (rho + radius)) + 1e-6
+ * with m = max_k max(|dx|, |dy|), a = max_k |theta| and rho the largest xy distance of a vertex of
+ * the slice from its pivot.  A hitter's w lies within radius of a point c of a segment, so |w -
+ * pivot| <= rho + radius (both ends of the segment are within rho of the pivot, and so is c); the
+ * rotation moves w by 2 sin(|theta| / 2) |w - pivot| <= a (rho + radius) and the shift by at most
+ * m per axis, so the unmoved x and y lie within reach of the box of the segment.  The 1e-6: every
+ * operation of step 2' and of the projection works on magnitudes up to 2e6 + 4 and rounds by at
+ * most ulp(2e6) / 2 = 1.2e-10; c and s carry 1.1e-16 relative each, 2.4e-10 at that magnitude; w
+ * takes six operations, h four more, rho one square root: below 3e-9 in all, and 1e-6 is kept from
+ * the shift rule with that margin.  With a = 0 the expression has slice_reach's bits.  The bitmaps
+ * and prh_align_select_count / _write are used unchanged with this reach.
+ *   prh_align_score_rigid   prh_align_score with the pose table and pivots [S,2]: the same work
+ *                           item (slice, 256 candidates, 16 poses); a thread computes its 16 (wx,
+ *                           wy) once from the pose rows, before the segment loop, and the loop is
+ *                           prh_align_score's.  poses must be 16-byte aligned.
+ *   prh_align_select_cells_count / _write   the select passes with one counter per bitmap cell:
+ *                           cell_counts [n_cells] int32 (zeroed here); with cell_offsets [n_cells+1]
+ *                           int64 their exclusive prefix (the caller scans), rows cell_offsets[c] ..
+ *                           cell_offsets[c+1] of records are cell c's survivors in the order of
+ *                           arrival.  Cells of a slice are contiguous from cell_base[s], so
+ *                           cand_offsets[s] = cell_offsets[cell_base[s]] and the records stay
+ *                           grouped by slice: a wave of the score kernel then holds neighbours on
+ *                           the road.  The rule does not see the order: the tables are bitwise
+ *                           equal either way.  PRH_ERR_WORKSPACE below
+ *                           prh_align_select_cells_workspace_bytes(n_cells). */
+int prh_align_max_poses(void);
+size_t prh_align_select_cells_workspace_bytes(long long n_cells);
+int prh_align_select_cells_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                                 long long n_points, const double* grid_origin, const int* grid_shape,
+                                 const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                                 double intensity_floor, int* cell_counts, int device, void* stream);
+int prh_align_select_cells_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                                 long long n_points, const double* grid_origin, const int* grid_shape,
+                                 const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                                 double intensity_floor, const long long* cell_offsets, void* records,
+                                 long long capacity, void* workspace, size_t workspace_bytes, int device,
+                                 void* stream);
+int prh_align_score_rigid(const void* records, const long long* cand_offsets, long long n_candidates,
+                          const double* line_vertices, long long n_vertices, const long long* line_offsets, int n_lines,
+                          const long long* slice_line_offsets, const double* poses, const long long* pose_offsets,
+                          long long n_poses, const double* pivots, const double* reach, int n_slices,
+                          const long long* items, long long n_items, double r2, long long* acc, int device,
+                          void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

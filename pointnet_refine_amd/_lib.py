@@ -107,6 +107,8 @@ EXPORTS = [
     "prh_ground_query",
     "prh_align_tile", "prh_align_max_shifts", "prh_align_select_workspace_bytes", "prh_align_select_count",
     "prh_align_select_write", "prh_align_score",
+    "prh_align_max_poses", "prh_align_select_cells_workspace_bytes", "prh_align_select_cells_count",
+    "prh_align_select_cells_write", "prh_align_score_rigid",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -497,6 +499,18 @@ def _bind(lib):
     lib.prh_align_select_write.argtypes = [vp, i, vp, i, ll, vp, vp, vp, vp, ll, dbl, dbl, vp, vp, ll, vp, sz, i, vp]
     lib.prh_align_score.restype = i
     lib.prh_align_score.argtypes = [vp, vp, ll, vp, ll, vp, i, vp, vp, vp, ll, vp, i, vp, ll, dbl, vp, i, vp]
+    if not hasattr(lib, "prh_align_score_rigid"):
+        return lib      # an older build under PRH_LIB_PATH (A/B runs): it has no rigid paint alignment
+    lib.prh_align_max_poses.restype = i
+    lib.prh_align_max_poses.argtypes = []
+    lib.prh_align_select_cells_workspace_bytes.restype = sz
+    lib.prh_align_select_cells_workspace_bytes.argtypes = [ll]
+    lib.prh_align_select_cells_count.restype = i
+    lib.prh_align_select_cells_count.argtypes = [vp, i, vp, i, ll, vp, vp, vp, vp, ll, dbl, dbl, vp, i, vp]
+    lib.prh_align_select_cells_write.restype = i
+    lib.prh_align_select_cells_write.argtypes = [vp, i, vp, i, ll, vp, vp, vp, vp, ll, dbl, dbl, vp, vp, ll, vp, sz, i, vp]
+    lib.prh_align_score_rigid.restype = i
+    lib.prh_align_score_rigid.argtypes = [vp, vp, ll, vp, ll, vp, i, vp, vp, vp, ll, vp, vp, i, vp, ll, dbl, vp, i, vp]
     return lib
 
 

@@ -20,8 +20,22 @@ alignment - the rule", and restated in ``tests/_align_oracle.py``).  It is the x
 
     shifted, report = align_lines(points, offsets, [[pixel_to_ego(px) for px in frame] for frame in frames])
 
-paint_scores and align_lines have no CPU fallback: without a GPU they raise RuntimeError.
+The rigid twin ("Rigid paint alignment - the rule") sweeps poses (dx, dy, theta): a yaw about a
+per-slice pivot - the sensor - plus the shift, for the heading error a shift cannot take out.
+
+  pose_grid        host: shift_grid crossed with a grid of yaws, the yaw index outer (numpy)
+  pose_table       host: (K,3) dx dy theta -> (K,4) dx dy cos sin, the bits the device and the oracle get
+  rigid_reach      host: per slice the reach of a pose table (conservative; cost only)
+  rigid_scores     HIP: the candidate filter in cell or arrival order, then prh_align_score_rigid
+  pick_pose        host: pick_shift with the norm dx^2 + dy^2 + (lever theta)^2
+  apply_pose       host: a pose applied to (n,3) vertices
+  align_lines_rigid  the coarse and the fine rigid_scores call with their picks
+
+paint_scores, rigid_scores, align_lines and align_lines_rigid have no CPU fallback: without a GPU
+they raise RuntimeError.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -43,6 +57,12 @@ GAIN = (5, 4)
 COARSE_HALF, COARSE_STEP = 1.0, 0.1
 FINE_HALF, FINE_STEP = 0.1, 0.02
 CANDIDATES, SHIFTS = 256, 16     # a work item of prh_align_score
+MAX_YAW = 0.1                # |theta| of a pose row, radians
+MAX_POSES = 32768            # prh_align_max_poses(): rows of one slice's pose table
+LEVER = 25.0                 # metres: the half length of a slice; what a radian of yaw moves a line end by
+COARSE_YAW, COARSE_YAW_STEP = 0.02, 0.004
+FINE_YAW_HALF, FINE_YAW_STEP = 0.004, 0.001
+ORDER = "cell"               # rigid_scores' default candidate order (DESIGN.md 4u has the measurement)
 
 
 # ------------------------------------------------------------------ host side
@@ -379,3 +399,283 @@ def align_lines(points, slice_offsets, lines_per_slice, max_shift=COARSE_HALF, r
               "score_best": np.array([p["score_best"] for p in picks], dtype=np.int64),
               "candidates": int(np.sum(cands))}
     return lines, report
+
+
+# ------------------------------------------------------------------ rigid: host side
+def pose_grid(centre=(0.0, 0.0), half=COARSE_HALF, step=COARSE_STEP, yaw_centre=0.0, yaw_half=COARSE_YAW,
+              yaw_step=COARSE_YAW_STEP):
+    """((2m+1) (2n+1)^2, 3) float64 dx dy theta: shift_grid(centre, half, step) under every yaw
+    yaw_centre + j * yaw_step, j = -m .. m with m = round(yaw_half / yaw_step); the yaw index runs
+    outer.  yaw_half = 0 gives the one yaw yaw_centre."""
+    yaw_centre, yaw_half, yaw_step = float(yaw_centre), float(yaw_half), float(yaw_step)
+    if not (yaw_step > 0.0 and np.isfinite(yaw_step) and yaw_half >= 0.0 and np.isfinite(yaw_half)
+            and np.isfinite(yaw_centre)):
+        raise ValueError("pose_grid: yaw_step > 0 and yaw_half >= 0")
+    sh = shift_grid(centre, half, step)
+    m = int(round(yaw_half / yaw_step))
+    th = yaw_centre + np.arange(-m, m + 1, dtype=np.float64) * yaw_step
+    return np.concatenate([np.tile(sh, (len(th), 1)), np.repeat(th, len(sh))[:, None]], axis=1)
+
+
+def pose_table(poses):
+    """(K,3) dx dy theta -> (K,4) float64 dx dy cos(theta) sin(theta): the table the device and the
+    oracle take.  math.cos and math.sin, once per distinct theta."""
+    ps = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    uniq, inv = np.unique(np.ascontiguousarray(ps[:, 2]).view(np.int64), return_inverse=True)   # as bits: -0.0 is not 0.0
+    cs = np.array([[math.cos(float(v)), math.sin(float(v))] for v in uniq.view(np.float64)], dtype=np.float64).reshape(-1, 2)
+    return np.ascontiguousarray(np.concatenate([ps[:, :2], cs[inv.reshape(-1)]], axis=1))
+
+
+def _pivots(pivots, n_s, what):
+    if pivots is None:
+        return np.zeros((n_s, 2))
+    shape = tuple(pivots.shape) if torch.is_tensor(pivots) else np.shape(pivots)
+    if shape != (n_s, 2):
+        raise ValueError(f"{what}: pivots must be ({n_s},2) x y, one per slice, got {shape}")
+    pv = np.ascontiguousarray(_host(pivots, np.float64).reshape(n_s, 2))
+    if not (np.isfinite(pv).all() and (n_s == 0 or np.abs(pv).max() <= MAX_COORD)):
+        raise ValueError(f"{what}: pivots must be finite and within {MAX_COORD:g} m of the slice's origin")
+    return pv
+
+
+def rigid_reach(poses, pose_offsets, radius, vertices, line_offsets, slice_line_offsets, pivots):
+    """(S,) float64: ((radius + m) + a * (rho + radius)) + GUARD per slice, m = max_k max(|dx|, |dy|)
+    and a = max_k |theta| over the slice's own rows of poses (K,3), rho the largest xy distance of a
+    vertex of the slice from its pivot ("Rigid paint alignment - the rule", Reach).  With a = 0 these
+    are slice_reach's bits."""
+    ps = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    off = np.asarray(pose_offsets, dtype=np.int64).reshape(-1)
+    n_s = len(off) - 1
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    pv = np.asarray(pivots, dtype=np.float64).reshape(n_s, 2)
+    v_off = np.asarray(line_offsets, dtype=np.int64)[np.asarray(slice_line_offsets, dtype=np.int64)]
+    big, yaw, rho = np.zeros(n_s), np.zeros(n_s), np.zeros(n_s)
+    used = np.flatnonzero(np.diff(off) > 0)
+    if len(used):
+        big[used] = np.maximum.reduceat(np.abs(ps[:, :2]).max(axis=1), off[:-1][used])
+        yaw[used] = np.maximum.reduceat(np.abs(ps[:, 2]), off[:-1][used])
+    used = np.flatnonzero(np.diff(v_off) > 0)
+    if len(used):
+        g = v[:, :2] - np.repeat(pv, np.diff(v_off), axis=0)
+        rho[used] = np.maximum.reduceat(np.sqrt(g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]), v_off[:-1][used])
+    return ((float(radius) + big) + yaw * (rho + float(radius))) + GUARD
+
+
+def pick_pose(poses, score, hits, lever=LEVER, min_points=MIN_POINTS, keep=KEEP, gain=GAIN):
+    """Steps 6'-10 of the rigid rule over one table.  poses (K,3) float64 dx dy theta, score and hits
+    (K,) integers.  Returns {'pose' (3,) float64, 'row' (the accepted row, or k0), 'aligned' bool,
+    'score_zero', 'score_best' (Python ints: the score at (0, 0, 0) and at the near-best row)}."""
+    what = "pick_pose"
+    ps = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    sc = [int(x) for x in np.asarray(score).reshape(-1)]
+    ht = [int(x) for x in np.asarray(hits).reshape(-1)]
+    if not (len(ps) == len(sc) == len(ht)):
+        raise ValueError(f"{what}: one score and one hit count per pose")
+    keep_num, keep_den = _ratio(keep, what, "keep", False)
+    gain_num, gain_den = _ratio(gain, what, "gain", True)
+    if int(min_points) != min_points or int(min_points) < 1:
+        raise ValueError(f"{what}: min_points must be an integer >= 1")
+    lever = float(lever)
+    if not (np.isfinite(lever) and lever > 0.0):
+        raise ValueError(f"{what}: lever must be positive and finite")
+    zero = np.flatnonzero((ps[:, 0] == 0.0) & (ps[:, 1] == 0.0) & (ps[:, 2] == 0.0))
+    if len(zero) == 0:
+        raise ValueError(f"{what}: the table must contain the pose (0, 0, 0)")
+    k0 = int(zero[0])
+    none = {"pose": np.zeros(3), "row": k0, "aligned": False, "score_zero": sc[k0], "score_best": sc[k0]}
+    best = max(sc)
+    if best == 0 or ht[sc.index(best)] < int(min_points):
+        return none
+    near = [k for k in range(len(sc)) if sc[k] * keep_den >= best * keep_num]
+    lt = lever * ps[near, 2]
+    n2 = ps[near, 0] * ps[near, 0] + ps[near, 1] * ps[near, 1] + lt * lt
+    row = near[int(np.argmin(n2))]                           # argmin: the first of equal values, the lowest row
+    none["score_best"] = sc[row]
+    if not sc[row] * gain_den > sc[k0] * gain_num:
+        return none
+    return {"pose": ps[row].copy(), "row": row, "aligned": True, "score_zero": sc[k0], "score_best": sc[row]}
+
+
+def apply_pose(vertices, pose, pivot=(0.0, 0.0)):
+    """(n,3) float64: the vertices under the pose (dx, dy, theta) about pivot - x' = ((c gx - s gy) +
+    px) + dx, y' = ((s gx + c gy) + py) + dy with g = vertex - pivot, z untouched.  A new array."""
+    v = np.array(vertices, dtype=np.float64).reshape(-1, 3)
+    dx, dy, th = (float(x) for x in pose)
+    c, s = math.cos(th), math.sin(th)
+    px, py = float(pivot[0]), float(pivot[1])
+    gx, gy = v[:, 0] - px, v[:, 1] - py
+    x = ((c * gx - s * gy) + px) + dx
+    y = ((s * gx + c * gy) + py) + dy
+    v[:, 0], v[:, 1] = x, y
+    return v
+
+
+# ------------------------------------------------------------------ rigid: GPU side
+def prepare_rigid(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots, radius, intensity_floor, cell, what):
+    """prepare for a pose table: 'sh' is the (K,4) table dx dy c s, 'reach' the rigid reach, 'pivots' (S,2)."""
+    radius, intensity_floor, cell = _params(radius, intensity_floor, cell, what)
+    dev = G.device("align", points.device if torch.is_tensor(points) and points.is_cuda else None)
+    pts = _points(points, dev, what)
+    off = _offsets(slice_offsets, pts.shape[0], what, "slice_offsets")
+    n_s = len(off) - 1
+    if len(lines_per_slice) != n_s:
+        raise ValueError(f"{what}: one list of lines per slice ({n_s}), got {len(lines_per_slice)}")
+    verts, l_off, sl_off = lines_csr(lines_per_slice, what)
+    shape = tuple(poses.shape) if torch.is_tensor(poses) else np.shape(poses)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{what}: poses must be (K,3) dx dy theta, got {shape}")
+    ps = np.ascontiguousarray(_host(poses, np.float64).reshape(-1, 3))
+    if not (np.isfinite(ps).all() and (len(ps) == 0 or (np.abs(ps[:, :2]).max() <= MAX_SHIFT
+                                                        and np.abs(ps[:, 2]).max() <= MAX_YAW))):
+        raise ValueError(f"{what}: poses must be finite with |dx|, |dy| <= {MAX_SHIFT:g} and |theta| <= {MAX_YAW:g}")
+    k_off = _offsets(pose_offsets, len(ps), what, "pose_offsets")
+    if len(k_off) != len(off):
+        raise ValueError(f"{what}: slice_offsets and pose_offsets must describe the same slices")
+    if n_s and int(np.diff(k_off).max()) > MAX_POSES:
+        raise ValueError(f"{what}: at most {MAX_POSES} poses per slice")
+    pv = _pivots(pivots, n_s, what)
+    reach = rigid_reach(ps, k_off, radius, verts, l_off, sl_off, pv)
+    maps = segment_bitmaps(verts, l_off, sl_off, reach, cell)
+    return {"dev": dev, "pts": pts, "off": off, "n_s": n_s, "verts": verts, "l_off": l_off, "sl_off": sl_off,
+            "sh": pose_table(ps), "k_off": k_off, "reach": reach, "maps": maps, "radius": radius, "pivots": pv,
+            "intensity_floor": intensity_floor, "what": what}
+
+
+def select_candidates_cells(p):
+    """prh_align_select_cells_count, the scan, prh_align_select_cells_write: what select_candidates
+    returns, a slice's records in ascending cell order (arrival order inside a cell)."""
+    lib, dev, pts, maps, n_s = L.lib(), p["dev"], p["pts"], p["maps"], p["n_s"]
+    n_cells = maps["n_cells"]
+    if n_s == 0 or pts.shape[0] == 0 or n_cells == 0:
+        return torch.empty((0, 4), dtype=torch.float64, device=dev), None, np.zeros(n_s + 1, dtype=np.int64)
+    counts = torch.zeros((n_cells,), dtype=torch.int32, device=dev)
+    off_t = torch.from_numpy(p["off"]).to(dev)
+    g_t = tuple(torch.from_numpy(np.ascontiguousarray(maps[k])).to(dev) for k in ("origin", "shape", "cell_base"))
+    bitmap = torch.from_numpy(maps["bitmap"].view(np.int32)).to(dev)
+    args = (G.ptr(pts), 1 if pts.dtype == torch.float64 else 0, G.ptr(off_t), n_s, pts.shape[0], G.ptr(g_t[0]), G.ptr(g_t[1]),
+            G.ptr(g_t[2]), G.ptr(bitmap), n_cells, maps["cell"], p["intensity_floor"])
+    L.check(lib.prh_align_select_cells_count(*args, G.ptr(counts), dev.index, G.stream(dev)), "prh_align_select_cells_count")
+    cell_off = G.exclusive_scan(counts)
+    # cells of a slice are contiguous from cell_base[s]: the slice's rows start at the scan there
+    cand_off = torch.cat([cell_off[g_t[2]], cell_off[-1:]]).contiguous()
+    c_off = cand_off.cpu().numpy()
+    total = int(c_off[-1])
+    rec = torch.empty((total, 4), dtype=torch.float64, device=dev)
+    if total:
+        nb = lib.prh_align_select_cells_workspace_bytes(n_cells)
+        ws = G.workspace(nb, dev)
+        L.check(lib.prh_align_select_cells_write(*args, G.ptr(cell_off), G.ptr(rec), total, G.ptr(ws), nb, dev.index,
+                                                 G.stream(dev)), "prh_align_select_cells_write")
+    return rec, cand_off, c_off
+
+
+def score_candidates_rigid(p, rec, cand_off, c_off):
+    """The plan and prh_align_score_rigid over the selected candidates: acc (K,2) int64 CUDA."""
+    dev, table = p["dev"], p["sh"]
+    acc = torch.zeros((len(table), 2), dtype=torch.int64, device=dev)
+    if p["n_s"] and int((np.diff(c_off) * np.diff(p["sl_off"])).max()) >= 2 ** 31:
+        raise OverflowError(f"{p['what']}: a slice has 2^31 or more (candidate, line) pairs")
+    items = work_items(c_off, p["k_off"], np.diff(p["l_off"][p["sl_off"]]))
+    if rec.shape[0] == 0 or len(items) == 0:
+        return acc
+    up = [torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+          for x in (p["verts"], p["l_off"], p["sl_off"], table, p["k_off"], p["pivots"], p["reach"], items)]
+    L.check(L.lib().prh_align_score_rigid(G.ptr(rec), G.ptr(cand_off), rec.shape[0], G.ptr(up[0]), len(p["verts"]),
+                                          G.ptr(up[1]), len(p["l_off"]) - 1, G.ptr(up[2]), G.ptr(up[3]), G.ptr(up[4]),
+                                          len(table), G.ptr(up[5]), G.ptr(up[6]), p["n_s"], G.ptr(up[7]), len(items),
+                                          p["radius"] * p["radius"], G.ptr(acc), dev.index, G.stream(dev)),
+            "prh_align_score_rigid")
+    return acc
+
+
+def _rigid(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots, radius, intensity_floor, cell, order, what):
+    if order not in ("cell", "arrival"):
+        raise ValueError(f"{what}: order must be 'cell' or 'arrival'")
+    p = prepare_rigid(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots, radius, intensity_floor, cell, what)
+    rec, cand_off, c_off = select_candidates_cells(p) if order == "cell" else select_candidates(p)
+    acc = score_candidates_rigid(p, rec, cand_off, c_off)
+    return {"score": acc[:, 0], "hits": acc[:, 1], "candidates": np.diff(c_off)}
+
+
+def rigid_scores(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots=None, radius=RADIUS,
+                 intensity_floor=0.0, cell=CELL, order=ORDER):
+    """The paint score of every (slice, pose) ("Rigid paint alignment - the rule", steps 1-5).
+
+    points, slice_offsets, lines_per_slice, radius, intensity_floor, cell: as paint_scores takes
+    them.  poses (K,3) float64 dx dy theta grouped by slice with pose_offsets (S+1,): |dx|, |dy| <= 4,
+    |theta| <= 0.1 rad, at most MAX_POSES rows per slice.  A pose moves a line vertex p to R(theta)(p
+    - pivot) + pivot + (dx, dy); pivots (S,2), one per slice, default (0, 0).  The cosine and sine go
+    to the device as pose_table computes them.  order: 'cell' hands the score kernel each slice's
+    candidates sorted by bitmap cell, 'arrival' in the order select_candidates leaves them - cost
+    only, the tables are bitwise equal.  Returns a dict of CUDA tensors 'score' (K,) int64 and 'hits'
+    (K,) int64.  A table whose thetas are all 0, with the default pivots, gives paint_scores'
+    integers."""
+    res = _rigid(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots, radius, intensity_floor, cell, order,
+                 "rigid_scores")
+    return {"score": res["score"], "hits": res["hits"]}
+
+
+def _stage_rigid(points, off, lines, tables, pivots, scope, radius, intensity_floor, lever, pick_kw, what):
+    """_stage for pose tables."""
+    n_s = len(lines)
+    if n_s == 0:
+        return [], np.zeros(0, dtype=np.int64)
+    k_off = np.zeros(n_s + 1, dtype=np.int64)
+    k_off[1:] = np.cumsum([len(t) for t in tables])
+    res = _rigid(points, off, lines, np.concatenate(tables), k_off, pivots, radius, intensity_floor, CELL, ORDER, what)
+    score, hits = res["score"].cpu().numpy(), res["hits"].cpu().numpy()
+    if scope == "drive":
+        k = len(tables[0])
+        one = pick_pose(tables[0], [int(x) for x in score.reshape(n_s, k).astype(object).sum(axis=0)],
+                        [int(x) for x in hits.reshape(n_s, k).astype(object).sum(axis=0)], lever, **pick_kw)
+        picks = [one] * n_s
+    else:
+        picks = [pick_pose(tables[s], score[k_off[s]:k_off[s + 1]], hits[k_off[s]:k_off[s + 1]], lever, **pick_kw)
+                 for s in range(n_s)]
+    return picks, res["candidates"]
+
+
+def align_lines_rigid(points, slice_offsets, lines_per_slice, max_shift=COARSE_HALF, max_yaw=COARSE_YAW, lever=LEVER,
+                      radius=RADIUS, intensity_floor=0.0, scope="frame", min_points=MIN_POINTS, keep=KEEP, gain=GAIN,
+                      pivots=None):
+    """Put every line on the paint of its own slice by a yaw about the slice's pivot and a shift.
+
+    align_lines with pose tables.  Coarse: pose_grid((0, 0), max_shift, 0.1, 0, max_yaw, 0.004) (441 x
+    11 rows at the defaults); fine: pose_grid(coarse shift, 0.1, 0.02, coarse theta, 0.004, 0.001)
+    with the row (0, 0, 0) appended; the picks are pick_pose's (lever, min_points, keep, gain).
+    max_yaw = 0 leaves the one yaw 0 in both stages: the result is then align_lines', bit for bit.
+    pivots (S,2): the point of every slice's frame the yaw turns about, default (0, 0), the sensor.
+    x and y of every vertex move by apply_pose; z never changes.  Returns (the moved (n,3) float64
+    lines in the same nesting, report: align_lines' keys plus 'yaws' (S,) float64)."""
+    what = "align_lines_rigid"
+    G.device("align")
+    if scope not in ("frame", "drive"):
+        raise ValueError(f"{what}: scope must be 'frame' or 'drive'")
+    max_shift, max_yaw = float(max_shift), float(max_yaw)
+    if not (np.isfinite(max_shift) and 0.0 < max_shift <= MAX_SHIFT - FINE_HALF):
+        raise ValueError(f"{what}: 0 < max_shift <= {MAX_SHIFT - FINE_HALF}")
+    if not (np.isfinite(max_yaw) and 0.0 <= max_yaw <= MAX_YAW - FINE_YAW_HALF):
+        raise ValueError(f"{what}: 0 <= max_yaw <= {MAX_YAW - FINE_YAW_HALF}")
+    coarse = pose_grid((0.0, 0.0), max_shift, COARSE_STEP, 0.0, max_yaw, COARSE_YAW_STEP)
+    if len(coarse) > MAX_POSES:
+        raise ValueError(f"{what}: max_shift and max_yaw give {len(coarse)} coarse poses, at most {MAX_POSES}")
+    pick_kw = {"min_points": min_points, "keep": keep, "gain": gain}
+    pick_pose(np.zeros((1, 3)), [0], [0], lever, **pick_kw)   # validates lever, min_points, keep and gain
+    lines = [[np.array(v, dtype=np.float64).reshape(-1, 3) for v in ls] for ls in lines_per_slice]
+    n_s = len(lines)
+    off = _host(slice_offsets, np.int64).reshape(-1)
+    pv = _pivots(pivots, n_s, what)
+    fine_yaw = FINE_YAW_HALF if max_yaw > 0.0 else 0.0
+    first, _ = _stage_rigid(points, off, lines, [coarse] * n_s, pv, scope, radius, intensity_floor, lever, pick_kw, what)
+    fine = [np.concatenate([pose_grid(p["pose"][:2], FINE_HALF, FINE_STEP, p["pose"][2], fine_yaw, FINE_YAW_STEP),
+                            np.zeros((1, 3))]) for p in first]
+    picks, cands = _stage_rigid(points, off, lines, fine, pv, scope, radius, intensity_floor, lever, pick_kw, what)
+    poses = np.array([p["pose"] for p in picks], dtype=np.float64).reshape(n_s, 3)
+    moved = [[apply_pose(v, poses[s], pv[s]) for v in ls] for s, ls in enumerate(lines)]
+    aligned = int(sum(1 for p in picks if p["aligned"]))
+    report = {"frames": n_s, "frames_aligned": aligned, "frames_unaligned": n_s - aligned,
+              "shifts": np.ascontiguousarray(poses[:, :2]), "yaws": np.ascontiguousarray(poses[:, 2]),
+              "score_zero": np.array([p["score_zero"] for p in picks], dtype=np.int64),
+              "score_best": np.array([p["score_best"] for p in picks], dtype=np.int64),
+              "candidates": int(np.sum(cands))}
+    return moved, report

@@ -15,7 +15,14 @@
 //                    that vertex (a, b, L2, line id; L2 = 0 where the line ends there).  d2min per
 //                    shift is carried across tiles and flushed when the line id changes or the list
 //                    ends.  Per shift: integer wave reduction, LDS, one 64-bit integer atomicAdd per
-//                    (block, shift, column).
+//                    (block, shift, column).  align_score_kernel<RIGID=true> is the same kernel
+//                    for "Rigid paint alignment - the rule": the table's rows are dx dy c s, the
+//                    slice has a pivot, and the 16 (wx, wy) come from the inverse pose; the
+//                    segment loop does not know the difference.
+//   align_select_cells_kernel<WRITE>  the select walk with one counter per bitmap cell instead of
+//                    one per slice: count, the caller's scan, write with a per-cell cursor.  A
+//                    slice's survivors then lie in ascending cell order (arrival order inside a
+//                    cell), so a wave of the score kernel holds neighbours on the road.
 // Every accumulated quantity is an integer, so no output depends on the order of the candidates,
 // on the filter, on the tiles or on the launch shape.  The geometry is fp64 with FMA contraction off.
 #pragma once
@@ -31,6 +38,7 @@ constexpr int ALIGN_WAVES = ALIGN_THREADS / 64;
 constexpr int ALIGN_SHIFTS = 16;         // shifts per work item
 constexpr int ALIGN_TILE = 512;          // vertex slots per LDS round (8 doubles each: 32 KB)
 constexpr int ALIGN_MAX_SHIFTS = 4096;   // shifts per slice
+constexpr int ALIGN_MAX_POSES = 32768;   // pose rows per slice
 
 struct AlignRecord { double x, y, z; long long qi; };      // 32 bytes, 16-byte aligned
 
@@ -56,6 +64,30 @@ __device__ __forceinline__ long long align_qi(double intensity, double intensity
   return (long long)rint(wi * 256.0);
 }
 
+// steps 1 of the rule and the bitmap lookup for flat row i: true for a survivor, with its slice s,
+// its cell c (global, < n_cells), x y z and qi
+template <typename T>
+__device__ __forceinline__ bool align_select_test(
+    const T* __restrict__ pts, const long long* __restrict__ slice_off, int S, long long n, long long i,
+    const double* __restrict__ origin, const int* __restrict__ shape, const long long* __restrict__ cell_base,
+    const unsigned* __restrict__ bitmap, long long n_cells, double cell, double intensity_floor, int& s, long long& c,
+    double& x, double& y, double& z, long long& qi) {
+#pragma clang fp contract(off)
+  if (i >= n) return false;
+  double w;
+  AlignPoint<T>::load(pts + 4 * i, x, y, z, w);
+  if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
+  qi = align_qi(w, intensity_floor);
+  if (qi <= 0) return false;
+  s = bev_slice_of(slice_off, S, i);
+  const int nx = shape[2 * s], ny = shape[2 * s + 1];
+  const double fx = floor((x - origin[2 * s]) / cell), fy = floor((y - origin[2 * s + 1]) / cell);
+  if (!(fx >= 0.0 && fx < (double)nx && fy >= 0.0 && fy < (double)ny)) return false;
+  c = cell_base[s] + (long long)fy * nx + (long long)fx;
+  if (c < 0 || c >= n_cells) return false;
+  return (bitmap[c >> 5] >> (unsigned)(c & 31)) & 1u;
+}
+
 // grid of slice s: origin[2s], origin[2s+1] = x0 y0, shape[2s], shape[2s+1] = nx ny, cell
 // cell_base[s] + iy * nx + ix is bit (c & 31) of bitmap[c >> 5].  counter [S]: the counts, or the cursors.
 template <typename T, bool WRITE>
@@ -68,25 +100,11 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_select_kernel(
 #pragma clang fp contract(off)
   const long long i = (long long)blockIdx.x * ALIGN_THREADS + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  bool keep = false;
   int s = 0;
-  double x = 0.0, y = 0.0, z = 0.0, w = 0.0;
-  long long qi = 0;
-  if (i < n) {
-    AlignPoint<T>::load(pts + 4 * i, x, y, z, w);
-    if (isfinite(x) && isfinite(y) && isfinite(z)) {
-      qi = align_qi(w, intensity_floor);
-      if (qi > 0) {
-        s = bev_slice_of(slice_off, S, i);
-        const int nx = shape[2 * s], ny = shape[2 * s + 1];
-        const double fx = floor((x - origin[2 * s]) / cell), fy = floor((y - origin[2 * s + 1]) / cell);
-        if (fx >= 0.0 && fx < (double)nx && fy >= 0.0 && fy < (double)ny) {
-          const long long c = cell_base[s] + (long long)fy * nx + (long long)fx;
-          if (c >= 0 && c < n_cells) keep = (bitmap[c >> 5] >> (unsigned)(c & 31)) & 1u;
-        }
-      }
-    }
-  }
+  long long c = 0, qi = 0;
+  double x = 0.0, y = 0.0, z = 0.0;
+  const bool keep = align_select_test<T>(pts, slice_off, S, n, i, origin, shape, cell_base, bitmap, n_cells, cell,
+                                         intensity_floor, s, c, x, y, z, qi);
   const unsigned long long m = __ballot(keep);
   if (m == 0ull) return;                                 // wave-uniform
   const int lead = __ffsll((long long)m) - 1;
@@ -111,6 +129,33 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_select_kernel(
   }
 }
 
+// counter [n_cells]: the counts, or the cursors; cell_off [n_cells+1]: the exclusive prefix of the
+// counts.  Cells of a slice are contiguous, so rows cell_off[cell_base[s]] .. are slice s's.
+template <typename T, bool WRITE>
+__global__ __launch_bounds__(ALIGN_THREADS) void align_select_cells_kernel(
+    const T* __restrict__ pts, const long long* __restrict__ slice_off, int S, long long n,
+    const double* __restrict__ origin, const int* __restrict__ shape, const long long* __restrict__ cell_base,
+    const unsigned* __restrict__ bitmap, long long n_cells, double cell, double intensity_floor,
+    int* __restrict__ counter, const long long* __restrict__ cell_off, AlignRecord* __restrict__ rec,
+    long long capacity) {
+  const long long i = (long long)blockIdx.x * ALIGN_THREADS + threadIdx.x;
+  int s = 0;
+  long long c = 0, qi = 0;
+  double x = 0.0, y = 0.0, z = 0.0;
+  if (!align_select_test<T>(pts, slice_off, S, n, i, origin, shape, cell_base, bitmap, n_cells, cell, intensity_floor, s,
+                            c, x, y, z, qi))
+    return;
+  const int k = atomicAdd(counter + c, 1);
+  if (WRITE) {
+    const long long pos = cell_off[c] + k;
+    if (pos < cell_off[c + 1] && pos < capacity) {
+      double2* r = reinterpret_cast<double2*>(rec + pos);
+      r[0] = make_double2(x, y);
+      r[1] = make_double2(z, __longlong_as_double(qi));
+    }
+  }
+}
+
 // the line of vertex v among lines lo .. hi-1 (line_off[lo] <= v < line_off[hi]): the last whose first vertex is <= v
 __device__ __forceinline__ int align_line_of(const long long* __restrict__ line_off, int lo, int hi, long long v) {
   while (hi - lo > 1) {
@@ -123,12 +168,16 @@ __device__ __forceinline__ int align_line_of(const long long* __restrict__ line_
 // items [n_items,3] int64 = (slice, first candidate, first shift): the candidates are rows of rec,
 // the shifts rows of shifts; the counts are what the slice has left, at most 256 and 16.
 // acc [n_shifts,2] int64 = score, hits; added to.
+// RIGID: shifts is the pose table [n_shifts,4] = dx dy c s and pivots [S,2] the slices' pivots; the
+// point is moved by the inverse pose ("Rigid paint alignment - the rule", step 2), once, before the loop.
+template <bool RIGID>
 __global__ __launch_bounds__(ALIGN_THREADS) void align_score_kernel(
     const AlignRecord* __restrict__ rec, const long long* __restrict__ cand_off, long long n_cand,
     const double* __restrict__ verts, long long n_verts, const long long* __restrict__ line_off, int n_lines,
     const long long* __restrict__ slice_line_off, const double* __restrict__ shifts,
     const long long* __restrict__ shift_off, long long n_shifts, const double* __restrict__ reach, int S,
-    const long long* __restrict__ items, double r2, unsigned long long* __restrict__ acc) {
+    const long long* __restrict__ items, double r2, unsigned long long* __restrict__ acc,
+    const double* __restrict__ pivots) {
 #pragma clang fp contract(off)
   __shared__ double tile[ALIGN_TILE * 8];                // ax ay az bx by bz L2 line
   __shared__ long long red[ALIGN_WAVES][ALIGN_SHIFTS][2];
@@ -157,13 +206,21 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_score_kernel(
     const double2 a = r[0], b = r[1];
     x = a.x; y = a.y; z = b.x; qi = __double_as_longlong(b.y);
   }
+  const double pvx = RIGID ? pivots[2 * s] : 0.0, pvy = RIGID ? pivots[2 * s + 1] : 0.0;
   double wx[ALIGN_SHIFTS], wy[ALIGN_SHIFTS], d2m[ALIGN_SHIFTS];
   long long score[ALIGN_SHIFTS];
   int hits[ALIGN_SHIFTS];
 #pragma unroll
   for (int k = 0; k < ALIGN_SHIFTS; ++k) {
     const long long row = k0 + (k < nk ? k : 0);         // a short tile repeats its first shift; not stored
-    wx[k] = x - shifts[2 * row]; wy[k] = y - shifts[2 * row + 1];
+    if (RIGID) {
+      const double2* pose = reinterpret_cast<const double2*>(shifts) + 2 * row;
+      const double2 d = pose[0], cs = pose[1];
+      const double gx = (x - d.x) - pvx, gy = (y - d.y) - pvy;
+      wx[k] = (cs.x * gx + cs.y * gy) + pvx; wy[k] = (cs.x * gy - cs.y * gx) + pvy;
+    } else {
+      wx[k] = x - shifts[2 * row]; wy[k] = y - shifts[2 * row + 1];
+    }
     d2m[k] = inf; score[k] = 0; hits[k] = 0;
   }
 

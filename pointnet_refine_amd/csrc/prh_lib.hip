@@ -3844,10 +3844,97 @@ int prh_align_score(const void* records, const long long* cand_offsets, long lon
     return fail(PRH_ERR_ARG, "align_score: null pointer");
   if (((uintptr_t)records & 15) != 0) return fail(PRH_ERR_ARG, "align_score: records must be 16-byte aligned");
   HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(align_score_kernel, dim3((unsigned)n_items), dim3(ALIGN_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(align_score_kernel<false>, dim3((unsigned)n_items), dim3(ALIGN_THREADS), 0, (hipStream_t)stream,
                      (const AlignRecord*)records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets,
                      n_lines, slice_line_offsets, shifts, shift_offsets, n_shifts, reach, n_slices, items, r2,
-                     (unsigned long long*)acc);
+                     (unsigned long long*)acc, (const double*)nullptr);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ rigid paint alignment
+int prh_align_max_poses(void) { return ALIGN_MAX_POSES; }
+size_t prh_align_select_cells_workspace_bytes(long long n_cells) {
+  return n_cells < 0 ? 0 : align_up((size_t)n_cells * sizeof(int), 256);
+}
+int prh_align_select_cells_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                                 long long n_points, const double* grid_origin, const int* grid_shape,
+                                 const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                                 double intensity_floor, int* cell_counts, int device, void* stream) {
+  TRY_RC(align_check_select("align_select_cells_count", points, is_double, slice_offsets, n_slices, n_points,
+                            grid_origin, grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor));
+  if (n_slices == 0 || n_cells == 0) return PRH_OK;
+  if (!cell_counts) return fail(PRH_ERR_ARG, "align_select_cells_count: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(cell_counts, 0, (size_t)n_cells * sizeof(int), st));
+  if (n_points == 0) return PRH_OK;
+  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
+  if (is_double)
+    hipLaunchKernelGGL((align_select_cells_kernel<double, false>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
+                       (const double*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                       bitmap, n_cells, cell, intensity_floor, cell_counts, (const long long*)nullptr,
+                       (AlignRecord*)nullptr, 0ll);
+  else
+    hipLaunchKernelGGL((align_select_cells_kernel<float, false>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
+                       (const float*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                       bitmap, n_cells, cell, intensity_floor, cell_counts, (const long long*)nullptr,
+                       (AlignRecord*)nullptr, 0ll);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_align_select_cells_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                                 long long n_points, const double* grid_origin, const int* grid_shape,
+                                 const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                                 double intensity_floor, const long long* cell_offsets, void* records,
+                                 long long capacity, void* workspace, size_t workspace_bytes, int device,
+                                 void* stream) {
+  TRY_RC(align_check_select("align_select_cells_write", points, is_double, slice_offsets, n_slices, n_points,
+                            grid_origin, grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor));
+  if (capacity < 0) return fail(PRH_ERR_ARG, "align_select_cells_write: bad capacity");
+  if (n_slices == 0 || n_points == 0 || n_cells == 0 || capacity == 0) return PRH_OK;
+  if (!cell_offsets || !records) return fail(PRH_ERR_ARG, "align_select_cells_write: null pointer");
+  if (((uintptr_t)records & 15) != 0)
+    return fail(PRH_ERR_ARG, "align_select_cells_write: records must be 16-byte aligned");
+  if (!workspace || workspace_bytes < prh_align_select_cells_workspace_bytes(n_cells))
+    return fail(PRH_ERR_WORKSPACE, "align_select_cells_write: workspace too small (%zu bytes)", workspace_bytes);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* cursor = (int*)workspace;
+  HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)n_cells * sizeof(int), st));
+  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
+  if (is_double)
+    hipLaunchKernelGGL((align_select_cells_kernel<double, true>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
+                       (const double*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                       bitmap, n_cells, cell, intensity_floor, cursor, cell_offsets, (AlignRecord*)records, capacity);
+  else
+    hipLaunchKernelGGL((align_select_cells_kernel<float, true>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
+                       (const float*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                       bitmap, n_cells, cell, intensity_floor, cursor, cell_offsets, (AlignRecord*)records, capacity);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_align_score_rigid(const void* records, const long long* cand_offsets, long long n_candidates,
+                          const double* line_vertices, long long n_vertices, const long long* line_offsets, int n_lines,
+                          const long long* slice_line_offsets, const double* poses, const long long* pose_offsets,
+                          long long n_poses, const double* pivots, const double* reach, int n_slices,
+                          const long long* items, long long n_items, double r2, long long* acc, int device,
+                          void* stream) {
+  if (n_candidates < 0 || n_vertices < 0 || n_lines < 0 || n_poses < 0 || n_slices < 0 || n_items < 0 ||
+      n_items > 0x7fffffffll)
+    return fail(PRH_ERR_ARG, "align_score_rigid: bad argument (at most 2^31 - 1 work items)");
+  if (!(r2 > 0.0) || !(r2 <= 1.0)) return fail(PRH_ERR_ARG, "align_score_rigid: 0 < radius <= 1");
+  if (n_items == 0) return PRH_OK;
+  if (!records || !cand_offsets || !line_vertices || !line_offsets || !slice_line_offsets || !poses || !pose_offsets ||
+      !pivots || !reach || !items || !acc || n_slices == 0)
+    return fail(PRH_ERR_ARG, "align_score_rigid: null pointer");
+  if (((uintptr_t)records & 15) != 0 || ((uintptr_t)poses & 15) != 0)
+    return fail(PRH_ERR_ARG, "align_score_rigid: records and poses must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(align_score_kernel<true>, dim3((unsigned)n_items), dim3(ALIGN_THREADS), 0, (hipStream_t)stream,
+                     (const AlignRecord*)records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets,
+                     n_lines, slice_line_offsets, poses, pose_offsets, n_poses, reach, n_slices, items, r2,
+                     (unsigned long long*)acc, pivots);
   LAUNCH_CHECK();
   return PRH_OK;
 }

@@ -461,7 +461,7 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
                        min_pieces=MIN_PIECES, step=F.STEP, min_count=F.MIN_COUNT, max_gap=F.MAX_GAP, origin=None,
                        batched=False, support=False, support_radius=None, intensity_floor=0.0, device_sync=False,
                        return_links=False, lift=False, lift_radius=0.5, lift_step=1.0, align=False, align_max_shift=1.0,
-                       align_radius=0.15, align_scope="frame"):
+                       align_radius=0.15, align_scope="frame", align_max_yaw=0.0):
     """A detector run refined into one drive-frame map, with no GT.
 
     drive_dir holds pose/*.json and merged.pcd; results_json is the detector's output
@@ -482,7 +482,10 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     of a shifted line, one shift per frame or - align_scope='drive' - one for the drive); it runs
     after the lift, because its distances are 3-D, and before the candidates are refined; the report
     gains 'align_frames', 'align_frames_aligned', 'align_frames_unaligned', 'align_shifts' (S,2),
-    'align_score_zero', 'align_score_best' and 'align_candidates'.
+    'align_score_zero', 'align_score_best' and 'align_candidates'.  align_max_yaw above 0 makes that
+    one align.align_lines_rigid call: a yaw of up to align_max_yaw radians about each frame's ego
+    origin is swept with the shift, for the heading error a shift cannot take out, and the report
+    gains 'align_yaws' (S,); at 0.0 the shift-only path runs untouched.
 
     Returns {'fused' [per kept cluster], 'pieces' (P,M,3) float64 ego frame, 'piece_frame' (P,) the
     row of 'poses' each piece was seen from, 'piece_slice' (the same), 'pose_index' (per used frame
@@ -519,8 +522,13 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
             cands_all, lift_report = GR.lift_lines(points, off, cands_all, step=lift_step, radius=lift_radius)
         if align:
             from . import align as AL
-            cands_all, align_report = AL.align_lines(points, off, cands_all, max_shift=align_max_shift,
-                                                     radius=align_radius, scope=align_scope)
+            if float(align_max_yaw) > 0.0:
+                cands_all, align_report = AL.align_lines_rigid(points, off, cands_all, max_shift=align_max_shift,
+                                                               max_yaw=align_max_yaw, radius=align_radius,
+                                                               scope=align_scope)
+            else:
+                cands_all, align_report = AL.align_lines(points, off, cands_all, max_shift=align_max_shift,
+                                                         radius=align_radius, scope=align_scope)
         if batched:
             pieces, piece_frame, _, sparse = F.refine_slices_batched(
                 model, points, off, cands_all, m, num_context_points, crop_radius, decay_scale, seed, precision,
@@ -557,6 +565,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     if lift:
         report.update({"lift_" + k: v for k, v in lift_report.items()})
     if align:
+        if float(align_max_yaw) > 0.0:
+            align_report.setdefault("yaws", np.zeros(0))
         report.update({"align_" + k: v for k, v in align_report.items()})
     res = {"fused": fused, "pieces": pieces, "piece_frame": piece_frame, "piece_slice": piece_frame.copy(),
            "pose_index": [int(c) for c in chosen[with_pose]], "poses": pq, "nodes": nodes, "report": report}

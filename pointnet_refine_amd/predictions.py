@@ -271,7 +271,7 @@ def match_predictions(pred_lines_per_frame, gt_lines_per_frame, threshold=MATCH_
 
 def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segment_len=SEGMENT_LEN, radius=RADIUS,
                           max_pose_gap=MAX_POSE_GAP_NS, threshold=MATCH_THRESHOLD, verbose=True, lift=False,
-                          align=False):
+                          align=False, align_max_yaw=0.0):
     """The tool's main() (:317-490) for one drive: drive_dir holds pose/*.json and merged.pcd, gt_json
     the GT polylines, results_json the detector's output.  One slice_cloud, one clip_lines_frames and
     one match_predictions call serve every frame that found a pose.  A frame is skipped when no pose
@@ -284,7 +284,9 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
     report; matching stays on xy and is unchanged.
     align=True moves the x y of the noisy_candidates onto the paint (align.align_lines over the
     frames' slices, its defaults, after the lift) and adds 'align': align_lines' report; the matches,
-    positions, context lines and PCD bytes are those of the detector's own lines.
+    positions, context lines and PCD bytes are those of the detector's own lines.  align_max_yaw
+    above 0 sweeps a yaw of up to that many radians about each frame's ego origin with the shift
+    (align.align_lines_rigid, its other defaults): the report then has 'yaws' as well.
     Returns {'frames' [result ts], 'pose_index' (per frame, -1: none), 'pose_ts', 'points' (T,4) CUDA
     and 'offsets' over the frames with a pose (row 'slice' of each frame, -1: none), 'slice',
     'items' [per frame list of item dicts, [] for a skipped frame], 'matches', 'costs', 'gt_index'
@@ -313,8 +315,11 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
         from .ground import lift_lines
         preds, res["lift"] = lift_lines(points, offsets, preds)
     if align:
-        from .align import align_lines
-        preds, res["align"] = align_lines(points, offsets, preds)
+        from .align import align_lines, align_lines_rigid
+        if float(align_max_yaw) > 0.0:
+            preds, res["align"] = align_lines_rigid(points, offsets, preds, max_yaw=align_max_yaw)
+        else:
+            preds, res["align"] = align_lines(points, offsets, preds)
     off = offsets.cpu().numpy()
     pcd_paths = [None] * (len(off) - 1)
     if out_dir is not None:
