@@ -1392,6 +1392,18 @@ int prh_test_gemm_tn_side(const float* a, const float* b, float* c, float* colsu
                           const float* kb, const float* kc, long rows, int cols, int side,
                           float* amax_out, void* workspace, size_t workspace_bytes, int device,
                           void* stream);
+/* The same (same workspace), reaching the rest of the carrier: qa / qb [ni] (device, both or
+ * neither) make the B operand relu(qa * b + qb), the wgrad of a layer behind BatchNorm + ReLU.
+ * period: k-tiles between two items of a thread's walk over the carried pass - 0 as the library
+ * plans it, 1 / 2 / 4 forced (whatever the k-loop does not reach is drained behind it; the
+ * results do not depend on the period).  *period_used (host, may be NULL): the period the
+ * carrier ran with, 0 where nothing was carried (side == 0). */
+int prh_test_gemm_tn_side_ex(const float* a, const float* b, float* c, float* colsum, int p, int mo,
+                             int ni, const float* qa, const float* qb, float* dy, long lddy,
+                             const float* z, long ldz, const float* ka, const float* kb,
+                             const float* kc, long rows, int cols, int side, int period,
+                             int* period_used, float* amax_out, void* workspace,
+                             size_t workspace_bytes, int device, void* stream);
 
 /* Raw second-stage reductions, exported for the unit tests (tests/test_ordered_reductions_gpu.py).
  * Each goes through the launcher the library itself calls, so a test runs the library's grid.

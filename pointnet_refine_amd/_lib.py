@@ -76,7 +76,7 @@ EXPORTS = [
     "prh_mlp_stack_workspace_bytes", "prh_mlp_stack_forward", "prh_mlp_stack_backward",
     "prh_test_gemm_nt", "prh_test_gemm_tn_workspace_bytes", "prh_test_gemm_tn",
     "prh_test_gate_backward_workspace_bytes", "prh_test_gate_backward",
-    "prh_test_gemm_tn_side_workspace_bytes", "prh_test_gemm_tn_side", "prh_test_xcc_map",
+    "prh_test_gemm_tn_side_workspace_bytes", "prh_test_gemm_tn_side", "prh_test_gemm_tn_side_ex", "prh_test_xcc_map",
     "prh_test_reduce_depth", "prh_test_reduce_slabs", "prh_test_reduce_bn_stage1", "prh_test_reduce_partials",
     "prh_test_reduce_ln_param_grad", "prh_test_reduce_pos_hidden_final", "prh_test_reduce_partial_rows_final",
     "prh_test_reduce_act_amax_workspace_bytes", "prh_test_reduce_act_amax",
@@ -450,6 +450,9 @@ def _bind(lib):
     lib.prh_test_gemm_tn_side_workspace_bytes.argtypes = [i, i, i]
     lib.prh_test_gemm_tn_side.restype = i
     lib.prh_test_gemm_tn_side.argtypes = [vp, vp, vp, vp, i, i, i, vp, lg, vp, lg, vp, vp, vp, lg, i, i, vp, vp, sz, i, vp]
+    lib.prh_test_gemm_tn_side_ex.restype = i
+    lib.prh_test_gemm_tn_side_ex.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, lg, vp, lg, vp, vp, vp, lg, i, i, i,
+                                             C.POINTER(i), vp, vp, sz, i, vp]
     lib.prh_test_xcc_map.restype = i
     lib.prh_test_xcc_map.argtypes = [i, i, vp, i, vp]
     if not hasattr(lib, "prh_test_reduce_depth"):

@@ -1041,10 +1041,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const NTParams p) {
 // apply pass of ANOTHER layer, dy <- ka*dy + kb*z + kc over [rows, cols] in place, carried by the
 // wgrad's workgroups between their MFMA batches.  part[workgroup] receives the workgroup's max|dz|;
 // amax (host side only) is where launch_tn has absmax_final_kernel reduce them to.  dy null: none.
+// period (host side only): k-tiles between two items of a thread's walk - 0 on entry has launch_tn
+// plan it (tn_side_period), 1 / 2 / 4 forces it; on return, the period the launch ran with.
 struct TNSide {
   float* dy; long lddy; const float* z; long ldz;
   const float* ka; const float* kb; const float* kc;
-  long rows; int cols;
+  long rows; int cols; int period;
   float* part; float* amax;
 };
 struct TNParams {

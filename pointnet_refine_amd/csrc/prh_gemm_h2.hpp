@@ -477,13 +477,24 @@ constexpr int TR_PACE_SPINS = 256;    // x (s_sleep 16 + one L2 load): ~0.3 ms a
 // no branches.  The coefficients live in LDS behind the stages (3 x cols rounded up to 256).
 // Same pro_apply expression, same 16-B granularity as bn_bwd_apply_kernel: dz and its maximum are
 // bit-identical to the stand-alone pass.
+// Q, the period of the walk: a k-tile of the launch has room for 128 x tiles side columns of each
+// of its 16 rows, so a job of fewer columns than that is over after cols / (128 x tiles) of the
+// k-loop - and while it lasts, the loop waits on HBM with 16 KB per CU in flight (the fusion wgrad at
+// B=4096: 2.5 us per k-tile instead of 1.4 for its first quarter, then nothing to carry).  The host
+// (tn_side_period) therefore spreads the job: one item per thread every Q = 1, 2 or 4 k-tiles.
+// With Q >= 2 the item's loads go out BEHIND the k-tile's own (the VM counter retires in order:
+// loads issued ahead of a tile's are waited for with it) and are used at the end of the next
+// k-tile, two k-tiles of lead in the same eight registers.  Q = 1 is the schedule described
+// above, instruction for instruction.  Which thread owns which element, and in which order a
+// thread takes its items, does not depend on Q, nor does any result.
 constexpr int TR_SIDE_MAX_COLS = 4096;
 inline size_t tr_side_lds(int cols) { return (size_t)3 * ((cols + 255) / 256 * 256) * 4 + 64; }
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-template <int PROB, bool SIDE = false>
+template <int PROB, bool SIDE = false, int Q = 1>
 __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
   static_assert(PROB == PRO_NONE || PROB == PRO_BNRELU, "prologue not supported");
+  static_assert(Q == 1 || (SIDE && (Q == 2 || Q == 4)), "side period: 1, 2 or 4 k-tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave >> 2) * 128, wn = (wave & 3) * 64;
@@ -656,18 +667,21 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
     store_tile(smem, va[0], vb[0]);
   }
   __syncthreads();
-  auto iter = [&](int kt, auto cs_) {
-    constexpr int CS = decltype(cs_)::value;
+  // PH: the k-tile's place in its group of Q.  Q = 1: an item per k-tile, its loads ahead of the
+  // tile's.  Q >= 2: one item per group, loads behind the tile's in phase 0, finished in phase 1.
+  auto iter = [&](int kt, auto cs_, auto ph_) {
+    constexpr int CS = decltype(cs_)::value, PH = decltype(ph_)::value;
     char* cur = smem + (kt & 1) * TR_STAGE;
     char* nxt = smem + ((kt + 1) & 1) * TR_STAGE;
-    if constexpr (SIDE) side_issue(sdy, sz);
+    if constexpr (SIDE && Q == 1) side_issue(sdy, sz);
     load_tile(kt + 2, va[CS ^ 1], vb[CS ^ 1]);
+    if constexpr (SIDE && Q > 1 && PH == 0) side_issue(sdy, sz);
     __builtin_amdgcn_sched_barrier(0);
     compute(cur, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
     __builtin_amdgcn_sched_barrier(0);
     compute(cur, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
     store_tile(nxt, va[CS], vb[CS]);
-    if constexpr (SIDE) side_finish(sdy, sz);
+    if constexpr (SIDE && PH == (Q > 1 ? 1 : 0)) side_finish(sdy, sz);
 #pragma unroll
     for (int g = 0; g < 12; ++g) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -677,8 +691,14 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
   };
   const int pace_tiles = p.tiles_m * p.tiles_n;
   bool pacing = p.pace != nullptr && tid == 0;
+  using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+  using IP = std::integral_constant<int, Q >= 2 ? 1 : 0>;      // phase of a group's second k-tile
+  constexpr int U = Q == 4 ? 4 : 2;      // k-tiles per trip: the phase is a constant next to the CS parity
   int kt = 0;
-  for (; kt + 1 < KT; kt += 2) {
+  // (Q = 1 keeps its bound as it was written: the form of the expression decides the compiler's induction
+  // variables, and with them whether the stream of the Q = 1 and the plain kernels stays what it was)
+  for (; Q == 1 ? kt + 1 < KT : kt + U - 1 < KT; kt += U) {
     if ((kt & (TR_PACE - 1)) == 0 && pacing) {
       const int mine = (kt / TR_PACE + 1) * pace_tiles;
       int tot = __hip_atomic_fetch_add(p.pace + split, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
@@ -690,10 +710,26 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_tr_kernel(const TNParams p) {
       }
       if (spins == TR_PACE_SPINS) pacing = false;
     }
-    iter(kt, std::integral_constant<int, 1>{});
-    iter(kt + 1, std::integral_constant<int, 0>{});
+    iter(kt, I1{}, I0{});
+    iter(kt + 1, I0{}, IP{});
+    if constexpr (Q == 4) {
+      iter(kt + 2, I1{}, I2{});
+      iter(kt + 3, I0{}, I3{});
+    }
   }
-  if (kt < KT) iter(kt, std::integral_constant<int, 1>{});
+  // peeled remainder (Q = 4: up to three k-tiles, as a group of two and a last one; a progress
+  // report that would fall on them is left out by every workgroup of the split alike)
+  if constexpr (Q == 4) {
+    if (kt + 1 < KT) {
+      iter(kt, I1{}, I0{});
+      iter(kt + 1, I0{}, I1{});
+      kt += 2;
+    }
+  }
+  if (kt < KT) {
+    iter(kt, I1{}, I0{});
+    if constexpr (Q >= 2) side_finish(sdy, sz);      // issued in this k-tile, pending at loop end
+  }
 
   if constexpr (SIDE) {      // the rest of this workgroup's slice, four items in flight per thread
     const long ngroups = (p.side.rows + srpw - 1) / srpw;

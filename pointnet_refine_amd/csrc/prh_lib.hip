@@ -685,6 +685,32 @@ inline bool tn_side_ok(Cores c, const TNParams& p, const TNSide& s) {
          s.ldz <= 65536 && al16(s.dy) && al16(s.z);
 }
 
+// k-tiles between two items of a thread's side walk: the largest of 4, 2, 1 at which the launch's
+// waves, one item each per period over a split's k-tiles, still reach every item of the job -
+// the job spread over the whole k-loop instead of packed into the head of it.  Counted over the
+// launch (period * items <= k-tiles * waves), not per wave with the items rounded up: at B=4096
+// the fusion wgrad has 2730.67 items per wave for 10923 k-tiles, and a rounded-up 2731 would
+// halve its period for the sake of one item, which the drain takes.  A job larger than its
+// carrier's k-loop runs at 1 and drains the rest, as it always has.
+inline int tn_side_period(const TNPlan& pl, const TNSide& s) {
+  const int c4s = s.cols >> 2;
+  int lpr = 64;                                          // lanes per row, as in the kernel
+  while (lpr > 1 && (lpr >> 1) >= c4s) lpr >>= 1;
+  const long rpw = 64 / lpr, groups = (s.rows + rpw - 1) / rpw, chunks = (c4s + 63) >> 6;
+  const long items = groups * chunks;
+  const long slots = (long)(pl.rows_per_split / S3_BK) * pl.tiles_m * pl.tiles_n * pl.splits * 8;
+  return 4 * items <= slots ? 4 : (2 * items <= slots ? 2 : 1);
+}
+template <int PROB, int Q>
+int launch_tn_tr_side(const TNParams& p, long blocks, hipStream_t st) {
+  static const int attr_sd = allow_big_lds(gemm_tn_tr_kernel<PROB, true, Q>);
+  if (attr_sd != PRH_OK) return attr_sd;
+  hipLaunchKernelGGL((gemm_tn_tr_kernel<PROB, true, Q>), dim3((unsigned)blocks), dim3(512),
+                     TR_LDS + tr_side_lds(p.side.cols), st, p);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
 // C[Mo,Ni] (ld ldc) = proA(A)^T proB(B); colsum_out[Mo] = column sums of proA(A) (optional)
 template <int PROA, int PROB>
 int launch_tn(Cores c, TNParams& p, float* slab, float* colsum_slab, float* C, long ldc, float* colsum_out,
@@ -744,11 +770,13 @@ int launch_tn(Cores c, TNParams& p, float* slab, float* colsum_slab, float* C, l
         ProfScope ps(nm, 2.0 * p.P * (double)p.Mo * p.Ni, by, st);
         if constexpr (PROA == PRO_NONE && (PROB == PRO_NONE || PROB == PRO_BNRELU)) {
           if (tr && side) {
-            static const int attr_sd = allow_big_lds(gemm_tn_tr_kernel<PROB, true>);
-            if (attr_sd != PRH_OK) return attr_sd;
-            hipLaunchKernelGGL((gemm_tn_tr_kernel<PROB, true>), dim3((unsigned)blocks), dim3(512),
-                               TR_LDS + tr_side_lds(p.side.cols), st, p);
-            LAUNCH_CHECK();
+            if (p.side.period == 0) p.side.period = tn_side_period(pl, p.side);
+            switch (p.side.period) {
+              case 4: TRY_RC((launch_tn_tr_side<PROB, 4>(p, blocks, st))); break;
+              case 2: TRY_RC((launch_tn_tr_side<PROB, 2>(p, blocks, st))); break;
+              case 1: TRY_RC((launch_tn_tr_side<PROB, 1>(p, blocks, st))); break;
+              default: return fail(PRH_ERR_ARG, "gemm_tn: side period %d (1, 2 or 4)", p.side.period);
+            }
             hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, (const float*)p.side.part, (int)blocks,
                                p.side.amax);
           } else if (tr) {
@@ -981,7 +1009,7 @@ inline TNSide side_job(float* dy, long lddy, const float* z, long ldz, const Sta
                        float* hdr) {
   TNSide s;
   s.dy = dy; s.lddy = lddy; s.z = z; s.ldz = ldz; s.ka = sc.ca; s.kb = sc.cb; s.kc = sc.cc;
-  s.rows = rows; s.cols = cols; s.part = hdr + 64; s.amax = hdr;
+  s.rows = rows; s.cols = cols; s.part = hdr + 64; s.amax = hdr; s.period = 0;
   return s;
 }
 
@@ -4243,7 +4271,21 @@ int prh_test_gemm_tn_side(const float* a, const float* b, float* c, float* colsu
                           float* dy, long lddy, const float* z, long ldz, const float* ka, const float* kb,
                           const float* kc, long rows, int cols, int side, float* amax_out, void* workspace,
                           size_t workspace_bytes, int device, void* stream) {
+  return prh_test_gemm_tn_side_ex(a, b, c, colsum, p, mo, ni, nullptr, nullptr, dy, lddy, z, ldz, ka, kb, kc, rows, cols,
+                                  side, 0, nullptr, amax_out, workspace, workspace_bytes, device, stream);
+}
+// ... with BN+ReLU coefficients qa / qb [ni] on b (both or neither), and the side walk's period: 0 planned,
+// 1 / 2 / 4 forced; *period_used (host, optional): the period the carrier ran with, 0 where nothing was carried.
+int prh_test_gemm_tn_side_ex(const float* a, const float* b, float* c, float* colsum, int p, int mo, int ni,
+                             const float* qa, const float* qb, float* dy, long lddy, const float* z, long ldz,
+                             const float* ka, const float* kb, const float* kc, long rows, int cols, int side,
+                             int period, int* period_used, float* amax_out, void* workspace, size_t workspace_bytes,
+                             int device, void* stream) {
   HIP_TRY(hipSetDevice(device));
+  if ((qa == nullptr) != (qb == nullptr)) return fail(PRH_ERR_ARG, "test_gemm_tn_side: qa and qb go together");
+  if (period != 0 && period != 1 && period != 2 && period != 4)
+    return fail(PRH_ERR_ARG, "test_gemm_tn_side: period %d (0, 1, 2 or 4)", period);
+  if (period_used) *period_used = 0;
   if (!dy || !z || !ka || !kb || !kc || !amax_out || rows <= 0 || cols <= 0 || (cols & 3) || (lddy & 3) || (ldz & 3) ||
       lddy < cols || ldz < cols)
     return fail(PRH_ERR_ARG, "test_gemm_tn_side: bad side matrix");
@@ -4258,11 +4300,17 @@ int prh_test_gemm_tn_side(const float* a, const float* b, float* c, float* colsu
   t.A = a; t.lda = mo; t.B = b; t.ldb = ni; t.P = p; t.Mo = mo; t.Ni = ni;
   if (side) {
     t.side.dy = dy; t.side.lddy = lddy; t.side.z = z; t.side.ldz = ldz; t.side.ka = ka; t.side.kb = kb; t.side.kc = kc;
-    t.side.rows = rows; t.side.cols = cols; t.side.part = hdr + 64; t.side.amax = hdr;
+    t.side.rows = rows; t.side.cols = cols; t.side.part = hdr + 64; t.side.amax = hdr; t.side.period = period;
   } else {
     TRY(materialize_dz(dy, lddy, z, ldz, ka, kb, kc, rows, cols, hdr, st));
   }
-  TRY((launch_tn<PRO_NONE, PRO_NONE>(cores, t, slab, cs, c, (long)ni, colsum, st)));
+  if (qa != nullptr) {
+    t.qa = qa; t.qb = qb;
+    TRY((launch_tn<PRO_NONE, PRO_BNRELU>(cores, t, slab, cs, c, (long)ni, colsum, st)));
+  } else {
+    TRY((launch_tn<PRO_NONE, PRO_NONE>(cores, t, slab, cs, c, (long)ni, colsum, st)));
+  }
+  if (period_used) *period_used = t.side.period;
   HIP_TRY(hipMemcpyAsync(amax_out, hdr, sizeof(float), hipMemcpyDeviceToDevice, st));
   return PRH_OK;
 }
