@@ -1,9 +1,10 @@
-"""What the tool modules (drive, predictions, bev, pcd, metrics, context) share on their way to the
-library: the device getter, pointers and streams for ctypes, the throwaway workspace, the
-exclusive scan between a count and a write call, the upload rule (numpy is uploaded, a CUDA tensor
-is used where it is, a CPU tensor is refused) and the two-pass polyline clip that drive.clip_lines
-and predictions.clip_lines_frames both are.  ops / model / train_step do not use this module:
-their workspace is a grow-only cache per stream and their pointers treat empty tensors differently.
+"""What the tool modules (drive, predictions, bev, pcd, metrics, context, fuse, link, view3d, support, ground, align)
+share on their way to the library: the device getter, pointers and streams for ctypes, the throwaway workspace, the
+exclusive scan between a count and a write call, the upload rule (numpy is uploaded, a CUDA tensor is used where it
+is, a CPU tensor is refused), the two-pass polyline clip that drive.clip_lines and predictions.clip_lines_frames both
+are, and what ground and align take a sliced cloud with: host copies, checked offsets, the (T,4) points and the
+per-slice cell grids.  ops / model / train_step do not use this module: their workspace is a grow-only cache per
+stream and their pointers treat empty tensors differently.
 """
 import ctypes as C
 
@@ -54,6 +55,63 @@ def as_cuda(x, dev, what, dtype=None):
     else:
         t = torch.from_numpy(np.ascontiguousarray(x, dtype=_NUMPY[dtype])).to(dev)
     return (t if dtype is None else t.to(dtype)).contiguous()
+
+
+def host(x, dtype):
+    """x (a tensor anywhere, or anything numpy takes) as a numpy array of dtype."""
+    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(dtype, copy=False)
+
+
+def offsets(x, n, what, name):
+    """x as (S+1,) int64 on the host; ValueError unless it rises from 0 to n."""
+    off = host(x, np.int64).reshape(-1)
+    if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
+        raise ValueError(f"{what}: {name} must rise from 0 to {n}")
+    return off
+
+
+def points4(points, dev, what):
+    """(T,4) float64 or float32 CUDA, aligned to two coordinates: numpy is uploaded once, a CUDA
+    tensor stays where it is."""
+    shape = tuple(points.shape) if torch.is_tensor(points) else np.shape(points)
+    if len(shape) != 2 or shape[1] != 4:
+        raise ValueError(f"{what}: points must be (T,4) x y z intensity, got {shape}")
+    if not torch.is_tensor(points):
+        points = np.asarray(points)
+        if points.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{what}: points must be float64 or float32, got {points.dtype}")
+    elif points.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: points must be float64 or float32, got {points.dtype}")
+    t = as_cuda(points, dev, what)
+    return t.clone() if t.numel() and t.data_ptr() % 16 else t
+
+
+def box_grids(xy, off, reach, cell, max_cells):
+    """Per slice a uniform xy grid, cell metres wide, over the box of its rows of xy (N,2) float64 (off (S+1,) int64)
+    expanded by reach (a scalar, or (S,)): nx = floor((hi - lo) / cell) + 1.  cell is doubled until all grids together
+    have at most max_cells cells.  Returns {'origin' (S,2) float64, 'shape' (S,2) int32 = nx ny (0 0 for a slice
+    without a row), 'cell_base' (S,) int64, 'n_cells', 'cell'}."""
+    n_s, cell = len(off) - 1, float(cell)
+    origin = np.zeros((n_s, 2))
+    shape = np.zeros((n_s, 2), dtype=np.int64)
+    used = np.flatnonzero(np.diff(off) > 0)
+    if len(used):
+        start = off[:-1][used]
+        r = np.broadcast_to(np.asarray(reach, dtype=np.float64), (n_s,))[used, None]
+        lo = np.stack([np.minimum.reduceat(xy[:, c], start) for c in (0, 1)], 1) - r
+        hi = np.stack([np.maximum.reduceat(xy[:, c], start) for c in (0, 1)], 1) + r
+        origin[used] = lo
+        while True:
+            n = np.floor((hi - lo) / cell).astype(np.int64) + 1
+            if int((n[:, 0] * n[:, 1]).sum()) <= max_cells:
+                break
+            cell *= 2.0
+        shape[used] = n
+    base = np.zeros(n_s, dtype=np.int64)
+    cells = shape[:, 0] * shape[:, 1]
+    if n_s:
+        base[1:] = np.cumsum(cells)[:-1]
+    return {"origin": origin, "shape": shape.astype(np.int32), "cell_base": base, "n_cells": int(cells.sum()), "cell": cell}
 
 
 def poses(poses_xyzq, dev, what):

@@ -30,6 +30,11 @@ per-slice pivot - the sensor - plus the shift, for the heading error a shift can
   pick_pose        host: pick_shift with the norm dx^2 + dy^2 + (lever theta)^2
   apply_pose       host: a pose applied to (n,3) vertices
   align_lines_rigid  the coarse and the fine rigid_scores call with their picks
+  align            align_lines at max_yaw = 0, align_lines_rigid above it
+
+Both kinds of table go down one path (prepare, select_candidates, score_candidates, _scores, _stage,
+_two_stage, _pick): a shift table is (K,2) and takes prh_align_score after the arrival-order filter,
+a pose table is (K,3) and takes prh_align_score_rigid after the filter in ORDER.
 
 paint_scores, rigid_scores, align_lines and align_lines_rigid have no CPU fallback: without a GPU
 they raise RuntimeError.
@@ -41,7 +46,6 @@ import torch
 
 from . import _gpu as G
 from . import _lib as L
-from .ground import _host, _offsets, _points
 
 RADIUS = 0.15                # metres: the tube around a shifted line
 MAX_RADIUS = 1.0
@@ -118,28 +122,10 @@ def segment_bitmaps(vertices, line_offsets, slice_line_offsets, reach, cell=CELL
     l_off = np.asarray(line_offsets, dtype=np.int64).reshape(-1)
     sl_off = np.asarray(slice_line_offsets, dtype=np.int64).reshape(-1)
     reach = np.asarray(reach, dtype=np.float64).reshape(-1)
-    cell = float(cell)
-    n_s = len(sl_off) - 1
     v_off = l_off[sl_off]                                   # the vertices of every slice
-    origin = np.zeros((n_s, 2))
-    shape = np.zeros((n_s, 2), dtype=np.int64)
-    used = np.flatnonzero(np.diff(v_off) > 0)
-    if len(used):
-        start = v_off[:-1][used]
-        lo = np.stack([np.minimum.reduceat(v[:, c], start) for c in (0, 1)], 1) - reach[used, None]
-        hi = np.stack([np.maximum.reduceat(v[:, c], start) for c in (0, 1)], 1) + reach[used, None]
-        origin[used] = lo
-        while True:
-            n = np.floor((hi - lo) / cell).astype(np.int64) + 1
-            if int((n[:, 0] * n[:, 1]).sum()) <= MAX_CELLS:
-                break
-            cell *= 2.0
-        shape[used] = n
-    base = np.zeros(n_s, dtype=np.int64)
-    cells = shape[:, 0] * shape[:, 1]
-    if n_s:
-        base[1:] = np.cumsum(cells)[:-1]
-    n_cells = int(cells.sum())
+    maps = G.box_grids(v[:, :2], v_off, reach, cell, MAX_CELLS)
+    origin, shape, base, n_cells, cell = (maps[k] for k in ("origin", "shape", "cell_base", "n_cells", "cell"))
+    shape = shape.astype(np.int64)
     bits = np.zeros(n_cells, dtype=bool)
     # segments: vertex k and k + 1 of one line
     is_a = np.ones(len(v), dtype=bool)
@@ -164,8 +150,7 @@ def segment_bitmaps(vertices, line_offsets, slice_line_offsets, reach, cell=CELL
     packed = np.packbits(bits, bitorder="little")
     words = np.zeros(((n_cells + 31) // 32) * 4, dtype=np.uint8)
     words[:len(packed)] = packed
-    return {"origin": origin, "shape": shape.astype(np.int32), "cell_base": base, "n_cells": n_cells, "cell": cell,
-            "bitmap": words.view("<u4").astype(np.uint32)}
+    return dict(maps, bitmap=words.view("<u4").astype(np.uint32))
 
 
 def _ratio(pair, what, name, allow_above_one):
@@ -180,35 +165,44 @@ def _ratio(pair, what, name, allow_above_one):
     return int(num), int(den)
 
 
-def pick_shift(shifts, score, hits, min_points=MIN_POINTS, keep=KEEP, gain=GAIN):
-    """Steps 6-10 of the rule over one table.  shifts (K,2) float64, score and hits (K,) integers.
-    Returns {'shift' (2,) float64, 'row' (the accepted row, or k0), 'aligned' bool, 'score_zero',
-    'score_best' (Python ints: the score at (0, 0) and at the near-best row)}."""
-    what = "pick_shift"
-    sh = np.asarray(shifts, dtype=np.float64).reshape(-1, 2)
+def _pick(what, rows, score, hits, norm2, key, zero, min_points, keep, gain, check=None):
+    """Steps 6-10 of either rule over one table: pick_shift and pick_pose.  rows (K,cols) float64; norm2: the
+    squared length of rows[near], by which the near-best rows are ranked; key: 'shift' or 'pose', the result's key
+    and the word of the error texts; zero: how those name the all-zero row; check: the caller's own validation, in
+    its place after the shared ones."""
     sc = [int(x) for x in np.asarray(score).reshape(-1)]
     ht = [int(x) for x in np.asarray(hits).reshape(-1)]
-    if not (len(sh) == len(sc) == len(ht)):
-        raise ValueError(f"{what}: one score and one hit count per shift")
+    if not (len(rows) == len(sc) == len(ht)):
+        raise ValueError(f"{what}: one score and one hit count per {key}")
     keep_num, keep_den = _ratio(keep, what, "keep", False)
     gain_num, gain_den = _ratio(gain, what, "gain", True)
     if int(min_points) != min_points or int(min_points) < 1:
         raise ValueError(f"{what}: min_points must be an integer >= 1")
-    zero = np.flatnonzero((sh[:, 0] == 0.0) & (sh[:, 1] == 0.0))
-    if len(zero) == 0:
-        raise ValueError(f"{what}: the table must contain the shift (0, 0)")
-    k0 = int(zero[0])
-    none = {"shift": np.zeros(2), "row": k0, "aligned": False, "score_zero": sc[k0], "score_best": sc[k0]}
+    if check is not None:
+        check()
+    zeros = np.flatnonzero((rows == 0.0).all(axis=1))
+    if len(zeros) == 0:
+        raise ValueError(f"{what}: the table must contain the {key} {zero}")
+    k0 = int(zeros[0])
+    none = {key: np.zeros(rows.shape[1]), "row": k0, "aligned": False, "score_zero": sc[k0], "score_best": sc[k0]}
     best = max(sc)
     if best == 0 or ht[sc.index(best)] < int(min_points):
         return none
     near = [k for k in range(len(sc)) if sc[k] * keep_den >= best * keep_num]
-    n2 = sh[near, 0] * sh[near, 0] + sh[near, 1] * sh[near, 1]
-    row = near[int(np.argmin(n2))]                           # argmin: the first of equal values, the lowest row
+    row = near[int(np.argmin(norm2(rows[near])))]            # argmin: the first of equal values, the lowest row
     none["score_best"] = sc[row]
     if not sc[row] * gain_den > sc[k0] * gain_num:
         return none
-    return {"shift": sh[row].copy(), "row": row, "aligned": True, "score_zero": sc[k0], "score_best": sc[row]}
+    return {key: rows[row].copy(), "row": row, "aligned": True, "score_zero": sc[k0], "score_best": sc[row]}
+
+
+def pick_shift(shifts, score, hits, min_points=MIN_POINTS, keep=KEEP, gain=GAIN):
+    """Steps 6-10 of the rule over one table.  shifts (K,2) float64, score and hits (K,) integers.
+    Returns {'shift' (2,) float64, 'row' (the accepted row, or k0), 'aligned' bool, 'score_zero',
+    'score_best' (Python ints: the score at (0, 0) and at the near-best row)}."""
+    sh = np.asarray(shifts, dtype=np.float64).reshape(-1, 2)
+    return _pick("pick_shift", sh, score, hits, lambda r: r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1], "shift", "(0, 0)",
+                 min_points, keep, gain)
 
 
 def work_items(cand_offsets, shift_offsets, slice_vertices):
@@ -238,80 +232,99 @@ def _params(radius, intensity_floor, cell, what):
     return radius, intensity_floor, cell
 
 
-def prepare(points, slice_offsets, lines_per_slice, shifts, shift_offsets, radius, intensity_floor, cell, what):
-    """Validation and the host side of one paint_scores call: the points on the device, the lines as
-    CSR, every slice's reach and bitmap.  Returns the dict select_candidates and score_candidates take."""
+def prepare(points, slice_offsets, lines_per_slice, table, table_offsets, radius, intensity_floor, cell, what, pivots=None,
+            rigid=False):
+    """Validation and the host side of one paint_scores or (rigid) rigid_scores call: the points on the device, the
+    lines as CSR, every slice's reach and bitmap.  table: (K,2) shifts dx dy, or with rigid (K,3) poses dx dy theta
+    and pivots (S,2) or None.  Returns the dict select_candidates and score_candidates take; 'sh' is the table the
+    device gets, for poses pose_table's (K,4)."""
+    name, cols, names, max_rows = ("poses", 3, "dx dy theta", MAX_POSES) if rigid else ("shifts", 2, "dx dy", MAX_SHIFTS)
     radius, intensity_floor, cell = _params(radius, intensity_floor, cell, what)
     dev = G.device("align", points.device if torch.is_tensor(points) and points.is_cuda else None)
-    pts = _points(points, dev, what)
-    off = _offsets(slice_offsets, pts.shape[0], what, "slice_offsets")
+    pts = G.points4(points, dev, what)
+    off = G.offsets(slice_offsets, pts.shape[0], what, "slice_offsets")
     n_s = len(off) - 1
     if len(lines_per_slice) != n_s:
         raise ValueError(f"{what}: one list of lines per slice ({n_s}), got {len(lines_per_slice)}")
     verts, l_off, sl_off = lines_csr(lines_per_slice, what)
-    shape = tuple(shifts.shape) if torch.is_tensor(shifts) else np.shape(shifts)
-    if len(shape) != 2 or shape[1] != 2:
-        raise ValueError(f"{what}: shifts must be (K,2) dx dy, got {shape}")
-    sh = np.ascontiguousarray(_host(shifts, np.float64).reshape(-1, 2))
-    if not (np.isfinite(sh).all() and (len(sh) == 0 or np.abs(sh).max() <= MAX_SHIFT)):
-        raise ValueError(f"{what}: shifts must be finite with |component| <= {MAX_SHIFT:g}")
-    k_off = _offsets(shift_offsets, len(sh), what, "shift_offsets")
+    shape = tuple(table.shape) if torch.is_tensor(table) else np.shape(table)
+    if len(shape) != 2 or shape[1] != cols:
+        raise ValueError(f"{what}: {name} must be (K,{cols}) {names}, got {shape}")
+    tb = np.ascontiguousarray(G.host(table, np.float64).reshape(-1, cols))
+    if not (np.isfinite(tb).all() and (len(tb) == 0 or (np.abs(tb[:, :2]).max() <= MAX_SHIFT
+                                                        and (not rigid or np.abs(tb[:, 2]).max() <= MAX_YAW)))):
+        limits = f"|dx|, |dy| <= {MAX_SHIFT:g} and |theta| <= {MAX_YAW:g}" if rigid else f"|component| <= {MAX_SHIFT:g}"
+        raise ValueError(f"{what}: {name} must be finite with {limits}")
+    k_off = G.offsets(table_offsets, len(tb), what, name[:-1] + "_offsets")
     if len(k_off) != len(off):
-        raise ValueError(f"{what}: slice_offsets and shift_offsets must describe the same slices")
-    if n_s and int(np.diff(k_off).max()) > MAX_SHIFTS:
-        raise ValueError(f"{what}: at most {MAX_SHIFTS} shifts per slice")
-    reach = slice_reach(sh, k_off, radius)
+        raise ValueError(f"{what}: slice_offsets and {name[:-1]}_offsets must describe the same slices")
+    if n_s and int(np.diff(k_off).max()) > max_rows:
+        raise ValueError(f"{what}: at most {max_rows} {name} per slice")
+    pv = _pivots(pivots, n_s, what) if rigid else None
+    reach = rigid_reach(tb, k_off, radius, verts, l_off, sl_off, pv) if rigid else slice_reach(tb, k_off, radius)
     maps = segment_bitmaps(verts, l_off, sl_off, reach, cell)
-    return {"dev": dev, "pts": pts, "off": off, "n_s": n_s, "verts": verts, "l_off": l_off, "sl_off": sl_off, "sh": sh,
-            "k_off": k_off, "reach": reach, "maps": maps, "radius": radius, "intensity_floor": intensity_floor, "what": what}
+    return {"dev": dev, "pts": pts, "off": off, "n_s": n_s, "verts": verts, "l_off": l_off, "sl_off": sl_off,
+            "sh": pose_table(tb) if rigid else tb, "k_off": k_off, "reach": reach, "maps": maps, "radius": radius,
+            "pivots": pv, "rigid": rigid, "intensity_floor": intensity_floor, "what": what}
 
 
-def select_candidates(p):
-    """prh_align_select_count, the scan, prh_align_select_write: (records (C,4) float64 CUDA - x y z
-    and the bits of qi -, cand_offsets (S+1,) int64 CUDA, the same offsets as numpy)."""
+def select_candidates(p, order="arrival"):
+    """The candidate filter - count, the scan, write: (records (C,4) float64 CUDA - x y z and the bits of qi -,
+    cand_offsets (S+1,) int64 CUDA, the same offsets as numpy).  order 'arrival': prh_align_select_*, one counter per
+    slice, a slice's records as they arrive; 'cell': prh_align_select_cells_*, one counter per bitmap cell, a slice's
+    records in ascending cell order (arrival order inside a cell)."""
     lib, dev, pts, maps, n_s = L.lib(), p["dev"], p["pts"], p["maps"], p["n_s"]
-    if n_s == 0 or pts.shape[0] == 0 or maps["n_cells"] == 0:
+    n_cells = maps["n_cells"]
+    if n_s == 0 or pts.shape[0] == 0 or n_cells == 0:
         return torch.empty((0, 4), dtype=torch.float64, device=dev), None, np.zeros(n_s + 1, dtype=np.int64)
-    counts = torch.zeros((n_s,), dtype=torch.int32, device=dev)
+    entry, n = ("prh_align_select_cells", n_cells) if order == "cell" else ("prh_align_select", n_s)
+    counts = torch.zeros((n,), dtype=torch.int32, device=dev)
     off_t = torch.from_numpy(p["off"]).to(dev)
     g_t = tuple(torch.from_numpy(np.ascontiguousarray(maps[k])).to(dev) for k in ("origin", "shape", "cell_base"))
     bitmap = torch.from_numpy(maps["bitmap"].view(np.int32)).to(dev)
     args = (G.ptr(pts), 1 if pts.dtype == torch.float64 else 0, G.ptr(off_t), n_s, pts.shape[0], G.ptr(g_t[0]), G.ptr(g_t[1]),
-            G.ptr(g_t[2]), G.ptr(bitmap), maps["n_cells"], maps["cell"], p["intensity_floor"])
-    L.check(lib.prh_align_select_count(*args, G.ptr(counts), dev.index, G.stream(dev)), "prh_align_select_count")
-    cand_off = G.exclusive_scan(counts)
+            G.ptr(g_t[2]), G.ptr(bitmap), n_cells, maps["cell"], p["intensity_floor"])
+    L.check(getattr(lib, entry + "_count")(*args, G.ptr(counts), dev.index, G.stream(dev)), entry + "_count")
+    scan = G.exclusive_scan(counts)
+    # cells of a slice are contiguous from cell_base[s]: the slice's rows start at the scan there
+    cand_off = torch.cat([scan[g_t[2]], scan[-1:]]).contiguous() if order == "cell" else scan
     c_off = cand_off.cpu().numpy()
     total = int(c_off[-1])
     rec = torch.empty((total, 4), dtype=torch.float64, device=dev)
     if total:
-        nb = lib.prh_align_select_workspace_bytes(n_s)
+        nb = getattr(lib, entry + "_workspace_bytes")(n)
         ws = G.workspace(nb, dev)
-        L.check(lib.prh_align_select_write(*args, G.ptr(cand_off), G.ptr(rec), total, G.ptr(ws), nb, dev.index,
-                                           G.stream(dev)), "prh_align_select_write")
+        L.check(getattr(lib, entry + "_write")(*args, G.ptr(scan), G.ptr(rec), total, G.ptr(ws), nb, dev.index, G.stream(dev)),
+                entry + "_write")
     return rec, cand_off, c_off
 
 
 def score_candidates(p, rec, cand_off, c_off):
-    """The plan and prh_align_score over the selected candidates: acc (K,2) int64 CUDA = score, hits."""
-    dev, sh = p["dev"], p["sh"]
-    acc = torch.zeros((len(sh), 2), dtype=torch.int64, device=dev)
+    """The plan and the score sweep over the selected candidates - prh_align_score for a shift p,
+    prh_align_score_rigid for a rigid one: acc (K,2) int64 CUDA = score, hits."""
+    dev, table, rigid = p["dev"], p["sh"], p["rigid"]
+    acc = torch.zeros((len(table), 2), dtype=torch.int64, device=dev)
     if p["n_s"] and int((np.diff(c_off) * np.diff(p["sl_off"])).max()) >= 2 ** 31:
         raise OverflowError(f"{p['what']}: a slice has 2^31 or more (candidate, line) pairs")
     items = work_items(c_off, p["k_off"], np.diff(p["l_off"][p["sl_off"]]))
     if rec.shape[0] == 0 or len(items) == 0:
         return acc
     up = [torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-          for x in (p["verts"], p["l_off"], p["sl_off"], sh, p["k_off"], p["reach"], items)]
-    L.check(L.lib().prh_align_score(G.ptr(rec), G.ptr(cand_off), rec.shape[0], G.ptr(up[0]), len(p["verts"]), G.ptr(up[1]),
-                                    len(p["l_off"]) - 1, G.ptr(up[2]), G.ptr(up[3]), G.ptr(up[4]), len(sh), G.ptr(up[5]),
-                                    p["n_s"], G.ptr(up[6]), len(items), p["radius"] * p["radius"], G.ptr(acc), dev.index,
-                                    G.stream(dev)), "prh_align_score")
+          for x in (p["verts"], p["l_off"], p["sl_off"], table, p["k_off"], p["reach"], items) + ((p["pivots"],) if rigid else ())]
+    verts, l_off, sl_off, tb, k_off, reach, plan, *pv = (G.ptr(t) for t in up)
+    entry = "prh_align_score_rigid" if rigid else "prh_align_score"
+    L.check(getattr(L.lib(), entry)(G.ptr(rec), G.ptr(cand_off), rec.shape[0], verts, len(p["verts"]), l_off, len(p["l_off"]) - 1,
+                                    sl_off, tb, k_off, len(table), *pv, reach, p["n_s"], plan, len(items),
+                                    p["radius"] * p["radius"], G.ptr(acc), dev.index, G.stream(dev)), entry)
     return acc
 
 
-def _scores(points, slice_offsets, lines_per_slice, shifts, shift_offsets, radius, intensity_floor, cell, what):
-    p = prepare(points, slice_offsets, lines_per_slice, shifts, shift_offsets, radius, intensity_floor, cell, what)
-    rec, cand_off, c_off = select_candidates(p)
+def _scores(points, slice_offsets, lines_per_slice, table, table_offsets, radius, intensity_floor, cell, what, pivots=None,
+            rigid=False, order="arrival"):
+    if order not in ("cell", "arrival"):
+        raise ValueError(f"{what}: order must be 'cell' or 'arrival'")
+    p = prepare(points, slice_offsets, lines_per_slice, table, table_offsets, radius, intensity_floor, cell, what, pivots, rigid)
+    rec, cand_off, c_off = select_candidates(p, order)
     acc = score_candidates(p, rec, cand_off, c_off)
     return {"score": acc[:, 0], "hits": acc[:, 1], "candidates": np.diff(c_off)}
 
@@ -334,26 +347,45 @@ def paint_scores(points, slice_offsets, lines_per_slice, shifts, shift_offsets, 
     return {"score": res["score"], "hits": res["hits"]}
 
 
-def _stage(points, off, lines, tables, scope, radius, intensity_floor, pick_kw, what):
-    """One paint_scores call over per-slice tables and the picks: per slice under scope 'frame', once
-    on the summed tables under scope 'drive' (every slice's table is then the same)."""
+def _stage(points, off, lines, tables, scope, radius, intensity_floor, pick, what, **scores_kw):
+    """One _scores call over per-slice tables and the picks - pick(table, score, hits): per slice under scope
+    'frame', once on the summed tables under scope 'drive' (every slice's table is then the same)."""
     n_s = len(lines)
     if n_s == 0:
         return [], np.zeros(0, dtype=np.int64)
     k_off = np.zeros(n_s + 1, dtype=np.int64)
     k_off[1:] = np.cumsum([len(t) for t in tables])
-    res = _scores(points, off, lines, np.concatenate(tables) if n_s else np.zeros((0, 2)), k_off, radius, intensity_floor,
-                  CELL, what)
+    res = _scores(points, off, lines, np.concatenate(tables), k_off, radius, intensity_floor, CELL, what, **scores_kw)
     score, hits = res["score"].cpu().numpy(), res["hits"].cpu().numpy()
     if scope == "drive":
         k = len(tables[0])
-        one = pick_shift(tables[0], [int(x) for x in score.reshape(n_s, k).astype(object).sum(axis=0)],
-                         [int(x) for x in hits.reshape(n_s, k).astype(object).sum(axis=0)], **pick_kw)
+        one = pick(tables[0], [int(x) for x in score.reshape(n_s, k).astype(object).sum(axis=0)],
+                   [int(x) for x in hits.reshape(n_s, k).astype(object).sum(axis=0)])
         picks = [one] * n_s
     else:
-        picks = [pick_shift(tables[s], score[k_off[s]:k_off[s + 1]], hits[k_off[s]:k_off[s + 1]], **pick_kw)
-                 for s in range(n_s)]
+        picks = [pick(tables[s], score[k_off[s]:k_off[s + 1]], hits[k_off[s]:k_off[s + 1]]) for s in range(n_s)]
     return picks, res["candidates"]
+
+
+def _two_stage(what, points, off, lines, scope, radius, intensity_floor, coarse, fine, pick, key, columns, **scores_kw):
+    """What align_lines and align_lines_rigid share: the coarse table for every slice and its picks, the table
+    fine(coarse pick) per slice and the final picks.  key: 'shift' or 'pose'; columns(rows): the report's entries
+    for the picked rows (S,cols).  Returns (the picked rows, the report)."""
+    n_s = len(lines)
+    first, _ = _stage(points, off, lines, [coarse] * n_s, scope, radius, intensity_floor, pick, what, **scores_kw)
+    picks, cands = _stage(points, off, lines, [fine(p[key]) for p in first], scope, radius, intensity_floor, pick, what,
+                          **scores_kw)
+    rows = np.array([p[key] for p in picks], dtype=np.float64).reshape(n_s, coarse.shape[1])
+    aligned = int(sum(1 for p in picks if p["aligned"]))
+    report = {"frames": n_s, "frames_aligned": aligned, "frames_unaligned": n_s - aligned, **columns(rows),
+              "score_zero": np.array([p["score_zero"] for p in picks], dtype=np.int64),
+              "score_best": np.array([p["score_best"] for p in picks], dtype=np.int64),
+              "candidates": int(np.sum(cands))}
+    return rows, report
+
+
+def _own_lines(lines_per_slice):
+    return [[np.array(v, dtype=np.float64).reshape(-1, 3) for v in ls] for ls in lines_per_slice]
 
 
 def align_lines(points, slice_offsets, lines_per_slice, max_shift=COARSE_HALF, radius=RADIUS, intensity_floor=0.0,
@@ -382,22 +414,16 @@ def align_lines(points, slice_offsets, lines_per_slice, max_shift=COARSE_HALF, r
         raise ValueError(f"{what}: max_shift gives {len(coarse)} coarse shifts, at most {MAX_SHIFTS}")
     pick_kw = {"min_points": min_points, "keep": keep, "gain": gain}
     pick_shift(np.zeros((1, 2)), [0], [0], **pick_kw)         # validates min_points, keep and gain
-    lines = [[np.array(v, dtype=np.float64).reshape(-1, 3) for v in ls] for ls in lines_per_slice]
-    n_s = len(lines)
-    off = _host(slice_offsets, np.int64).reshape(-1)
-    first, _ = _stage(points, off, lines, [coarse] * n_s, scope, radius, intensity_floor, pick_kw, what)
-    fine = [np.concatenate([shift_grid(p["shift"], FINE_HALF, FINE_STEP), np.zeros((1, 2))]) for p in first]
-    picks, cands = _stage(points, off, lines, fine, scope, radius, intensity_floor, pick_kw, what)
-    shifts = np.array([p["shift"] for p in picks], dtype=np.float64).reshape(n_s, 2)
+    lines = _own_lines(lines_per_slice)
+    off = G.host(slice_offsets, np.int64).reshape(-1)
+    shifts, report = _two_stage(
+        what, points, off, lines, scope, radius, intensity_floor, coarse,
+        lambda c: np.concatenate([shift_grid(c, FINE_HALF, FINE_STEP), np.zeros((1, 2))]),
+        lambda t, sc, ht: pick_shift(t, sc, ht, **pick_kw), "shift", lambda rows: {"shifts": rows})
     for s, ls in enumerate(lines):
         for v in ls:
             v[:, 0] = v[:, 0] + shifts[s, 0]
             v[:, 1] = v[:, 1] + shifts[s, 1]
-    aligned = int(sum(1 for p in picks if p["aligned"]))
-    report = {"frames": n_s, "frames_aligned": aligned, "frames_unaligned": n_s - aligned, "shifts": shifts,
-              "score_zero": np.array([p["score_zero"] for p in picks], dtype=np.int64),
-              "score_best": np.array([p["score_best"] for p in picks], dtype=np.int64),
-              "candidates": int(np.sum(cands))}
     return lines, report
 
 
@@ -432,7 +458,7 @@ def _pivots(pivots, n_s, what):
     shape = tuple(pivots.shape) if torch.is_tensor(pivots) else np.shape(pivots)
     if shape != (n_s, 2):
         raise ValueError(f"{what}: pivots must be ({n_s},2) x y, one per slice, got {shape}")
-    pv = np.ascontiguousarray(_host(pivots, np.float64).reshape(n_s, 2))
+    pv = np.ascontiguousarray(G.host(pivots, np.float64).reshape(n_s, 2))
     if not (np.isfinite(pv).all() and (n_s == 0 or np.abs(pv).max() <= MAX_COORD)):
         raise ValueError(f"{what}: pivots must be finite and within {MAX_COORD:g} m of the slice's origin")
     return pv
@@ -465,35 +491,16 @@ def pick_pose(poses, score, hits, lever=LEVER, min_points=MIN_POINTS, keep=KEEP,
     """Steps 6'-10 of the rigid rule over one table.  poses (K,3) float64 dx dy theta, score and hits
     (K,) integers.  Returns {'pose' (3,) float64, 'row' (the accepted row, or k0), 'aligned' bool,
     'score_zero', 'score_best' (Python ints: the score at (0, 0, 0) and at the near-best row)}."""
-    what = "pick_pose"
     ps = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
-    sc = [int(x) for x in np.asarray(score).reshape(-1)]
-    ht = [int(x) for x in np.asarray(hits).reshape(-1)]
-    if not (len(ps) == len(sc) == len(ht)):
-        raise ValueError(f"{what}: one score and one hit count per pose")
-    keep_num, keep_den = _ratio(keep, what, "keep", False)
-    gain_num, gain_den = _ratio(gain, what, "gain", True)
-    if int(min_points) != min_points or int(min_points) < 1:
-        raise ValueError(f"{what}: min_points must be an integer >= 1")
-    lever = float(lever)
-    if not (np.isfinite(lever) and lever > 0.0):
-        raise ValueError(f"{what}: lever must be positive and finite")
-    zero = np.flatnonzero((ps[:, 0] == 0.0) & (ps[:, 1] == 0.0) & (ps[:, 2] == 0.0))
-    if len(zero) == 0:
-        raise ValueError(f"{what}: the table must contain the pose (0, 0, 0)")
-    k0 = int(zero[0])
-    none = {"pose": np.zeros(3), "row": k0, "aligned": False, "score_zero": sc[k0], "score_best": sc[k0]}
-    best = max(sc)
-    if best == 0 or ht[sc.index(best)] < int(min_points):
-        return none
-    near = [k for k in range(len(sc)) if sc[k] * keep_den >= best * keep_num]
-    lt = lever * ps[near, 2]
-    n2 = ps[near, 0] * ps[near, 0] + ps[near, 1] * ps[near, 1] + lt * lt
-    row = near[int(np.argmin(n2))]                           # argmin: the first of equal values, the lowest row
-    none["score_best"] = sc[row]
-    if not sc[row] * gain_den > sc[k0] * gain_num:
-        return none
-    return {"pose": ps[row].copy(), "row": row, "aligned": True, "score_zero": sc[k0], "score_best": sc[row]}
+
+    def check():
+        if not (np.isfinite(float(lever)) and float(lever) > 0.0):
+            raise ValueError("pick_pose: lever must be positive and finite")
+
+    def norm2(r):
+        lt = float(lever) * r[:, 2]
+        return r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + lt * lt
+    return _pick("pick_pose", ps, score, hits, norm2, "pose", "(0, 0, 0)", min_points, keep, gain, check)
 
 
 def apply_pose(vertices, pose, pivot=(0.0, 0.0)):
@@ -511,92 +518,6 @@ def apply_pose(vertices, pose, pivot=(0.0, 0.0)):
 
 
 # ------------------------------------------------------------------ rigid: GPU side
-def prepare_rigid(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots, radius, intensity_floor, cell, what):
-    """prepare for a pose table: 'sh' is the (K,4) table dx dy c s, 'reach' the rigid reach, 'pivots' (S,2)."""
-    radius, intensity_floor, cell = _params(radius, intensity_floor, cell, what)
-    dev = G.device("align", points.device if torch.is_tensor(points) and points.is_cuda else None)
-    pts = _points(points, dev, what)
-    off = _offsets(slice_offsets, pts.shape[0], what, "slice_offsets")
-    n_s = len(off) - 1
-    if len(lines_per_slice) != n_s:
-        raise ValueError(f"{what}: one list of lines per slice ({n_s}), got {len(lines_per_slice)}")
-    verts, l_off, sl_off = lines_csr(lines_per_slice, what)
-    shape = tuple(poses.shape) if torch.is_tensor(poses) else np.shape(poses)
-    if len(shape) != 2 or shape[1] != 3:
-        raise ValueError(f"{what}: poses must be (K,3) dx dy theta, got {shape}")
-    ps = np.ascontiguousarray(_host(poses, np.float64).reshape(-1, 3))
-    if not (np.isfinite(ps).all() and (len(ps) == 0 or (np.abs(ps[:, :2]).max() <= MAX_SHIFT
-                                                        and np.abs(ps[:, 2]).max() <= MAX_YAW))):
-        raise ValueError(f"{what}: poses must be finite with |dx|, |dy| <= {MAX_SHIFT:g} and |theta| <= {MAX_YAW:g}")
-    k_off = _offsets(pose_offsets, len(ps), what, "pose_offsets")
-    if len(k_off) != len(off):
-        raise ValueError(f"{what}: slice_offsets and pose_offsets must describe the same slices")
-    if n_s and int(np.diff(k_off).max()) > MAX_POSES:
-        raise ValueError(f"{what}: at most {MAX_POSES} poses per slice")
-    pv = _pivots(pivots, n_s, what)
-    reach = rigid_reach(ps, k_off, radius, verts, l_off, sl_off, pv)
-    maps = segment_bitmaps(verts, l_off, sl_off, reach, cell)
-    return {"dev": dev, "pts": pts, "off": off, "n_s": n_s, "verts": verts, "l_off": l_off, "sl_off": sl_off,
-            "sh": pose_table(ps), "k_off": k_off, "reach": reach, "maps": maps, "radius": radius, "pivots": pv,
-            "intensity_floor": intensity_floor, "what": what}
-
-
-def select_candidates_cells(p):
-    """prh_align_select_cells_count, the scan, prh_align_select_cells_write: what select_candidates
-    returns, a slice's records in ascending cell order (arrival order inside a cell)."""
-    lib, dev, pts, maps, n_s = L.lib(), p["dev"], p["pts"], p["maps"], p["n_s"]
-    n_cells = maps["n_cells"]
-    if n_s == 0 or pts.shape[0] == 0 or n_cells == 0:
-        return torch.empty((0, 4), dtype=torch.float64, device=dev), None, np.zeros(n_s + 1, dtype=np.int64)
-    counts = torch.zeros((n_cells,), dtype=torch.int32, device=dev)
-    off_t = torch.from_numpy(p["off"]).to(dev)
-    g_t = tuple(torch.from_numpy(np.ascontiguousarray(maps[k])).to(dev) for k in ("origin", "shape", "cell_base"))
-    bitmap = torch.from_numpy(maps["bitmap"].view(np.int32)).to(dev)
-    args = (G.ptr(pts), 1 if pts.dtype == torch.float64 else 0, G.ptr(off_t), n_s, pts.shape[0], G.ptr(g_t[0]), G.ptr(g_t[1]),
-            G.ptr(g_t[2]), G.ptr(bitmap), n_cells, maps["cell"], p["intensity_floor"])
-    L.check(lib.prh_align_select_cells_count(*args, G.ptr(counts), dev.index, G.stream(dev)), "prh_align_select_cells_count")
-    cell_off = G.exclusive_scan(counts)
-    # cells of a slice are contiguous from cell_base[s]: the slice's rows start at the scan there
-    cand_off = torch.cat([cell_off[g_t[2]], cell_off[-1:]]).contiguous()
-    c_off = cand_off.cpu().numpy()
-    total = int(c_off[-1])
-    rec = torch.empty((total, 4), dtype=torch.float64, device=dev)
-    if total:
-        nb = lib.prh_align_select_cells_workspace_bytes(n_cells)
-        ws = G.workspace(nb, dev)
-        L.check(lib.prh_align_select_cells_write(*args, G.ptr(cell_off), G.ptr(rec), total, G.ptr(ws), nb, dev.index,
-                                                 G.stream(dev)), "prh_align_select_cells_write")
-    return rec, cand_off, c_off
-
-
-def score_candidates_rigid(p, rec, cand_off, c_off):
-    """The plan and prh_align_score_rigid over the selected candidates: acc (K,2) int64 CUDA."""
-    dev, table = p["dev"], p["sh"]
-    acc = torch.zeros((len(table), 2), dtype=torch.int64, device=dev)
-    if p["n_s"] and int((np.diff(c_off) * np.diff(p["sl_off"])).max()) >= 2 ** 31:
-        raise OverflowError(f"{p['what']}: a slice has 2^31 or more (candidate, line) pairs")
-    items = work_items(c_off, p["k_off"], np.diff(p["l_off"][p["sl_off"]]))
-    if rec.shape[0] == 0 or len(items) == 0:
-        return acc
-    up = [torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-          for x in (p["verts"], p["l_off"], p["sl_off"], table, p["k_off"], p["pivots"], p["reach"], items)]
-    L.check(L.lib().prh_align_score_rigid(G.ptr(rec), G.ptr(cand_off), rec.shape[0], G.ptr(up[0]), len(p["verts"]),
-                                          G.ptr(up[1]), len(p["l_off"]) - 1, G.ptr(up[2]), G.ptr(up[3]), G.ptr(up[4]),
-                                          len(table), G.ptr(up[5]), G.ptr(up[6]), p["n_s"], G.ptr(up[7]), len(items),
-                                          p["radius"] * p["radius"], G.ptr(acc), dev.index, G.stream(dev)),
-            "prh_align_score_rigid")
-    return acc
-
-
-def _rigid(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots, radius, intensity_floor, cell, order, what):
-    if order not in ("cell", "arrival"):
-        raise ValueError(f"{what}: order must be 'cell' or 'arrival'")
-    p = prepare_rigid(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots, radius, intensity_floor, cell, what)
-    rec, cand_off, c_off = select_candidates_cells(p) if order == "cell" else select_candidates(p)
-    acc = score_candidates_rigid(p, rec, cand_off, c_off)
-    return {"score": acc[:, 0], "hits": acc[:, 1], "candidates": np.diff(c_off)}
-
-
 def rigid_scores(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots=None, radius=RADIUS,
                  intensity_floor=0.0, cell=CELL, order=ORDER):
     """The paint score of every (slice, pose) ("Rigid paint alignment - the rule", steps 1-5).
@@ -606,33 +527,13 @@ def rigid_scores(points, slice_offsets, lines_per_slice, poses, pose_offsets, pi
     |theta| <= 0.1 rad, at most MAX_POSES rows per slice.  A pose moves a line vertex p to R(theta)(p
     - pivot) + pivot + (dx, dy); pivots (S,2), one per slice, default (0, 0).  The cosine and sine go
     to the device as pose_table computes them.  order: 'cell' hands the score kernel each slice's
-    candidates sorted by bitmap cell, 'arrival' in the order select_candidates leaves them - cost
+    candidates sorted by bitmap cell, 'arrival' in the order of the per-slice filter - cost
     only, the tables are bitwise equal.  Returns a dict of CUDA tensors 'score' (K,) int64 and 'hits'
     (K,) int64.  A table whose thetas are all 0, with the default pivots, gives paint_scores'
     integers."""
-    res = _rigid(points, slice_offsets, lines_per_slice, poses, pose_offsets, pivots, radius, intensity_floor, cell, order,
-                 "rigid_scores")
+    res = _scores(points, slice_offsets, lines_per_slice, poses, pose_offsets, radius, intensity_floor, cell, "rigid_scores",
+                  pivots, True, order)
     return {"score": res["score"], "hits": res["hits"]}
-
-
-def _stage_rigid(points, off, lines, tables, pivots, scope, radius, intensity_floor, lever, pick_kw, what):
-    """_stage for pose tables."""
-    n_s = len(lines)
-    if n_s == 0:
-        return [], np.zeros(0, dtype=np.int64)
-    k_off = np.zeros(n_s + 1, dtype=np.int64)
-    k_off[1:] = np.cumsum([len(t) for t in tables])
-    res = _rigid(points, off, lines, np.concatenate(tables), k_off, pivots, radius, intensity_floor, CELL, ORDER, what)
-    score, hits = res["score"].cpu().numpy(), res["hits"].cpu().numpy()
-    if scope == "drive":
-        k = len(tables[0])
-        one = pick_pose(tables[0], [int(x) for x in score.reshape(n_s, k).astype(object).sum(axis=0)],
-                        [int(x) for x in hits.reshape(n_s, k).astype(object).sum(axis=0)], lever, **pick_kw)
-        picks = [one] * n_s
-    else:
-        picks = [pick_pose(tables[s], score[k_off[s]:k_off[s + 1]], hits[k_off[s]:k_off[s + 1]], lever, **pick_kw)
-                 for s in range(n_s)]
-    return picks, res["candidates"]
 
 
 def align_lines_rigid(points, slice_offsets, lines_per_slice, max_shift=COARSE_HALF, max_yaw=COARSE_YAW, lever=LEVER,
@@ -661,21 +562,22 @@ def align_lines_rigid(points, slice_offsets, lines_per_slice, max_shift=COARSE_H
         raise ValueError(f"{what}: max_shift and max_yaw give {len(coarse)} coarse poses, at most {MAX_POSES}")
     pick_kw = {"min_points": min_points, "keep": keep, "gain": gain}
     pick_pose(np.zeros((1, 3)), [0], [0], lever, **pick_kw)   # validates lever, min_points, keep and gain
-    lines = [[np.array(v, dtype=np.float64).reshape(-1, 3) for v in ls] for ls in lines_per_slice]
-    n_s = len(lines)
-    off = _host(slice_offsets, np.int64).reshape(-1)
-    pv = _pivots(pivots, n_s, what)
+    lines = _own_lines(lines_per_slice)
+    off = G.host(slice_offsets, np.int64).reshape(-1)
+    pv = _pivots(pivots, len(lines), what)
     fine_yaw = FINE_YAW_HALF if max_yaw > 0.0 else 0.0
-    first, _ = _stage_rigid(points, off, lines, [coarse] * n_s, pv, scope, radius, intensity_floor, lever, pick_kw, what)
-    fine = [np.concatenate([pose_grid(p["pose"][:2], FINE_HALF, FINE_STEP, p["pose"][2], fine_yaw, FINE_YAW_STEP),
-                            np.zeros((1, 3))]) for p in first]
-    picks, cands = _stage_rigid(points, off, lines, fine, pv, scope, radius, intensity_floor, lever, pick_kw, what)
-    poses = np.array([p["pose"] for p in picks], dtype=np.float64).reshape(n_s, 3)
-    moved = [[apply_pose(v, poses[s], pv[s]) for v in ls] for s, ls in enumerate(lines)]
-    aligned = int(sum(1 for p in picks if p["aligned"]))
-    report = {"frames": n_s, "frames_aligned": aligned, "frames_unaligned": n_s - aligned,
-              "shifts": np.ascontiguousarray(poses[:, :2]), "yaws": np.ascontiguousarray(poses[:, 2]),
-              "score_zero": np.array([p["score_zero"] for p in picks], dtype=np.int64),
-              "score_best": np.array([p["score_best"] for p in picks], dtype=np.int64),
-              "candidates": int(np.sum(cands))}
-    return moved, report
+    poses, report = _two_stage(
+        what, points, off, lines, scope, radius, intensity_floor, coarse,
+        lambda c: np.concatenate([pose_grid(c[:2], FINE_HALF, FINE_STEP, c[2], fine_yaw, FINE_YAW_STEP), np.zeros((1, 3))]),
+        lambda t, sc, ht: pick_pose(t, sc, ht, lever, **pick_kw), "pose",
+        lambda rows: {"shifts": np.ascontiguousarray(rows[:, :2]), "yaws": np.ascontiguousarray(rows[:, 2])},
+        pivots=pv, rigid=True, order=ORDER)
+    return [[apply_pose(v, poses[s], pv[s]) for v in ls] for s, ls in enumerate(lines)], report
+
+
+def align(points, slice_offsets, lines_per_slice, max_yaw=0.0, **kw):
+    """align_lines(points, slice_offsets, lines_per_slice, **kw) at max_yaw = 0, align_lines_rigid(..., max_yaw=max_yaw,
+    **kw) above it: the shift path and its kernels run untouched unless a yaw is asked for."""
+    if float(max_yaw) > 0.0:
+        return align_lines_rigid(points, slice_offsets, lines_per_slice, max_yaw=max_yaw, **kw)
+    return align_lines(points, slice_offsets, lines_per_slice, **kw)

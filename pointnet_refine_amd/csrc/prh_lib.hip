@@ -1265,6 +1265,11 @@ void lin16_carve(Arena& a, Lin16WS& w, int rows, int k, int n, bool backward) {
 inline bool lin16_ws_ok(const Arena& a, const void* workspace, size_t workspace_bytes) {
   return workspace != nullptr && a.ok && workspace_bytes >= a.off + 256;
 }
+// f(T{}) with T = double or float: the kernel instantiation a points buffer of that type takes (ground lift, paint alignment)
+template <typename F> void for_points(int is_double, F f) {
+  if (is_double) f(double{}); else f(float{});
+}
+
 }  // namespace
 
 // =======================================================================================
@@ -3673,7 +3678,25 @@ int prh_support_accumulate(const float* cloud, long long n_points, double origin
   return PRH_OK;
 }
 
-// ------------------------------------------------------------------ ground lift
+// ------------------------------------------------------------------ ground lift, paint alignment
+// What every entry that takes a slice grid checks first, in one order.  align_mask and align_text: the points'
+// alignment rule; floor_ok and bitmap_ok: the two checks the paint-alignment entries add in their places
+// (ground lift has neither).
+static int check_grid(const char* what, const void* points, unsigned align_mask, const char* align_text,
+                      const long long* slice_offsets, int n_slices, long long n_points, const double* grid_origin,
+                      const int* grid_shape, const long long* cell_base, long long n_cells, double cell,
+                      bool floor_ok = true, bool bitmap_ok = true) {
+  if (n_slices < 0 || n_points < 0 || n_cells < 0 || n_cells > 0x7fffffffll || n_points >= 256ll * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "%s: bad argument (at most 2^31 - 1 cells)", what);
+  if (!(cell > 0.0) || !(cell < 1e300)) return fail(PRH_ERR_ARG, "%s: cell must be positive and finite", what);
+  if (!floor_ok) return fail(PRH_ERR_ARG, "%s: intensity_floor must be finite", what);
+  if ((n_slices > 0 && (!slice_offsets || !grid_origin || !grid_shape || !cell_base)) || !bitmap_ok)
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if (n_points > 0 && (!points || n_slices == 0)) return fail(PRH_ERR_ARG, "%s: points without a slice", what);
+  if (((uintptr_t)points & align_mask) != 0) return fail(PRH_ERR_ARG, "%s: points must be %s", what, align_text);
+  return PRH_OK;
+}
+
 int prh_ground_max_bins(void) { return GROUND_MAX_BINS; }
 size_t prh_ground_bin_workspace_bytes(long long n_cells) {
   return n_cells < 0 ? 0 : align_up((size_t)n_cells * sizeof(int), 256);
@@ -3681,67 +3704,57 @@ size_t prh_ground_bin_workspace_bytes(long long n_cells) {
 static int ground_check_grid(const char* what, const void* points, int is_double, const long long* slice_offsets,
                              int n_slices, long long n_points, const double* grid_origin, const int* grid_shape,
                              const long long* cell_base, long long n_cells, double cell) {
-  if (n_slices < 0 || n_points < 0 || n_cells < 0 || n_cells > 0x7fffffffll || n_points >= 256ll * 0x7fffffff)
-    return fail(PRH_ERR_ARG, "%s: bad argument (at most 2^31 - 1 cells)", what);
-  if (!(cell > 0.0) || !(cell < 1e300)) return fail(PRH_ERR_ARG, "%s: cell must be positive and finite", what);
-  if (n_slices > 0 && (!slice_offsets || !grid_origin || !grid_shape || !cell_base))
-    return fail(PRH_ERR_ARG, "%s: null pointer", what);
-  if (n_points > 0 && (!points || n_slices == 0)) return fail(PRH_ERR_ARG, "%s: points without a slice", what);
-  if (((uintptr_t)points & (is_double ? 15 : 7)) != 0)
-    return fail(PRH_ERR_ARG, "%s: points must be aligned to two coordinates (%d bytes)", what, is_double ? 16 : 8);
+  return check_grid(what, points, is_double ? 15 : 7,
+                    is_double ? "aligned to two coordinates (16 bytes)" : "aligned to two coordinates (8 bytes)",
+                    slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell);
+}
+// count (counter: the caller's cell_counts, zeroed here) or write (counter: the cursors, in the workspace)
+static int ground_bin(bool write, const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                      long long n_points, const double* grid_origin, const int* grid_shape, const long long* cell_base,
+                      long long n_cells, double cell, int* cell_counts, const long long* cell_offsets, int* rows,
+                      long long capacity, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const char* what = write ? "ground_bin_write" : "ground_bin_count";
+  TRY_RC(ground_check_grid(what, points, is_double, slice_offsets, n_slices, n_points, grid_origin, grid_shape,
+                           cell_base, n_cells, cell));
+  if (write) {
+    if (capacity < 0) return fail(PRH_ERR_ARG, "%s: bad capacity", what);
+    if (n_cells == 0 || n_points == 0 || capacity == 0) return PRH_OK;
+    if (!cell_offsets || !rows) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+    if (!workspace || workspace_bytes < prh_ground_bin_workspace_bytes(n_cells))
+      return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  } else {
+    if (n_cells == 0) return PRH_OK;
+    if (!cell_counts) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  }
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* counter = write ? (int*)workspace : cell_counts;
+  HIP_TRY(hipMemsetAsync(counter, 0, (size_t)n_cells * sizeof(int), st));
+  if (n_points == 0) return PRH_OK;
+  const unsigned nblk = (unsigned)((n_points + GROUND_THREADS - 1) / GROUND_THREADS);
+  for_points(is_double, [&](auto t) {
+    using T = decltype(t);
+    auto kernel = write ? ground_bin_kernel<T, true> : ground_bin_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(GROUND_THREADS), 0, st, (const T*)points, slice_offsets, n_slices,
+                       n_points, grid_origin, grid_shape, cell_base, n_cells, cell, counter, cell_offsets, rows, capacity);
+  });
+  LAUNCH_CHECK();
   return PRH_OK;
 }
 int prh_ground_bin_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
                          long long n_points, const double* grid_origin, const int* grid_shape,
                          const long long* cell_base, long long n_cells, double cell, int* cell_counts, int device,
                          void* stream) {
-  TRY_RC(ground_check_grid("ground_bin_count", points, is_double, slice_offsets, n_slices, n_points, grid_origin,
-                           grid_shape, cell_base, n_cells, cell));
-  if (n_cells == 0) return PRH_OK;
-  if (!cell_counts) return fail(PRH_ERR_ARG, "ground_bin_count: null pointer");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(cell_counts, 0, (size_t)n_cells * sizeof(int), st));
-  if (n_points == 0) return PRH_OK;
-  const unsigned nblk = (unsigned)((n_points + GROUND_THREADS - 1) / GROUND_THREADS);
-  if (is_double)
-    hipLaunchKernelGGL((ground_bin_kernel<double, false>), dim3(nblk), dim3(GROUND_THREADS), 0, st, (const double*)points,
-                       slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell, cell_counts,
-                       (const long long*)nullptr, (int*)nullptr, 0ll);
-  else
-    hipLaunchKernelGGL((ground_bin_kernel<float, false>), dim3(nblk), dim3(GROUND_THREADS), 0, st, (const float*)points,
-                       slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell, cell_counts,
-                       (const long long*)nullptr, (int*)nullptr, 0ll);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  return ground_bin(false, points, is_double, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                    n_cells, cell, cell_counts, nullptr, nullptr, 0, nullptr, 0, device, stream);
 }
 int prh_ground_bin_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
                          long long n_points, const double* grid_origin, const int* grid_shape,
                          const long long* cell_base, long long n_cells, double cell, const long long* cell_offsets,
                          int* rows, long long capacity, void* workspace, size_t workspace_bytes, int device,
                          void* stream) {
-  TRY_RC(ground_check_grid("ground_bin_write", points, is_double, slice_offsets, n_slices, n_points, grid_origin,
-                           grid_shape, cell_base, n_cells, cell));
-  if (capacity < 0) return fail(PRH_ERR_ARG, "ground_bin_write: bad capacity");
-  if (n_cells == 0 || n_points == 0 || capacity == 0) return PRH_OK;
-  if (!cell_offsets || !rows) return fail(PRH_ERR_ARG, "ground_bin_write: null pointer");
-  if (!workspace || workspace_bytes < prh_ground_bin_workspace_bytes(n_cells))
-    return fail(PRH_ERR_WORKSPACE, "ground_bin_write: workspace too small (%zu bytes)", workspace_bytes);
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  int* cursor = (int*)workspace;
-  HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)n_cells * sizeof(int), st));
-  const unsigned nblk = (unsigned)((n_points + GROUND_THREADS - 1) / GROUND_THREADS);
-  if (is_double)
-    hipLaunchKernelGGL((ground_bin_kernel<double, true>), dim3(nblk), dim3(GROUND_THREADS), 0, st, (const double*)points,
-                       slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell, cursor,
-                       cell_offsets, rows, capacity);
-  else
-    hipLaunchKernelGGL((ground_bin_kernel<float, true>), dim3(nblk), dim3(GROUND_THREADS), 0, st, (const float*)points,
-                       slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base, n_cells, cell, cursor,
-                       cell_offsets, rows, capacity);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  return ground_bin(true, points, is_double, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
+                    n_cells, cell, nullptr, cell_offsets, rows, capacity, workspace, workspace_bytes, device, stream);
 }
 int prh_ground_query(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long n_points,
                      const double* queries, const long long* query_offsets, long long n_queries,
@@ -3768,92 +3781,126 @@ int prh_ground_query(const void* points, int is_double, const long long* slice_o
   hipStream_t st = (hipStream_t)stream;
   GroundParams prm{r2, reach, cell, z_lo, bin, n_bins, min_points, peak_num, peak_den};
   const unsigned nblk = (unsigned)((n_queries + GROUND_WAVES - 1) / GROUND_WAVES);
-  if (is_double)
-    hipLaunchKernelGGL(ground_query_kernel<double>, dim3(nblk), dim3(GROUND_THREADS), 0, st, (const double*)points,
-                       slice_offsets, n_slices, queries, query_offsets, n_queries, grid_origin, grid_shape, cell_base,
-                       cell_offsets, rows, n_rows, n_cells, prm, height, count, hits, bin_index);
-  else
-    hipLaunchKernelGGL(ground_query_kernel<float>, dim3(nblk), dim3(GROUND_THREADS), 0, st, (const float*)points,
-                       slice_offsets, n_slices, queries, query_offsets, n_queries, grid_origin, grid_shape, cell_base,
-                       cell_offsets, rows, n_rows, n_cells, prm, height, count, hits, bin_index);
+  for_points(is_double, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(ground_query_kernel<T>, dim3(nblk), dim3(GROUND_THREADS), 0, st, (const T*)points, slice_offsets,
+                       n_slices, queries, query_offsets, n_queries, grid_origin, grid_shape, cell_base, cell_offsets, rows,
+                       n_rows, n_cells, prm, height, count, hits, bin_index);
+  });
   LAUNCH_CHECK();
   return PRH_OK;
 }
 
-// ------------------------------------------------------------------ paint alignment
 int prh_align_tile(void) { return ALIGN_TILE; }
 int prh_align_max_shifts(void) { return ALIGN_MAX_SHIFTS; }
+int prh_align_max_poses(void) { return ALIGN_MAX_POSES; }
 size_t prh_align_select_workspace_bytes(int n_slices) {
   return n_slices < 0 ? 0 : align_up((size_t)n_slices * sizeof(int), 256);
 }
-static int align_check_select(const char* what, const void* points, int is_double, const long long* slice_offsets,
-                              int n_slices, long long n_points, const double* grid_origin, const int* grid_shape,
-                              const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
-                              double intensity_floor) {
-  if (n_slices < 0 || n_points < 0 || n_cells < 0 || n_cells > 0x7fffffffll || n_points >= 256ll * 0x7fffffff)
-    return fail(PRH_ERR_ARG, "%s: bad argument (at most 2^31 - 1 cells)", what);
-  if (!(cell > 0.0) || !(cell < 1e300)) return fail(PRH_ERR_ARG, "%s: cell must be positive and finite", what);
-  if (!(intensity_floor == intensity_floor) || !(intensity_floor > -1e300) || !(intensity_floor < 1e300))
-    return fail(PRH_ERR_ARG, "%s: intensity_floor must be finite", what);
-  if (n_slices > 0 && (!slice_offsets || !grid_origin || !grid_shape || !cell_base))
-    return fail(PRH_ERR_ARG, "%s: null pointer", what);
-  if (n_cells > 0 && !bitmap) return fail(PRH_ERR_ARG, "%s: null pointer", what);
-  if (n_points > 0 && (!points || n_slices == 0)) return fail(PRH_ERR_ARG, "%s: points without a slice", what);
-  if (((uintptr_t)points & 15) != 0) return fail(PRH_ERR_ARG, "%s: points must be 16-byte aligned", what);
+size_t prh_align_select_cells_workspace_bytes(long long n_cells) {
+  return n_cells < 0 ? 0 : align_up((size_t)n_cells * sizeof(int), 256);
+}
+// The candidate filter in arrival order (one counter per slice) or, by_cell, in cell order (one per bitmap cell):
+// count (counter: the caller's counts, zeroed here) or write (counter: the cursors, in the workspace; offsets: the
+// exclusive scan of the counts).
+static int align_select(bool by_cell, bool write, const void* points, int is_double, const long long* slice_offsets,
+                        int n_slices, long long n_points, const double* grid_origin, const int* grid_shape,
+                        const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                        double intensity_floor, int* counts, const long long* offsets, void* records,
+                        long long capacity, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const char* what = by_cell ? (write ? "align_select_cells_write" : "align_select_cells_count")
+                             : (write ? "align_select_write" : "align_select_count");
+  TRY_RC(check_grid(what, points, 15, "16-byte aligned", slice_offsets, n_slices, n_points, grid_origin, grid_shape,
+                    cell_base, n_cells, cell, intensity_floor > -1e300 && intensity_floor < 1e300,
+                    !(n_cells > 0 && !bitmap)));
+  const long long n_counters = by_cell ? n_cells : n_slices;
+  if (write) {
+    if (capacity < 0) return fail(PRH_ERR_ARG, "%s: bad capacity", what);
+    if (n_slices == 0 || n_points == 0 || n_cells == 0 || capacity == 0) return PRH_OK;
+    if (!offsets || !records) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+    if (((uintptr_t)records & 15) != 0) return fail(PRH_ERR_ARG, "%s: records must be 16-byte aligned", what);
+    if (!workspace || workspace_bytes < (by_cell ? prh_align_select_cells_workspace_bytes(n_cells)
+                                                 : prh_align_select_workspace_bytes(n_slices)))
+      return fail(PRH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes)", what, workspace_bytes);
+  } else {
+    if (n_counters == 0 || n_slices == 0) return PRH_OK;
+    if (!counts) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  }
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  int* counter = write ? (int*)workspace : counts;
+  HIP_TRY(hipMemsetAsync(counter, 0, (size_t)n_counters * sizeof(int), st));
+  if (n_points == 0 || n_cells == 0) return PRH_OK;
+  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
+  for_points(is_double, [&](auto t) {
+    using T = decltype(t);
+    auto kernel = by_cell ? (write ? align_select_cells_kernel<T, true> : align_select_cells_kernel<T, false>)
+                          : (write ? align_select_kernel<T, true> : align_select_kernel<T, false>);
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(ALIGN_THREADS), 0, st, (const T*)points, slice_offsets, n_slices,
+                       n_points, grid_origin, grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor, counter,
+                       offsets, (AlignRecord*)records, capacity);
+  });
+  LAUNCH_CHECK();
   return PRH_OK;
 }
 int prh_align_select_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
                            long long n_points, const double* grid_origin, const int* grid_shape,
                            const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
                            double intensity_floor, int* slice_counts, int device, void* stream) {
-  TRY_RC(align_check_select("align_select_count", points, is_double, slice_offsets, n_slices, n_points, grid_origin,
-                            grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor));
-  if (n_slices == 0) return PRH_OK;
-  if (!slice_counts) return fail(PRH_ERR_ARG, "align_select_count: null pointer");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(slice_counts, 0, (size_t)n_slices * sizeof(int), st));
-  if (n_points == 0 || n_cells == 0) return PRH_OK;
-  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
-  if (is_double)
-    hipLaunchKernelGGL((align_select_kernel<double, false>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
-                       (const double*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
-                       bitmap, n_cells, cell, intensity_floor, slice_counts, (const long long*)nullptr,
-                       (AlignRecord*)nullptr, 0ll);
-  else
-    hipLaunchKernelGGL((align_select_kernel<float, false>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
-                       (const float*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
-                       bitmap, n_cells, cell, intensity_floor, slice_counts, (const long long*)nullptr,
-                       (AlignRecord*)nullptr, 0ll);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  return align_select(false, false, points, is_double, slice_offsets, n_slices, n_points, grid_origin, grid_shape,
+                      cell_base, bitmap, n_cells, cell, intensity_floor, slice_counts, nullptr, nullptr, 0, nullptr, 0,
+                      device, stream);
 }
 int prh_align_select_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
                            long long n_points, const double* grid_origin, const int* grid_shape,
                            const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
                            double intensity_floor, const long long* cand_offsets, void* records, long long capacity,
                            void* workspace, size_t workspace_bytes, int device, void* stream) {
-  TRY_RC(align_check_select("align_select_write", points, is_double, slice_offsets, n_slices, n_points, grid_origin,
-                            grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor));
-  if (capacity < 0) return fail(PRH_ERR_ARG, "align_select_write: bad capacity");
-  if (n_slices == 0 || n_points == 0 || n_cells == 0 || capacity == 0) return PRH_OK;
-  if (!cand_offsets || !records) return fail(PRH_ERR_ARG, "align_select_write: null pointer");
-  if (((uintptr_t)records & 15) != 0) return fail(PRH_ERR_ARG, "align_select_write: records must be 16-byte aligned");
-  if (!workspace || workspace_bytes < prh_align_select_workspace_bytes(n_slices))
-    return fail(PRH_ERR_WORKSPACE, "align_select_write: workspace too small (%zu bytes)", workspace_bytes);
+  return align_select(false, true, points, is_double, slice_offsets, n_slices, n_points, grid_origin, grid_shape,
+                      cell_base, bitmap, n_cells, cell, intensity_floor, nullptr, cand_offsets, records, capacity,
+                      workspace, workspace_bytes, device, stream);
+}
+int prh_align_select_cells_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                                 long long n_points, const double* grid_origin, const int* grid_shape,
+                                 const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                                 double intensity_floor, int* cell_counts, int device, void* stream) {
+  return align_select(true, false, points, is_double, slice_offsets, n_slices, n_points, grid_origin, grid_shape,
+                      cell_base, bitmap, n_cells, cell, intensity_floor, cell_counts, nullptr, nullptr, 0, nullptr, 0,
+                      device, stream);
+}
+int prh_align_select_cells_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                                 long long n_points, const double* grid_origin, const int* grid_shape,
+                                 const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
+                                 double intensity_floor, const long long* cell_offsets, void* records,
+                                 long long capacity, void* workspace, size_t workspace_bytes, int device,
+                                 void* stream) {
+  return align_select(true, true, points, is_double, slice_offsets, n_slices, n_points, grid_origin, grid_shape,
+                      cell_base, bitmap, n_cells, cell, intensity_floor, nullptr, cell_offsets, records, capacity,
+                      workspace, workspace_bytes, device, stream);
+}
+// the score sweep over a shift table (K,2) or, rigid, a pose table (K,4) with the slices' pivots
+static int align_score(bool rigid, const void* records, const long long* cand_offsets, long long n_candidates,
+                       const double* line_vertices, long long n_vertices, const long long* line_offsets, int n_lines,
+                       const long long* slice_line_offsets, const double* table, const long long* table_offsets,
+                       long long n_rows, const double* pivots, const double* reach, int n_slices, const long long* items,
+                       long long n_items, double r2, long long* acc, int device, void* stream) {
+  const char* what = rigid ? "align_score_rigid" : "align_score";
+  if (n_candidates < 0 || n_vertices < 0 || n_lines < 0 || n_rows < 0 || n_slices < 0 || n_items < 0 ||
+      n_items > 0x7fffffffll)
+    return fail(PRH_ERR_ARG, "%s: bad argument (at most 2^31 - 1 work items)", what);
+  if (!(r2 > 0.0) || !(r2 <= 1.0)) return fail(PRH_ERR_ARG, "%s: 0 < radius <= 1", what);
+  if (n_items == 0) return PRH_OK;
+  if (!records || !cand_offsets || !line_vertices || !line_offsets || !slice_line_offsets || !table || !table_offsets ||
+      (rigid && !pivots) || !reach || !items || !acc || n_slices == 0)
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  if (((uintptr_t)records & 15) != 0 || (rigid && ((uintptr_t)table & 15) != 0))
+    return fail(PRH_ERR_ARG, "%s: %s must be 16-byte aligned", what, rigid ? "records and poses" : "records");
   HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  int* cursor = (int*)workspace;
-  HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)n_slices * sizeof(int), st));
-  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
-  if (is_double)
-    hipLaunchKernelGGL((align_select_kernel<double, true>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
-                       (const double*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
-                       bitmap, n_cells, cell, intensity_floor, cursor, cand_offsets, (AlignRecord*)records, capacity);
-  else
-    hipLaunchKernelGGL((align_select_kernel<float, true>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
-                       (const float*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
-                       bitmap, n_cells, cell, intensity_floor, cursor, cand_offsets, (AlignRecord*)records, capacity);
+  auto kernel = rigid ? align_score_kernel<true> : align_score_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_items), dim3(ALIGN_THREADS), 0, (hipStream_t)stream,
+                     (const AlignRecord*)records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets,
+                     n_lines, slice_line_offsets, table, table_offsets, n_rows, reach, n_slices, items, r2,
+                     (unsigned long long*)acc, pivots);
   LAUNCH_CHECK();
   return PRH_OK;
 }
@@ -3862,85 +3909,9 @@ int prh_align_score(const void* records, const long long* cand_offsets, long lon
                     const long long* slice_line_offsets, const double* shifts, const long long* shift_offsets,
                     long long n_shifts, const double* reach, int n_slices, const long long* items, long long n_items,
                     double r2, long long* acc, int device, void* stream) {
-  if (n_candidates < 0 || n_vertices < 0 || n_lines < 0 || n_shifts < 0 || n_slices < 0 || n_items < 0 ||
-      n_items > 0x7fffffffll)
-    return fail(PRH_ERR_ARG, "align_score: bad argument (at most 2^31 - 1 work items)");
-  if (!(r2 > 0.0) || !(r2 <= 1.0)) return fail(PRH_ERR_ARG, "align_score: 0 < radius <= 1");
-  if (n_items == 0) return PRH_OK;
-  if (!records || !cand_offsets || !line_vertices || !line_offsets || !slice_line_offsets || !shifts || !shift_offsets ||
-      !reach || !items || !acc || n_slices == 0)
-    return fail(PRH_ERR_ARG, "align_score: null pointer");
-  if (((uintptr_t)records & 15) != 0) return fail(PRH_ERR_ARG, "align_score: records must be 16-byte aligned");
-  HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(align_score_kernel<false>, dim3((unsigned)n_items), dim3(ALIGN_THREADS), 0, (hipStream_t)stream,
-                     (const AlignRecord*)records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets,
-                     n_lines, slice_line_offsets, shifts, shift_offsets, n_shifts, reach, n_slices, items, r2,
-                     (unsigned long long*)acc, (const double*)nullptr);
-  LAUNCH_CHECK();
-  return PRH_OK;
-}
-
-// ------------------------------------------------------------------ rigid paint alignment
-int prh_align_max_poses(void) { return ALIGN_MAX_POSES; }
-size_t prh_align_select_cells_workspace_bytes(long long n_cells) {
-  return n_cells < 0 ? 0 : align_up((size_t)n_cells * sizeof(int), 256);
-}
-int prh_align_select_cells_count(const void* points, int is_double, const long long* slice_offsets, int n_slices,
-                                 long long n_points, const double* grid_origin, const int* grid_shape,
-                                 const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
-                                 double intensity_floor, int* cell_counts, int device, void* stream) {
-  TRY_RC(align_check_select("align_select_cells_count", points, is_double, slice_offsets, n_slices, n_points,
-                            grid_origin, grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor));
-  if (n_slices == 0 || n_cells == 0) return PRH_OK;
-  if (!cell_counts) return fail(PRH_ERR_ARG, "align_select_cells_count: null pointer");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(cell_counts, 0, (size_t)n_cells * sizeof(int), st));
-  if (n_points == 0) return PRH_OK;
-  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
-  if (is_double)
-    hipLaunchKernelGGL((align_select_cells_kernel<double, false>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
-                       (const double*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
-                       bitmap, n_cells, cell, intensity_floor, cell_counts, (const long long*)nullptr,
-                       (AlignRecord*)nullptr, 0ll);
-  else
-    hipLaunchKernelGGL((align_select_cells_kernel<float, false>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
-                       (const float*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
-                       bitmap, n_cells, cell, intensity_floor, cell_counts, (const long long*)nullptr,
-                       (AlignRecord*)nullptr, 0ll);
-  LAUNCH_CHECK();
-  return PRH_OK;
-}
-int prh_align_select_cells_write(const void* points, int is_double, const long long* slice_offsets, int n_slices,
-                                 long long n_points, const double* grid_origin, const int* grid_shape,
-                                 const long long* cell_base, const unsigned* bitmap, long long n_cells, double cell,
-                                 double intensity_floor, const long long* cell_offsets, void* records,
-                                 long long capacity, void* workspace, size_t workspace_bytes, int device,
-                                 void* stream) {
-  TRY_RC(align_check_select("align_select_cells_write", points, is_double, slice_offsets, n_slices, n_points,
-                            grid_origin, grid_shape, cell_base, bitmap, n_cells, cell, intensity_floor));
-  if (capacity < 0) return fail(PRH_ERR_ARG, "align_select_cells_write: bad capacity");
-  if (n_slices == 0 || n_points == 0 || n_cells == 0 || capacity == 0) return PRH_OK;
-  if (!cell_offsets || !records) return fail(PRH_ERR_ARG, "align_select_cells_write: null pointer");
-  if (((uintptr_t)records & 15) != 0)
-    return fail(PRH_ERR_ARG, "align_select_cells_write: records must be 16-byte aligned");
-  if (!workspace || workspace_bytes < prh_align_select_cells_workspace_bytes(n_cells))
-    return fail(PRH_ERR_WORKSPACE, "align_select_cells_write: workspace too small (%zu bytes)", workspace_bytes);
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  int* cursor = (int*)workspace;
-  HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)n_cells * sizeof(int), st));
-  const unsigned nblk = (unsigned)((n_points + ALIGN_THREADS - 1) / ALIGN_THREADS);
-  if (is_double)
-    hipLaunchKernelGGL((align_select_cells_kernel<double, true>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
-                       (const double*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
-                       bitmap, n_cells, cell, intensity_floor, cursor, cell_offsets, (AlignRecord*)records, capacity);
-  else
-    hipLaunchKernelGGL((align_select_cells_kernel<float, true>), dim3(nblk), dim3(ALIGN_THREADS), 0, st,
-                       (const float*)points, slice_offsets, n_slices, n_points, grid_origin, grid_shape, cell_base,
-                       bitmap, n_cells, cell, intensity_floor, cursor, cell_offsets, (AlignRecord*)records, capacity);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  return align_score(false, records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets, n_lines,
+                     slice_line_offsets, shifts, shift_offsets, n_shifts, nullptr, reach, n_slices, items, n_items, r2, acc,
+                     device, stream);
 }
 int prh_align_score_rigid(const void* records, const long long* cand_offsets, long long n_candidates,
                           const double* line_vertices, long long n_vertices, const long long* line_offsets, int n_lines,
@@ -3948,23 +3919,9 @@ int prh_align_score_rigid(const void* records, const long long* cand_offsets, lo
                           long long n_poses, const double* pivots, const double* reach, int n_slices,
                           const long long* items, long long n_items, double r2, long long* acc, int device,
                           void* stream) {
-  if (n_candidates < 0 || n_vertices < 0 || n_lines < 0 || n_poses < 0 || n_slices < 0 || n_items < 0 ||
-      n_items > 0x7fffffffll)
-    return fail(PRH_ERR_ARG, "align_score_rigid: bad argument (at most 2^31 - 1 work items)");
-  if (!(r2 > 0.0) || !(r2 <= 1.0)) return fail(PRH_ERR_ARG, "align_score_rigid: 0 < radius <= 1");
-  if (n_items == 0) return PRH_OK;
-  if (!records || !cand_offsets || !line_vertices || !line_offsets || !slice_line_offsets || !poses || !pose_offsets ||
-      !pivots || !reach || !items || !acc || n_slices == 0)
-    return fail(PRH_ERR_ARG, "align_score_rigid: null pointer");
-  if (((uintptr_t)records & 15) != 0 || ((uintptr_t)poses & 15) != 0)
-    return fail(PRH_ERR_ARG, "align_score_rigid: records and poses must be 16-byte aligned");
-  HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(align_score_kernel<true>, dim3((unsigned)n_items), dim3(ALIGN_THREADS), 0, (hipStream_t)stream,
-                     (const AlignRecord*)records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets,
-                     n_lines, slice_line_offsets, poses, pose_offsets, n_poses, reach, n_slices, items, r2,
-                     (unsigned long long*)acc, pivots);
-  LAUNCH_CHECK();
-  return PRH_OK;
+  return align_score(true, records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets, n_lines,
+                     slice_line_offsets, poses, pose_offsets, n_poses, pivots, reach, n_slices, items, n_items, r2, acc,
+                     device, stream);
 }
 
 // ------------------------------------------------------------------ fused cross-attention

@@ -97,39 +97,8 @@ def slice_grids(queries, query_offsets, radius, cell):
     without a query), 'cell_base' (S,) int64, 'n_cells', 'cell', 'reach'}."""
     q = np.asarray(queries, dtype=np.float64).reshape(-1, 2)
     qoff = np.asarray(query_offsets, dtype=np.int64).reshape(-1)
-    n_s = len(qoff) - 1
-    reach, cell = float(radius) + GUARD, float(cell)
-    origin = np.zeros((n_s, 2))
-    shape = np.zeros((n_s, 2), dtype=np.int64)
-    used = np.flatnonzero(np.diff(qoff) > 0)
-    if len(used):
-        start = qoff[:-1][used]
-        lo = np.stack([np.minimum.reduceat(q[:, c], start) for c in (0, 1)], 1) - reach
-        hi = np.stack([np.maximum.reduceat(q[:, c], start) for c in (0, 1)], 1) + reach
-        origin[used] = lo
-        while True:
-            n = np.floor((hi - lo) / cell).astype(np.int64) + 1
-            if int((n[:, 0] * n[:, 1]).sum()) <= MAX_CELLS:
-                break
-            cell *= 2.0
-        shape[used] = n
-    base = np.zeros(n_s, dtype=np.int64)
-    cells = shape[:, 0] * shape[:, 1]
-    if n_s:
-        base[1:] = np.cumsum(cells)[:-1]
-    return {"origin": origin, "shape": shape.astype(np.int32), "cell_base": base, "n_cells": int(cells.sum()),
-            "cell": cell, "reach": reach}
-
-
-def _host(x, dtype):
-    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(dtype, copy=False)
-
-
-def _offsets(x, n, what, name):
-    off = _host(x, np.int64).reshape(-1)
-    if len(off) < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
-        raise ValueError(f"{what}: {name} must rise from 0 to {n}")
-    return off
+    reach = float(radius) + GUARD
+    return dict(G.box_grids(q, qoff, reach, cell, MAX_CELLS), reach=reach)
 
 
 def _params(radius, min_points, peak_share, z_lo, bin, n_bins, what):
@@ -153,22 +122,6 @@ def _params(radius, min_points, peak_share, z_lo, bin, n_bins, what):
 
 
 # ------------------------------------------------------------------ GPU side
-def _points(points, dev, what):
-    """(T,4) float64 or float32 CUDA, aligned to two coordinates: numpy is uploaded once, a CUDA
-    tensor stays where it is."""
-    shape = tuple(points.shape) if torch.is_tensor(points) else np.shape(points)
-    if len(shape) != 2 or shape[1] != 4:
-        raise ValueError(f"{what}: points must be (T,4) x y z intensity, got {shape}")
-    if not torch.is_tensor(points):
-        points = np.asarray(points)
-        if points.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what}: points must be float64 or float32, got {points.dtype}")
-    elif points.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"{what}: points must be float64 or float32, got {points.dtype}")
-    t = G.as_cuda(points, dev, what)
-    return t.clone() if t.numel() and t.data_ptr() % 16 else t
-
-
 def bin_points(pts, off_t, grids, dev):
     """prh_ground_bin_count, the scan, prh_ground_bin_write: (cell_offsets (n_cells+1,) int64 CUDA,
     rows (R,) int32 CUDA, the device copies of the grid arrays)."""
@@ -230,17 +183,17 @@ def ground_heights(points, slice_offsets, queries, query_offsets, radius=RADIUS,
     if not (np.isfinite(cell) and cell >= radius):
         raise ValueError(f"{what}: cell must be finite and >= radius")
     dev = G.device("ground", points.device if torch.is_tensor(points) and points.is_cuda else None)
-    pts = _points(points, dev, what)
-    off = _offsets(slice_offsets, pts.shape[0], what, "slice_offsets")
+    pts = G.points4(points, dev, what)
+    off = G.offsets(slice_offsets, pts.shape[0], what, "slice_offsets")
     if len(off) > 1 and int(np.diff(off).max()) >= 2 ** 31:
         raise ValueError(f"{what}: fewer than 2^31 points per slice")
     shape = tuple(queries.shape) if torch.is_tensor(queries) else np.shape(queries)
     if len(shape) != 2 or shape[1] != 2:
         raise ValueError(f"{what}: queries must be (Q,2) x y, got {shape}")
-    q = np.ascontiguousarray(_host(queries, np.float64).reshape(-1, 2))
+    q = np.ascontiguousarray(G.host(queries, np.float64).reshape(-1, 2))
     if not (np.isfinite(q).all() and (len(q) == 0 or np.abs(q).max() <= MAX_COORD)):
         raise ValueError(f"{what}: queries must be finite and within {MAX_COORD:g} m of the slice's origin")
-    qoff = _offsets(query_offsets, len(q), what, "query_offsets")
+    qoff = G.offsets(query_offsets, len(q), what, "query_offsets")
     if len(qoff) != len(off):
         raise ValueError(f"{what}: slice_offsets and query_offsets must describe the same slices")
     grids = slice_grids(q, qoff, radius, cell)

@@ -522,13 +522,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
             cands_all, lift_report = GR.lift_lines(points, off, cands_all, step=lift_step, radius=lift_radius)
         if align:
             from . import align as AL
-            if float(align_max_yaw) > 0.0:
-                cands_all, align_report = AL.align_lines_rigid(points, off, cands_all, max_shift=align_max_shift,
-                                                               max_yaw=align_max_yaw, radius=align_radius,
-                                                               scope=align_scope)
-            else:
-                cands_all, align_report = AL.align_lines(points, off, cands_all, max_shift=align_max_shift,
-                                                         radius=align_radius, scope=align_scope)
+            cands_all, align_report = AL.align(points, off, cands_all, align_max_yaw, max_shift=align_max_shift,
+                                               radius=align_radius, scope=align_scope)
         if batched:
             pieces, piece_frame, _, sparse = F.refine_slices_batched(
                 model, points, off, cands_all, m, num_context_points, crop_radius, decay_scale, seed, precision,

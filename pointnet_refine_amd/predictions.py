@@ -315,11 +315,8 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
         from .ground import lift_lines
         preds, res["lift"] = lift_lines(points, offsets, preds)
     if align:
-        from .align import align_lines, align_lines_rigid
-        if float(align_max_yaw) > 0.0:
-            preds, res["align"] = align_lines_rigid(points, offsets, preds, max_yaw=align_max_yaw)
-        else:
-            preds, res["align"] = align_lines(points, offsets, preds)
+        from .align import align as align_on_paint
+        preds, res["align"] = align_on_paint(points, offsets, preds, align_max_yaw)
     off = offsets.cpu().numpy()
     pcd_paths = [None] * (len(off) - 1)
     if out_dir is not None:

@@ -81,21 +81,21 @@ def main():
     for name, floor in (("floor0", 0.0), ("paint", PAINT_FLOOR)):
         # (a) the prologue: the same records, the same 441 rows
         p = AL.prepare(s_pts, s_off, s_lines, *tables(shifts, nf), AL.RADIUS, floor, AL.CELL, "bench")
-        q = AL.prepare_rigid(s_pts, s_off, s_lines, *tables(flat, nf), None, AL.RADIUS, floor, AL.CELL, "bench")
+        q = AL.prepare(s_pts, s_off, s_lines, *tables(flat, nf), AL.RADIUS, floor, AL.CELL, "bench", rigid=True)
         assert np.array_equal(p["reach"], q["reach"])
         rec, cand_off, c_off = AL.select_candidates(p)
         shift = stat(events_ms(lambda: AL.score_candidates(p, rec, cand_off, c_off), args.reps))
-        rigid = stat(events_ms(lambda: AL.score_candidates_rigid(q, rec, cand_off, c_off), args.reps))
-        same_a = bool(torch.equal(AL.score_candidates(p, rec, cand_off, c_off), AL.score_candidates_rigid(q, rec, cand_off, c_off)))
+        rigid = stat(events_ms(lambda: AL.score_candidates(q, rec, cand_off, c_off), args.reps))
+        same_a = bool(torch.equal(AL.score_candidates(p, rec, cand_off, c_off), AL.score_candidates(q, rec, cand_off, c_off)))
         # (b) the order of the candidates under the 4,851-row table
-        r = AL.prepare_rigid(s_pts, s_off, s_lines, *tables(coarse, nf), None, AL.RADIUS, floor, AL.CELL, "bench")
+        r = AL.prepare(s_pts, s_off, s_lines, *tables(coarse, nf), AL.RADIUS, floor, AL.CELL, "bench", rigid=True)
         sel_a = stat(events_ms(lambda: AL.select_candidates(r), args.reps))
-        sel_c = stat(events_ms(lambda: AL.select_candidates_cells(r), args.reps))
+        sel_c = stat(events_ms(lambda: AL.select_candidates(r, "cell"), args.reps))
         ra, oa, ha = AL.select_candidates(r)
-        rc, oc, hc = AL.select_candidates_cells(r)
-        sc_a = stat(events_ms(lambda: AL.score_candidates_rigid(r, ra, oa, ha), args.reps))
-        sc_c = stat(events_ms(lambda: AL.score_candidates_rigid(r, rc, oc, hc), args.reps))
-        same_b = bool(torch.equal(AL.score_candidates_rigid(r, ra, oa, ha), AL.score_candidates_rigid(r, rc, oc, hc)))
+        rc, oc, hc = AL.select_candidates(r, "cell")
+        sc_a = stat(events_ms(lambda: AL.score_candidates(r, ra, oa, ha), args.reps))
+        sc_c = stat(events_ms(lambda: AL.score_candidates(r, rc, oc, hc), args.reps))
+        same_b = bool(torch.equal(AL.score_candidates(r, ra, oa, ha), AL.score_candidates(r, rc, oc, hc)))
         res[name] = {"candidates_441": int(rec.shape[0]), "score_shift": shift, "score_rigid_theta0": rigid, "equal_a": same_a,
                      "candidates_4851": int(ra.shape[0]), "cells": r["maps"]["n_cells"], "reach": float(r["reach"][0]),
                      "select_arrival": sel_a, "select_cell": sel_c, "score_arrival": sc_a, "score_cell": sc_c, "equal_b": same_b}

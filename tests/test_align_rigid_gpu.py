@@ -107,8 +107,8 @@ def test_cell_order_sorts_the_records_and_keeps_them():
     """The cell passes leave every slice's records in ascending cell order, and they are the records
     the arrival passes leave."""
     c = RC.case("tiles")
-    p = AL.prepare_rigid(*RC.args(c), AL.RADIUS, 0.0, 1.0, "test")
-    rec_c, off_c, host_c = AL.select_candidates_cells(p)
+    p = AL.prepare(*RC.args(c)[:5], AL.RADIUS, 0.0, 1.0, "test", pivots=c["pivots"], rigid=True)
+    rec_c, off_c, host_c = AL.select_candidates(p, "cell")
     rec_a, off_a, host_a = AL.select_candidates(p)
     assert np.array_equal(host_c, host_a) and torch.equal(off_c, off_a) and np.diff(host_c).tolist() == [0, 1, 63, 64, 65, 257]
     rc, ra, m = rec_c.cpu().numpy(), rec_a.cpu().numpy(), p["maps"]
