@@ -108,8 +108,7 @@ def main():
         show("fused map", fuse.map_error(res["fused"], gt))
     if args.png is not None:
         from pointnet_refine_amd import view3d
-        from pointnet_refine_amd.io import load_pcd_data
-        cloud = np.atleast_2d(load_pcd_data(os.path.join(args.drive_dir, "merged.pcd")))[:, :4]
+        cloud = drive.load_merged_cloud(args.drive_dir)
         parts = [(p, items[l]["category"]) for l, f in enumerate(res["fused"]) for p in f]
         name = os.path.basename(os.path.normpath(args.drive_dir)) + "_map"
         view3d.render_cloud3d(cloud, [p for p, _ in parts], categories=[c for _, c in parts], out_dir=args.png, name=name)

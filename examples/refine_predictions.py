@@ -146,8 +146,7 @@ def main():
               f"({e['vertices']} vertices)")
     if args.png is not None:
         from pointnet_refine_amd import bev
-        from pointnet_refine_amd.io import load_pcd_data
-        cloud = np.atleast_2d(load_pcd_data(os.path.join(args.drive_dir, "merged.pcd")))[:, :4].astype(np.float32)
+        cloud = drive.load_merged_cloud(args.drive_dir).astype(np.float32)
         image, extent = bev.bev_map(cloud, resolution=PNG_RESOLUTION)
         norm, _ = bev.tone_map(image)
         rgba = bev.colorize(norm, image).contiguous()

@@ -45,6 +45,14 @@ def exclusive_scan(counts):
     return out
 
 
+def csr_offsets(counts):
+    """(n+1,) int64 on the host: 0 followed by the running sums of counts, an array or a list of
+    ints; an empty one gives [0]."""
+    out = np.zeros(len(counts) + 1, dtype=np.int64)
+    out[1:] = np.cumsum(np.asarray(counts, dtype=np.int64))
+    return out
+
+
 def as_cuda(x, dev, what, dtype=None):
     """x as a contiguous CUDA tensor of dtype (None: its own): a numpy array (or nested list) is
     converted on the host and uploaded to dev, a CUDA tensor stays on its device, a CPU tensor raises."""
@@ -125,8 +133,7 @@ def lines_csr(lines, dev):
     """A list of (n,3) polylines (None: no vertex) as CSR: (vertices (V,3) float64 CUDA, offsets
     (L+1,) int64 CUDA, the same offsets as numpy)."""
     arrs = [np.zeros((0, 3)) if l is None else np.asarray(l, dtype=np.float64).reshape(-1, 3) for l in lines]
-    off = np.zeros(len(arrs) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([len(a) for a in arrs])
+    off = csr_offsets([len(a) for a in arrs])
     verts = np.concatenate(arrs) if off[-1] > 0 else np.zeros((0, 3))
     return torch.from_numpy(np.ascontiguousarray(verts)).to(dev), torch.from_numpy(off).to(dev), off
 

@@ -87,10 +87,8 @@ def lines_csr(lines_per_slice, what="paint_scores"):
     slice_line_offsets (S+1,) int64).  A vertex must be finite and within MAX_COORD of the origin."""
     flat = [np.asarray(v, dtype=np.float64).reshape(-1, 3) for ls in lines_per_slice for v in ls]
     per_slice = np.array([len(ls) for ls in lines_per_slice], dtype=np.int64)
-    sl_off = np.zeros(len(per_slice) + 1, dtype=np.int64)
-    sl_off[1:] = np.cumsum(per_slice)
-    l_off = np.zeros(len(flat) + 1, dtype=np.int64)
-    l_off[1:] = np.cumsum([len(v) for v in flat])
+    sl_off = G.csr_offsets(per_slice)
+    l_off = G.csr_offsets([len(v) for v in flat])
     verts = np.ascontiguousarray(np.concatenate(flat)) if l_off[-1] > 0 else np.zeros((0, 3))
     if not (np.isfinite(verts).all() and (len(verts) == 0 or np.abs(verts).max() <= MAX_COORD)):
         raise ValueError(f"{what}: line vertices must be finite and within {MAX_COORD:g} m of the slice's origin")
@@ -353,8 +351,7 @@ def _stage(points, off, lines, tables, scope, radius, intensity_floor, pick, wha
     n_s = len(lines)
     if n_s == 0:
         return [], np.zeros(0, dtype=np.int64)
-    k_off = np.zeros(n_s + 1, dtype=np.int64)
-    k_off[1:] = np.cumsum([len(t) for t in tables])
+    k_off = G.csr_offsets([len(t) for t in tables])
     res = _scores(points, off, lines, np.concatenate(tables), k_off, radius, intensity_floor, CELL, what, **scores_kw)
     score, hits = res["score"].cpu().numpy(), res["hits"].cpu().numpy()
     if scope == "drive":

@@ -331,8 +331,7 @@ def crop_views(rgba, extent, windows, resolution=RESOLUTION):
     h = np.maximum(np.floor((win[:, 3] - win[:, 2]) / res + 0.5), 1).astype(np.int64)
     if len(win) and (np.abs(u0).max() >= 2 ** 30 or np.abs(v0).max() >= 2 ** 30 or w.max() >= 2 ** 30 or h.max() >= 2 ** 30):
         raise ValueError("crop_views: a window is too far from the image or too large")
-    off = np.zeros(len(win) + 1, dtype=np.int64)
-    off[1:] = np.cumsum(h * w)
+    off = G.csr_offsets(h * w)
     snapped = np.stack([y_min + u0 * res, y_min + (u0 + w) * res, x_max - (v0 + h) * res, x_max - v0 * res], 1)
     data = torch.empty((int(off[-1]), 4), dtype=torch.uint8, device=dev)
     if len(win):
@@ -417,8 +416,7 @@ def draw_lines(canvas, window, lines, line_view, styles, resolution=None):
     tile = lib.prh_bev_tile()
     ntx, nty = -(-shapes[:, 1] // tile), -(-shapes[:, 0] // tile)
     dims = np.stack([shapes[:, 0], shapes[:, 1], ntx, nty], 1).astype(np.int32)
-    base = np.zeros(len(shapes) + 1, dtype=np.int64)
-    base[1:] = np.cumsum(ntx * nty)
+    base = G.csr_offsets(ntx * nty)
     n_tiles = int(base[-1])
     if n_tiles == 0:
         return canvas

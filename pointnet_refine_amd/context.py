@@ -155,8 +155,7 @@ def ragged_block_offsets(slice_offsets, line_slice):
     if (np.diff(ls) < 0).any():
         raise RuntimeError("build_contexts_ragged: line_slice must never decrease (lines are grouped by slice)")
     blocks = (np.diff(so) + (CROP_BLOCK - 1)) // CROP_BLOCK
-    out = np.zeros(len(ls) + 1, dtype=np.int64)
-    out[1:] = np.cumsum(blocks[ls])
+    out = G.csr_offsets(blocks[ls])
     return out
 
 

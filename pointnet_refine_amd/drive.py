@@ -91,6 +91,12 @@ def plan_slices(poses, segment_len=SEGMENT_LEN, stride=STRIDE, max_pose_gap=MAX_
     return chosen
 
 
+def load_merged_cloud(drive_dir):
+    """drive_dir/merged.pcd as io.load_pcd_data gives it (its dtype), at least 2-D, the columns x y z intensity."""
+    from .io import load_pcd_data
+    return np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
+
+
 def load_gt_items(json_path):
     """The drive's GT polylines (:99-130): list of {'category', 'points' (n,3) float64, 'attributes'}
     from items[].position or items[].semantic_line.position; items without vertices are dropped."""
@@ -260,7 +266,6 @@ def slice_drive(drive_dir, gt_json, out_dir=None, candidates=False, noise_scales
     is empty and writes an empty file when only the crop is).  Returns {'pose_index', 'names',
     'points' (T,4) CUDA, 'offsets', 'source_index', 'items' [per slice list of item dicts],
     'written' [names]}."""
-    from .io import load_pcd_data
     poses = load_poses(os.path.join(drive_dir, "pose"))
     res = {"pose_index": [], "names": [], "points": None, "offsets": None, "source_index": None, "items": [],
            "written": []}
@@ -268,7 +273,7 @@ def slice_drive(drive_dir, gt_json, out_dir=None, candidates=False, noise_scales
         if verbose:
             print("  No poses found. Skipping.")
         return res
-    cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
+    cloud = load_merged_cloud(drive_dir)
     if len(cloud) == 0:
         if verbose:
             print("  No points found. Skipping.")

@@ -10,7 +10,9 @@ polyline per input line (``csrc/prh_fuse.hpp``; the rule is in ``include/pointne
   fuse_pieces        HIP: steps 1-5 (project, then one thread per 0.5 m node gathers the piece
                      segments that pass it) and the host's step 6 (nodes -> polylines)
   map_error          distance of a fused map to its lines and the share of their length it covers
-  refine_drive       plan_slices, slice_cloud, clip_lines, io.scene_offsets per slice, fuse_pieces
+  refine_slices      the slice refinement refine_drive and link.refine_predictions share: io.scene_offsets
+                     per slice or one io.scene_offsets_ragged call, the sparse count, the tube cut
+  refine_drive       plan_slices, slice_cloud, clip_lines, refine_slices, fuse_pieces
   cloud_support      refine_drive(support=True): support.map_support of the input lines and the fused map
   write_map_json     the drive file layout drive.load_gt_items reads
 
@@ -36,10 +38,32 @@ MIN_TUBE_POINTS = 32
 
 
 # ------------------------------------------------------------------ host side
+def floor_km(p):
+    """p with each component rounded down to a multiple of 1000 m: the default origin of every tool
+    that shifts world coordinates before an upload."""
+    return np.floor(np.asarray(p, dtype=np.float64) / 1000.0) * 1000.0
+
+
 def default_origin(poses_xyzq):
     """The first pose's translation with each component rounded down to a multiple of 1000 m."""
     p = np.asarray(poses_xyzq, dtype=np.float64).reshape(-1, 7)
-    return np.floor(p[0, :3] / 1000.0) * 1000.0 if len(p) else np.zeros(3)
+    return floor_km(p[0, :3]) if len(p) else np.zeros(3)
+
+
+def inverse_permutation(order):
+    """back with back[order] = 0 .. n-1: rows taken in order go back to where they were with [back]."""
+    back = np.empty_like(order)
+    back[order] = np.arange(len(order))
+    return back
+
+
+def node_offsets(cums_or_lengths, step):
+    """The node layout of fusion, support and the draft carriers: a line of arc length c has the
+    nodes 0 .. floor(c / step).  cums_or_lengths: a list with every line's carrier_cum (a line
+    without a vertex has no node) or an array of the lines' lengths.  Returns (L+1,) int64 offsets."""
+    if isinstance(cums_or_lengths, np.ndarray):
+        return G.csr_offsets(np.floor(cums_or_lengths / float(step)).astype(np.int64) + 1)
+    return G.csr_offsets([int(np.floor(c[-1] / float(step))) + 1 if len(c) else 0 for c in cums_or_lengths])
 
 
 def carrier_cum(verts):
@@ -150,6 +174,28 @@ def _project(dev, pieces, piece_line, piece_pose, poses, shifted, cums):
     return world, s, d, seg
 
 
+def gather_nodes(dev, world, s, piece_off, node_off, step):
+    """prh_fuse_gather, the one driver of fuse_pieces and of link's draft carriers: world (P,M,3) and s
+    (P,M) float64 CUDA with the pieces grouped by line, piece_off and node_off (L+1,) host offsets of
+    every line's pieces and nodes (node_offsets), one node per step metres.  Returns CUDA (X (N,3),
+    W (N,), C (N,) int32, spread (N,)), all 0 for a node nothing reaches."""
+    n_p, m = world.shape[:2]
+    n_l, n_nodes = len(node_off) - 1, int(node_off[-1])
+    X = torch.zeros((n_nodes, 3), dtype=torch.float64, device=dev)
+    W = torch.zeros((n_nodes,), dtype=torch.float64, device=dev)
+    C = torch.zeros((n_nodes,), dtype=torch.int32, device=dev)
+    spread = torch.zeros((n_nodes,), dtype=torch.float64, device=dev)
+    if n_nodes:
+        lib = L.lib()
+        po_t, no_t = torch.from_numpy(piece_off).to(dev), torch.from_numpy(node_off).to(dev)
+        nb = lib.prh_fuse_gather_workspace_bytes(n_p)
+        ws = G.workspace(nb, dev)
+        L.check(lib.prh_fuse_gather(G.ptr(world), G.ptr(s), n_p, m, G.ptr(po_t), n_l, G.ptr(no_t), n_nodes, float(step),
+                                    G.ptr(X), G.ptr(W), G.ptr(C), G.ptr(spread), G.ptr(ws), nb, dev.index, G.stream(dev)),
+                "prh_fuse_gather")
+    return X, W, C, spread
+
+
 def pieces_to_world(pieces, piece_pose, poses_xyzq, origin=None):
     """Step 1: pieces (P,M,3) in the ego frame of pose piece_pose[p] -> (P,M,3) float64 numpy in the
     drive frame, w = R(q) p + t in fp64 on the GPU (1 <= M <= 64).  The rotation runs on
@@ -179,7 +225,7 @@ def project_to_lines(points, point_line, lines, origin=None):
         raise ValueError(f"project_to_lines: points must be (N,3), got {pts.shape}")
     pl = _check_index(point_line, len(pts), len(lines), "point_line", "project_to_lines")
     first = next((np.asarray(l, dtype=np.float64).reshape(-1, 3)[0] for l in lines if len(l)), np.zeros(3))
-    org = np.floor(first / 1000.0) * 1000.0 if origin is None else np.asarray(origin, dtype=np.float64).reshape(3)
+    org = floor_km(first) if origin is None else np.asarray(origin, dtype=np.float64).reshape(3)
     shifted, cums = _lines(lines, org)
     if any(len(shifted[l]) == 0 for l in np.unique(pl)):
         raise ValueError("project_to_lines: a line that points refer to has no vertex")
@@ -189,8 +235,7 @@ def project_to_lines(points, point_line, lines, origin=None):
     order = np.argsort(pl, kind="stable")
     _, s, d, seg = _project(dev, np.ascontiguousarray((pts - org)[order].reshape(-1, 1, 3)), pl[order], None, None,
                             shifted, cums)
-    back = np.empty_like(order)
-    back[order] = np.arange(len(order))
+    back = inverse_permutation(order)
     return s.cpu().numpy()[back, 0], d.cpu().numpy()[back, 0], seg.cpu().numpy()[back, 0]
 
 
@@ -220,43 +265,26 @@ def fuse_pieces(lines, pieces, piece_line, piece_pose, poses_xyzq, step=STEP, mi
         raise ValueError("fuse_pieces: a line that pieces refer to has no vertex")
     dev = G.device("fuse")
     n_l = len(lines)
-    counts = np.array([int(np.floor(c[-1] / float(step))) + 1 if len(c) else 0 for c in cums], dtype=np.int64)
-    node_off = np.zeros(n_l + 1, dtype=np.int64)
-    node_off[1:] = np.cumsum(counts)
-    n_nodes = int(node_off[-1])
+    node_off = node_offsets(cums, step)
     order = np.argsort(pl, kind="stable")
-    piece_off = np.zeros(n_l + 1, dtype=np.int64)
-    piece_off[1:] = np.cumsum(np.bincount(pl, minlength=n_l)[:n_l]) if n_l else 0
     ps = poses.copy()
     ps[:, :3] -= org
-    X = torch.zeros((n_nodes, 3), dtype=torch.float64, device=dev)
-    W = torch.zeros((n_nodes,), dtype=torch.float64, device=dev)
-    C = torch.zeros((n_nodes,), dtype=torch.int32, device=dev)
-    spread = torch.zeros((n_nodes,), dtype=torch.float64, device=dev)
-    world = s = d = seg = None
     if n_p:
         world, s, d, seg = _project(dev, np.ascontiguousarray(pc[order]), pl[order], pp[order], ps, shifted, cums)
-    if n_nodes:
-        lib = L.lib()
-        po_t, no_t = torch.from_numpy(piece_off).to(dev), torch.from_numpy(node_off).to(dev)
-        nb = lib.prh_fuse_gather_workspace_bytes(n_p)
-        ws = G.workspace(nb, dev)
-        L.check(lib.prh_fuse_gather(G.ptr(world), G.ptr(s), n_p, m, G.ptr(po_t), n_l, G.ptr(no_t), n_nodes, float(step),
-                                    G.ptr(X), G.ptr(W), G.ptr(C), G.ptr(spread), G.ptr(ws), nb, dev.index, G.stream(dev)),
-                "prh_fuse_gather")
+    else:
+        world = torch.zeros((0, m, 3), dtype=torch.float64, device=dev)
+        s, d, seg = world[:, :, 0], world[:, :, 0], world[:, :, 0].to(torch.int32)
+    X, W, C, spread = gather_nodes(dev, world, s, G.csr_offsets(np.bincount(pl, minlength=n_l)[:n_l]), node_off, step)
     Xh, Ch = X.cpu().numpy(), C.cpu().numpy()
     Xh[Ch > 0] += org
     fused = [node_polylines(Xh[node_off[l]:node_off[l + 1]], Ch[node_off[l]:node_off[l + 1]], step, min_count, max_gap)
              for l in range(n_l)]
     if not return_nodes:
         return fused
-    back = np.empty_like(order)
-    back[order] = np.arange(len(order))
+    back = inverse_permutation(order)
     nodes = {"X": Xh, "W": W.cpu().numpy(), "C": Ch, "spread": spread.cpu().numpy(), "offsets": node_off, "origin": org,
-             "world": world.cpu().numpy()[back] + org if n_p else np.zeros((0, m, 3)),
-             "s": s.cpu().numpy()[back] if n_p else np.zeros((0, m)),
-             "d": d.cpu().numpy()[back] if n_p else np.zeros((0, m)),
-             "seg": seg.cpu().numpy()[back] if n_p else np.zeros((0, m), dtype=np.int32)}
+             "world": world.cpu().numpy()[back] + org, "s": s.cpu().numpy()[back], "d": d.cpu().numpy()[back],
+             "seg": seg.cpu().numpy()[back]}
     return fused, nodes
 
 
@@ -299,33 +327,50 @@ def map_error(fused, gt_lines):
             "vertices": int(len(pts)), "covered_length": covered, "line_length": total}
 
 
-def refine_slices_batched(model, points, off, cands, num_line_points, num_context_points, crop_radius, decay_scale,
-                          seed, precision, min_tube_points):
-    """The per-slice loop of refine_drive / link.refine_predictions as one io.scene_offsets_ragged
-    call.  points (T,4) CUDA and off (S+1,) host offsets from drive.slice_cloud; cands: per slice the
-    list of candidate polylines in that slice's frame.  Slice si draws with seed * 1000003 + si, the
-    lines of a slice without points are counted as sparse and never reach the model, a piece whose
-    tube held fewer than min_tube_points points is left out and counted - all as in the loop.
-    Returns (pieces (P,M,3) float64, piece_slice (P,), piece_row (P,) the row in cands[slice],
-    sparse), pieces in slice order, then candidate order."""
-    from .io import scene_offsets_ragged
+def refine_slices(model, points, off, cands, num_line_points, num_context_points, crop_radius, decay_scale, seed,
+                  precision, min_tube_points, batched=False):
+    """The slice refinement of refine_drive and link.refine_predictions.  points (T,4) CUDA and off
+    (S+1,) host offsets from drive.slice_cloud; cands: per slice the list of candidate polylines in
+    that slice's frame.  One io.scene_offsets call per slice that has candidates and points, or,
+    batched, one io.scene_offsets_ragged call over those slices: the same contexts byte for byte,
+    other rows sharing a forward call.  Slice si draws with seed * 1000003 + si; the lines of a slice
+    without points are counted as sparse and never reach the model; a piece whose tube held fewer
+    than min_tube_points points is left out and counted.  Returns (pieces (P,M,3) float64 = noisy_c +
+    centres + offset, piece_slice (P,), piece_row (P,) the row in cands[slice], both int64, sparse),
+    pieces in slice order, then candidate order."""
+    from .io import scene_offsets, scene_offsets_ragged
     off = np.asarray(off, dtype=np.int64)
+    m = int(num_line_points)
     n_cand = np.array([len(c) for c in cands], dtype=np.int64)
     has_points = np.diff(off) > 0
     sparse = int(n_cand[~has_points].sum())
     used = np.flatnonzero(has_points & (n_cand > 0))
     if len(used) == 0:
-        return np.zeros((0, int(num_line_points), 3)), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), sparse
+        return np.zeros((0, m, 3)), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), sparse
     line_slice = np.repeat(used, n_cand[used])
     line_row = np.concatenate([np.arange(n_cand[si]) for si in used])
-    raw = [v for si in used for v in cands[si]]
     seeds = [int(seed) * 1000003 + si for si in range(len(off) - 1)]
-    offset, noisy_c, centres, counts = scene_offsets_ragged(
-        model, points.to(torch.float32), off, raw, line_slice, seeds, int(num_line_points), num_context_points,
-        crop_radius, decay_scale, precision=precision, return_counts=True)
-    refined = (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy()
-    keep = counts.cpu().numpy() >= int(min_tube_points)
+    kw = dict(precision=precision, return_counts=True)
+
+    def to_host(offset, noisy_c, centres, counts):
+        return (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy(), counts.cpu().numpy()
+
+    if batched:
+        parts = [to_host(*scene_offsets_ragged(model, points.to(torch.float32), off, [v for si in used for v in cands[si]],
+                                               line_slice, seeds, m, num_context_points, crop_radius, decay_scale, **kw))]
+    else:
+        parts = [to_host(*scene_offsets(model, points[off[si]:off[si + 1]].to(torch.float32), cands[si], m,
+                                        num_context_points, crop_radius, decay_scale, seed=seeds[si], **kw)) for si in used]
+    refined = np.concatenate([r for r, _ in parts])
+    keep = np.concatenate([c for _, c in parts]) >= int(min_tube_points)
     return refined[keep], line_slice[keep], line_row[keep], sparse + int((~keep).sum())
+
+
+def refine_report(n_slices, pieces, sparse, nodes, fused, min_count):
+    """What the 'report' of refine_drive and of link.refine_predictions have in common."""
+    return {"slices": int(n_slices), "pieces": int(len(pieces)), "pieces_sparse": int(sparse),
+            "nodes": int(len(nodes["C"])), "nodes_used": int((nodes["C"] >= min_count).sum()),
+            "fused_polylines": int(sum(len(f) for f in fused))}
 
 
 @torch.no_grad()
@@ -341,16 +386,15 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     polylines in the drive frame (GT with noise, detector output matched to a carrier, ...).
 
     A chain of the project's calls: drive.plan_slices picks the slice poses; drive.slice_cloud cuts
-    every slice's points; drive.clip_lines cuts the lines per slice; per slice, io.scene_offsets
-    runs the model on that slice's points taken straight from slice_cloud on the device - the
+    every slice's points; drive.clip_lines cuts the lines per slice; refine_slices runs the model,
+    one io.scene_offsets call per slice, on the points taken straight from slice_cloud on the device - the
     points are rounded to float32 once, there is no PCD text round trip, so they are not rounded to
     the file format's 4 decimals the way a drive written by slice_drive and read back is; the
     refined pieces noisy_c + centres + offset are collected with their line and slice; fuse_pieces
     merges them with the input lines as carriers.  A piece whose tube held fewer than
     min_tube_points cloud points is left out and counted (the model saw padding, not a lane).
-    batched=True replaces the per-slice loop by one io.scene_offsets_ragged call over all slices
-    (refine_slices_batched): the same contexts byte for byte, the same pieces in the same order up
-    to which rows share a forward call.
+    batched=True makes that one io.scene_offsets_ragged call over all slices: the same contexts
+    byte for byte, the same pieces in the same order up to which rows share a forward call.
     support=True scores the input lines and the fused map against the cloud (support.map_support
     with tube radius support_radius, default crop_radius, and intensity_floor): the lateral offset
     of the paint before and after refinement, with no GT.
@@ -361,7 +405,6 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     and, with support=True, 'support': {'input', 'fused' (map_support's dicts), 'attributes'
     (support.marking_attributes of the fused map, per line)}."""
     from . import drive as D
-    from .io import load_pcd_data, scene_offsets
     G.device("fuse")
     if not 2 <= int(num_line_points) <= MAX_POINTS:
         raise ValueError(f"refine_drive: 2..{MAX_POINTS} points per line, got {num_line_points}")
@@ -370,7 +413,7 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     if isinstance(drive_dir_or_cloud, (str, os.PathLike)):
         if poses is None:
             poses = D.load_poses(os.path.join(drive_dir_or_cloud, "pose"))
-        cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir_or_cloud, "merged.pcd")))[:, :4].astype(np.float32, copy=False)
+        cloud = D.load_merged_cloud(drive_dir_or_cloud).astype(np.float32, copy=False)
     else:
         cloud = drive_dir_or_cloud
     if poses is None:
@@ -381,47 +424,20 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     else:
         pq = np.asarray(poses, dtype=np.float64).reshape(-1, 7)[chosen].reshape(-1, 7)
     lines = [np.asarray(l, dtype=np.float64).reshape(-1, 3) for l in lines]
-    m = int(num_line_points)
-    pieces, piece_line, piece_slice, sparse = [], [], [], 0
+    points, off, clipped = None, np.zeros(1, dtype=np.int64), []        # without a slice or a line: nothing to refine
     if len(chosen) and len(lines):
         points, offsets, _ = D.slice_cloud(cloud, pq, segment_len, D.RADIUS if radius is None else radius)
         clipped = D.clip_lines(lines, pq, segment_len)
         off = offsets.cpu().numpy()
-        if batched:
-            pieces, piece_slice, row, sparse = refine_slices_batched(
-                model, points, off, [[v for _, v in kept] for kept in clipped], m, num_context_points, crop_radius,
-                decay_scale, seed, precision, min_tube_points)
-            first = np.cumsum([0] + [len(kept) for kept in clipped])
-            piece_line = np.array([l for kept in clipped for l, _ in kept], dtype=np.int64)[first[piece_slice] + row]
-        else:
-            for si, kept in enumerate(clipped):
-                if not kept:
-                    continue
-                if off[si + 1] == off[si]:
-                    sparse += len(kept)                    # no cloud at all in this slice
-                    continue
-                pts = points[off[si]:off[si + 1]].to(torch.float32)
-                offset, noisy_c, centres, counts = scene_offsets(model, pts, [v for _, v in kept], m, num_context_points,
-                                                                 crop_radius, decay_scale, seed=int(seed) * 1000003 + si,
-                                                                 precision=precision, return_counts=True)
-                refined = (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy()
-                keep = counts.cpu().numpy() >= int(min_tube_points)
-                sparse += int((~keep).sum())
-                for r, (l, _) in enumerate(kept):
-                    if keep[r]:
-                        pieces.append(refined[r])
-                        piece_line.append(l)
-                        piece_slice.append(si)
-    pieces = np.stack(pieces) if len(pieces) else np.zeros((0, m, 3))
-    piece_line = np.asarray(piece_line, dtype=np.int64)
-    piece_slice = np.asarray(piece_slice, dtype=np.int64)
+    pieces, piece_slice, row, sparse = refine_slices(
+        model, points, off, [[v for _, v in kept] for kept in clipped], num_line_points,
+        num_context_points, crop_radius, decay_scale, seed, precision, min_tube_points, batched)
+    first = G.csr_offsets([len(kept) for kept in clipped])
+    piece_line = np.array([l for kept in clipped for l, _ in kept], dtype=np.int64)[first[piece_slice] + row]
     fused, nodes = fuse_pieces(lines, pieces, piece_line, piece_slice, pq, step, min_count, max_gap, origin,
                                return_nodes=True)
-    report = {"slices": len(chosen), "pieces": int(len(pieces)), "pieces_sparse": int(sparse),
-              "nodes": int(len(nodes["C"])), "nodes_used": int((nodes["C"] >= min_count).sum()),
-              "fused_polylines": int(sum(len(f) for f in fused))}
-    res = {"fused": fused, "pieces": pieces, "piece_line": piece_line, "piece_slice": piece_slice,
-           "pose_index": chosen, "poses": pq, "nodes": nodes, "report": report}
+    res = {"fused": fused, "pieces": pieces, "piece_line": piece_line, "piece_slice": piece_slice, "pose_index": chosen,
+           "poses": pq, "nodes": nodes, "report": refine_report(len(chosen), pieces, sparse, nodes, fused, min_count)}
     if support:
         res["support"] = cloud_support(cloud, fused, lines, step, crop_radius if support_radius is None else support_radius,
                                        intensity_floor, nodes["origin"])

@@ -71,8 +71,7 @@ def line_stations(lines, step=STEP):
         xy.append(pxy)
         arc.append(s)
         counts.append(len(s))
-    off = np.zeros(len(counts) + 1, dtype=np.int64)
-    off[1:] = np.cumsum(counts)
+    off = G.csr_offsets(counts)
     if off[-1] == 0:
         return np.zeros((0, 2)), np.zeros(0), off
     return np.concatenate(xy), np.concatenate(arc), off
@@ -235,8 +234,7 @@ def lift_lines(points, slice_offsets, lines_per_slice, step=STEP, **ground_kw):
     flat = [np.asarray(v, dtype=np.float64).reshape(-1, 3) for ls in lines_per_slice for v in ls]
     xy, arc, s_off = line_stations(flat, step)
     per_slice = np.array([len(ls) for ls in lines_per_slice], dtype=np.int64)
-    l_off = np.zeros(len(per_slice) + 1, dtype=np.int64)
-    l_off[1:] = np.cumsum(per_slice)
+    l_off = G.csr_offsets(per_slice)
     res = ground_heights(points, slice_offsets, xy, s_off[l_off], **ground_kw)
     height = res["height"].cpu().numpy()
     out, lifted = lift_vertices(flat, arc, s_off, height)

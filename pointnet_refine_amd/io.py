@@ -18,6 +18,7 @@ import json
 import numpy as np
 import torch
 
+from . import _gpu as G
 from .context import build_contexts, build_contexts_ragged
 
 _XYZI_F32 = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4")])
@@ -312,8 +313,7 @@ class SceneSampleStream:
             gts.append(gt)
             seeds.append(seed)
             line_slice.extend([s] * len(pairs))
-        slice_offsets = np.zeros(len(clouds) + 1, dtype=np.int64)
-        slice_offsets[1:] = np.cumsum([c.shape[0] for c in clouds])
+        slice_offsets = G.csr_offsets([c.shape[0] for c in clouds])
         points = torch.cat(clouds)
         del clouds
         return self._samples(*build_contexts_ragged(points, slice_offsets, raw, line_slice, seeds, self.num_line_points,

@@ -13,8 +13,7 @@ per cluster from the pieces themselves and hands them to the standard fusion.
                       refine_predictions(device_sync=True) go through it (default off)
   fuse_unmatched      steps 1-8 from ego-frame pieces: pieces_to_world, link_pieces, sync_pieces,
                       prh_fuse_gather for the draft carriers, fuse_pieces for the map
-  refine_predictions  a detector run to a map: load_results, slice_cloud, io.scene_offsets per frame,
-                      fuse_unmatched
+  refine_predictions  a detector run to a map: load_results, slice_cloud, fuse.refine_slices, fuse_unmatched
 
     res = refine_predictions(model, "DRIVE_annotation_raw_data", "results.json")
     fuse.write_map_json("map.json", res["fused"])
@@ -112,8 +111,7 @@ def sync_pieces(n_pieces, links):
     src_is_i = np.concatenate([np.ones(len(ei), dtype=bool), np.zeros(len(ei), dtype=bool)])
     order = np.argsort(src, kind="stable")
     src, dst, num, src_is_i = src[order], dst[order], num[order], src_is_i[order]
-    ptr = np.zeros(n + 1, dtype=np.int64)
-    ptr[1:] = np.cumsum(np.bincount(src, minlength=n)[:n]) if n else 0
+    ptr = G.csr_offsets(np.bincount(src, minlength=n)[:n])
     level = np.full(n, -1, dtype=np.int64)
     parent = np.full(n, -1, dtype=np.int64)
     sign = np.ones(n, dtype=np.int8)
@@ -316,7 +314,7 @@ def _link_sync(dev, world_t, frame, gate, min_in, out_ratio, return_links):
 
 def _origin_of(w, origin):
     if origin is None:
-        return np.floor(w[0, 0] / 1000.0) * 1000.0 if len(w) else np.zeros(3)
+        return F.floor_km(w[0, 0]) if len(w) else np.zeros(3)
     return np.asarray(origin, dtype=np.float64).reshape(3)
 
 
@@ -351,27 +349,11 @@ def link_pieces(world, piece_frame, gate=GATE, min_in=MIN_IN, out_ratio=OUT_RATI
 def _draft_carriers(dev, world, g, line, n_lines, step):
     """Step 7: prh_fuse_gather with s := g over pieces grouped by line (already in line order).
     world (K,M,3), g (K,M) numpy.  Returns per line the (k,3) nodes with C >= 1, shifted frame."""
-    lib = L.lib()
-    n_k, m = g.shape
     top = np.zeros(n_lines)
     np.maximum.at(top, line, g.max(axis=1))
-    counts = np.floor(top / float(step)).astype(np.int64) + 1
-    node_off = np.zeros(n_lines + 1, dtype=np.int64)
-    node_off[1:] = np.cumsum(counts)
-    piece_off = np.zeros(n_lines + 1, dtype=np.int64)
-    piece_off[1:] = np.cumsum(np.bincount(line, minlength=n_lines)[:n_lines])
-    n_nodes = int(node_off[-1])
-    X = torch.zeros((n_nodes, 3), dtype=torch.float64, device=dev)
-    W = torch.zeros((n_nodes,), dtype=torch.float64, device=dev)
-    C = torch.zeros((n_nodes,), dtype=torch.int32, device=dev)
-    spread = torch.zeros((n_nodes,), dtype=torch.float64, device=dev)
+    node_off = F.node_offsets(top, step)
     w_t, g_t = torch.from_numpy(np.ascontiguousarray(world)).to(dev), torch.from_numpy(np.ascontiguousarray(g)).to(dev)
-    po_t, no_t = torch.from_numpy(piece_off).to(dev), torch.from_numpy(node_off).to(dev)
-    nb = lib.prh_fuse_gather_workspace_bytes(n_k)
-    ws = G.workspace(nb, dev)
-    L.check(lib.prh_fuse_gather(G.ptr(w_t), G.ptr(g_t), n_k, m, G.ptr(po_t), n_lines, G.ptr(no_t), n_nodes, float(step),
-                                G.ptr(X), G.ptr(W), G.ptr(C), G.ptr(spread), G.ptr(ws), nb, dev.index, G.stream(dev)),
-            "prh_fuse_gather")
+    X, _, C, _ = F.gather_nodes(dev, w_t, g_t, G.csr_offsets(np.bincount(line, minlength=n_lines)[:n_lines]), node_off, step)
     Xh, Ch = X.cpu().numpy(), C.cpu().numpy()
     return [Xh[node_off[l]:node_off[l + 1]][Ch[node_off[l]:node_off[l + 1]] >= 1] for l in range(n_lines)]
 
@@ -467,11 +449,11 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     drive_dir holds pose/*.json and merged.pcd; results_json is the detector's output
     (predictions.load_results).  A chain of the project's calls: load_frame_poses, load_results and
     match_poses pick a pose per camera frame; one drive.slice_cloud cuts the cloud of every frame
-    that has a pose; per frame, io.scene_offsets runs the model on that frame's device-resident slice
-    with the pixel_to_ego lines as candidates, exactly what refine_drive does per slice; a piece
+    that has a pose; fuse.refine_slices runs the model on every frame's device-resident slice with the
+    pixel_to_ego lines as candidates, exactly what refine_drive does per slice (one io.scene_offsets
+    call per frame, or with batched=True one io.scene_offsets_ragged call over all frames); a piece
     whose tube held fewer than min_tube_points cloud points is left out and counted; fuse_unmatched
-    links and fuses the rest.  batched=True replaces the per-frame loop by one
-    io.scene_offsets_ragged call over all frames (fuse.refine_slices_batched), as in refine_drive.
+    links and fuses the rest.
     device_sync and return_links go to fuse_unmatched: the same map and report, steps 5-6 on the device.
     lift=True puts the pixel_to_ego lines (z = 0) on the road first: one ground.lift_lines call over
     all frames' slices (stations every lift_step metres, cloud points within lift_radius in xy), and
@@ -494,7 +476,6 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     'clusters', 'clusters_kept', 'pieces_unlinked'}}."""
     from . import drive as D
     from . import predictions as PR
-    from .io import load_pcd_data, scene_offsets
     G.device("link")
     m = int(num_line_points)
     if not 2 <= m <= F.MAX_POINTS:
@@ -506,15 +487,14 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
                             PR.MAX_POSE_GAP_NS if max_pose_gap is None else max_pose_gap)
     with_pose = np.flatnonzero(chosen >= 0)
     pq = D.poses_xyzq(poses, chosen[with_pose]) if len(with_pose) else np.zeros((0, 7))
-    pieces, piece_frame, sparse = [], [], 0
+    pieces, piece_frame, sparse = np.zeros((0, m, 3)), np.zeros(0, dtype=np.int64), 0
     cloud = None
     lift_report = {"lines": 0, "lines_lifted": 0, "lines_unlifted": 0, "stations": 0, "stations_without_ground": 0}
     align_report = {"frames": 0, "frames_aligned": 0, "frames_unaligned": 0, "shifts": np.zeros((0, 2)),
                     "score_zero": np.zeros(0, dtype=np.int64), "score_best": np.zeros(0, dtype=np.int64), "candidates": 0}
     if len(with_pose):
-        cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
-        points, offsets, _ = D.slice_cloud(np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4), pq, segment_len,
-                                           PR.RADIUS if radius is None else radius)
+        cloud = np.ascontiguousarray(D.load_merged_cloud(drive_dir), dtype=np.float32).reshape(-1, 4)
+        points, offsets, _ = D.slice_cloud(cloud, pq, segment_len, PR.RADIUS if radius is None else radius)
         off = offsets.cpu().numpy()
         cands_all = [[PR.pixel_to_ego(px) for px in frames[n]["pixels"]] for n in with_pose]
         if lift:
@@ -524,39 +504,15 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
             from . import align as AL
             cands_all, align_report = AL.align(points, off, cands_all, align_max_yaw, max_shift=align_max_shift,
                                                radius=align_radius, scope=align_scope)
-        if batched:
-            pieces, piece_frame, _, sparse = F.refine_slices_batched(
-                model, points, off, cands_all, m, num_context_points, crop_radius, decay_scale, seed, precision,
-                min_tube_points)
-        else:
-            for si in range(len(with_pose)):
-                cands = cands_all[si]
-                if not cands:
-                    continue
-                if off[si + 1] == off[si]:
-                    sparse += len(cands)                   # no cloud at all in this frame's slice
-                    continue
-                pts = points[off[si]:off[si + 1]].to(torch.float32)
-                offset, noisy_c, centres, counts = scene_offsets(model, pts, cands, m, num_context_points, crop_radius,
-                                                                 decay_scale, seed=int(seed) * 1000003 + si,
-                                                                 precision=precision, return_counts=True)
-                refined = (noisy_c + centres[:, None, :] + offset).to(torch.float64).cpu().numpy()
-                keep = counts.cpu().numpy() >= int(min_tube_points)
-                sparse += int((~keep).sum())
-                for r in np.flatnonzero(keep):
-                    pieces.append(refined[r])
-                    piece_frame.append(si)
-    pieces = np.stack(pieces) if len(pieces) else np.zeros((0, m, 3))
-    piece_frame = np.asarray(piece_frame, dtype=np.int64)
+        pieces, piece_frame, _, sparse = F.refine_slices(model, points, off, cands_all, m, num_context_points, crop_radius,
+                                                         decay_scale, seed, precision, min_tube_points, batched)
     fused, nodes = fuse_unmatched(pieces, piece_frame, pq, gate, min_in, out_ratio, min_pieces, step, min_count, max_gap,
                                   origin, return_nodes=True, device_sync=device_sync, return_links=return_links)
     all_clusters = nodes["clusters_all"]
-    report = {"slices": int(len(with_pose)), "pieces": int(len(pieces)), "pieces_sparse": int(sparse),
-              "nodes": int(len(nodes["C"])), "nodes_used": int((nodes["C"] >= min_count).sum()),
-              "fused_polylines": int(sum(len(f) for f in fused)), "candidates": int(nodes["n_candidates"]),
-              "edges": int(nodes["n_edges"]),
-              "clusters": int(all_clusters.max()) + 1 if len(all_clusters) else 0, "clusters_kept": len(fused),
-              "pieces_unlinked": int((nodes["cluster"] < 0).sum())}
+    report = F.refine_report(len(with_pose), pieces, sparse, nodes, fused, min_count)
+    report.update({"candidates": int(nodes["n_candidates"]), "edges": int(nodes["n_edges"]),
+                   "clusters": int(all_clusters.max()) + 1 if len(all_clusters) else 0, "clusters_kept": len(fused),
+                   "pieces_unlinked": int((nodes["cluster"] < 0).sum())})
     if lift:
         report.update({"lift_" + k: v for k, v in lift_report.items()})
     if align:
@@ -567,8 +523,7 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
            "pose_index": [int(c) for c in chosen[with_pose]], "poses": pq, "nodes": nodes, "report": report}
     if support:
         if cloud is None:
-            cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
-        res["support"] = F.cloud_support(np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4), fused, None, step,
-                                         crop_radius if support_radius is None else support_radius, intensity_floor,
-                                         nodes["origin"])
+            cloud = np.ascontiguousarray(D.load_merged_cloud(drive_dir), dtype=np.float32).reshape(-1, 4)
+        res["support"] = F.cloud_support(cloud, fused, None, step, crop_radius if support_radius is None else support_radius,
+                                         intensity_floor, nodes["origin"])
     return res

@@ -58,8 +58,7 @@ def line_metrics(noisy, refined, gt_lines, gt_index=None):
     gt_index = np.asarray(gt_index, dtype=np.int64).reshape(-1)
     if len(gt_index) != n_lines or (n_lines and (gt_index.min() < -1 or gt_index.max() >= len(gts))):
         raise ValueError("line_metrics: gt_index must hold one index in [-1, len(gt_lines)) per line")
-    offsets = np.zeros(len(gts) + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum([len(g) for g in gts])
+    offsets = G.csr_offsets([len(g) for g in gts])
     verts = np.concatenate(gts) if offsets[-1] > 0 else np.zeros((1, 3))      # never an empty buffer
     gt_t = torch.from_numpy(np.ascontiguousarray(verts)).to(dev)
     off_t = torch.from_numpy(offsets).to(dev)
@@ -152,8 +151,7 @@ def sweep_work_items(pred_counts, shift_counts):
     if len(pc) != len(sc) or (pc <= 0).any() or (sc <= 0).any():
         raise ValueError("sweep_work_items: one positive point count and one positive shift count per problem")
     n_qt = (pc + (SWEEP_QUERIES - 1)) // SWEEP_QUERIES
-    out = np.zeros(len(pc) + 1, dtype=np.int64)
-    out[1:] = np.cumsum(n_qt * ((sc + (SWEEP_SHIFTS - 1)) // SWEEP_SHIFTS))
+    out = G.csr_offsets(n_qt * ((sc + (SWEEP_SHIFTS - 1)) // SWEEP_SHIFTS))
     return out, n_qt
 
 
@@ -168,8 +166,7 @@ def sweep_item(item_offsets, n_qt, item):
 def _points_csr(sets, width):
     """A list of (n,width) numpy arrays as one (N,width) float64 array and its (len+1,) int64 offsets."""
     arrs = [np.asarray(a, dtype=np.float64).reshape(-1, width) for a in sets]
-    off = np.zeros(len(arrs) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([len(a) for a in arrs])
+    off = G.csr_offsets([len(a) for a in arrs])
     return (np.concatenate(arrs) if len(arrs) and off[-1] > 0 else np.zeros((0, width))), off
 
 
@@ -207,8 +204,7 @@ def _sweep_ragged(pred_t, pred_off, gt_t, gt_off, gt_index, shifts_t, shift_off,
 def _device_csr(sets, width, dev, what):
     """Sets given as CUDA tensors (numpy sets are uploaded one by one): (flat (N,width) CUDA float64, offsets)."""
     ts = [G.as_cuda(a, dev, what, torch.float64).reshape(-1, width) for a in sets]
-    off = np.zeros(len(ts) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([t.shape[0] for t in ts])
+    off = G.csr_offsets([t.shape[0] for t in ts])
     return (torch.cat(ts) if ts else torch.zeros((0, width), dtype=torch.float64, device=dev)), off
 
 
@@ -436,8 +432,7 @@ def evaluate_scenes(model, scenes, num_line_points=32, num_context_points=1024, 
     m = int(num_line_points)
     per_scene = [scene_rows(items) for _, items in scenes]                   # rows, raw, gts, cal_gt
     with_rows = [s for s, r in enumerate(per_scene) if r[0]]
-    row_off = np.zeros(len(scenes) + 1, dtype=np.int64)
-    row_off[1:] = np.cumsum([len(r[0]) for r in per_scene])
+    row_off = G.csr_offsets([len(r[0]) for r in per_scene])
     n_rows = int(row_off[-1])
     raw_all = [line for r in per_scene for line in r[1]]
     noisy = refined = None
@@ -446,8 +441,7 @@ def evaluate_scenes(model, scenes, num_line_points=32, num_context_points=1024, 
         offsets = []
         for g0, g1 in scene_groups([_cloud_rows(scenes[s][0]) for s in with_rows], max_points):
             group = with_rows[g0:g1]
-            so = np.zeros(len(group) + 1, dtype=np.int64)
-            so[1:] = np.cumsum([_cloud_rows(scenes[s][0]) for s in group])
+            so = G.csr_offsets([_cloud_rows(scenes[s][0]) for s in group])
             points = torch.empty((int(so[-1]), 4), dtype=torch.float32, device=mdev)
             for k, s in enumerate(group):                # one cloud at a time: never two copies of all of them
                 cloud = scenes[s][0]

@@ -151,8 +151,7 @@ def clip_lines_frames(lines, poses_xyzq, segment_len=SEGMENT_LEN, return_counts=
 def _xy_csr(lines, dev):
     arrs = [np.asarray(l, dtype=np.float64) for l in lines]
     arrs = [a.reshape(-1, a.shape[-1] if a.ndim == 2 and a.shape[-1] in (2, 3) else 3)[:, :2] for a in arrs]
-    off = np.zeros(len(arrs) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([len(a) for a in arrs])
+    off = G.csr_offsets([len(a) for a in arrs])
     xy = np.concatenate(arrs) if off[-1] > 0 else np.zeros((0, 2))
     return torch.from_numpy(np.ascontiguousarray(xy, dtype=np.float64)).to(dev), torch.from_numpy(off).to(dev)
 
@@ -184,8 +183,7 @@ def _pack_lines(pred_lines, pred_offsets, gt_lines, gt_offsets):
         raise ValueError("line_costs: prediction and GT offsets must describe the same frames")
     n_f = len(p_off) - 1
     shapes = np.stack([np.diff(p_off), np.diff(g_off)], 1).astype(np.int64).reshape(n_f, 2)
-    c_off = np.zeros(n_f + 1, dtype=np.int64)
-    c_off[1:] = np.cumsum(shapes[:, 0] * shapes[:, 1])
+    c_off = G.csr_offsets(shapes[:, 0] * shapes[:, 1])
     pxy, pl_off = _xy_csr(pred_lines, dev)
     gxy, gl_off = _xy_csr(gt_lines, dev)
     pf, gf, cf = (torch.from_numpy(a).to(dev) for a in (p_off, g_off, c_off))
@@ -228,10 +226,8 @@ def assign(costs, cost_offsets, shapes, threshold=None, return_duals=False):
     ct = G.as_cuda(costs, dev, "assign", torch.float64).reshape(-1)
     if ct.numel() != (int(c_off[-1]) if n_f else 0):
         raise ValueError(f"assign: {ct.numel()} costs for offsets that end at {int(c_off[-1]) if n_f else 0}")
-    r_off = np.zeros(n_f + 1, dtype=np.int64)
-    r_off[1:] = np.cumsum(shapes[:, 0])
-    g_off = np.zeros(n_f + 1, dtype=np.int64)
-    g_off[1:] = np.cumsum(shapes[:, 1])
+    r_off = G.csr_offsets(shapes[:, 0])
+    g_off = G.csr_offsets(shapes[:, 1])
     match = torch.full((int(r_off[-1]),), -1, dtype=torch.int32, device=dev)
     total = torch.zeros((n_f,), dtype=torch.float64, device=dev)
     status = torch.zeros((n_f,), dtype=torch.int32, device=dev)
@@ -259,8 +255,8 @@ def match_predictions(pred_lines_per_frame, gt_lines_per_frame, threshold=MATCH_
     if len(pred_lines_per_frame) != len(gt_lines_per_frame):
         raise ValueError("match_predictions: one list of predictions and one of GT lines per frame")
     G.device("predictions")
-    p_off = np.concatenate([[0], np.cumsum([len(p) for p in pred_lines_per_frame])]).astype(np.int64)
-    g_off = np.concatenate([[0], np.cumsum([len(g) for g in gt_lines_per_frame])]).astype(np.int64)
+    p_off = G.csr_offsets([len(p) for p in pred_lines_per_frame])
+    g_off = G.csr_offsets([len(g) for g in gt_lines_per_frame])
     costs, c_off, shapes = line_costs([l for p in pred_lines_per_frame for l in p], p_off,
                                       [l for g in gt_lines_per_frame for l in g], g_off)
     match, _ = assign(costs, c_off, shapes, threshold=threshold)
@@ -291,7 +287,6 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
     and 'offsets' over the frames with a pose (row 'slice' of each frame, -1: none), 'slice',
     'items' [per frame list of item dicts, [] for a skipped frame], 'matches', 'costs', 'gt_index'
     [per frame the GT item of each context line], 'written' [result ts]}."""
-    from .io import load_pcd_data
     G.device("predictions")
     poses = load_frame_poses(os.path.join(drive_dir, "pose"))
     res = {"frames": [], "pose_index": [], "pose_ts": [], "points": None, "offsets": None, "slice": [], "items": [],
@@ -300,7 +295,7 @@ def predictions_to_scenes(drive_dir, gt_json, results_json, out_dir=None, segmen
         if verbose:
             print("No poses found.")
         return res
-    cloud = np.atleast_2d(load_pcd_data(os.path.join(drive_dir, "merged.pcd")))[:, :4]
+    cloud = D.load_merged_cloud(drive_dir)
     gt_items = D.load_gt_items(gt_json)
     frames = load_results(results_json)
     chosen = match_poses([fr["ts"] for fr in frames], [p["ts"] for p in poses], max_pose_gap)

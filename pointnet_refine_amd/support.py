@@ -86,8 +86,7 @@ def segment_grid(lines_shifted, radius, cell=CELL):
     local = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(count) - count, count)
     cell_id = (iy0[seg] + local // w[seg]) * nx + ix0[seg] + local % w[seg]
     order = np.argsort(cell_id, kind="stable")           # segments come line by line, segment by segment
-    offsets = np.zeros(nx * ny + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum(np.bincount(cell_id, minlength=nx * ny))
+    offsets = G.csr_offsets(np.bincount(cell_id, minlength=nx * ny))
     entries = np.stack([sl[seg[order]], sk[seg[order]]], 1).astype(np.int32)
     return {"x0": x0, "y0": y0, "cell": cell, "nx": nx, "ny": ny, "cell_offsets": offsets.astype(np.int32),
             "entries": np.ascontiguousarray(entries)}
@@ -232,11 +231,9 @@ def node_support(cloud, lines, step=STEP, radius=RADIUS, intensity_floor=0.0, or
     dev = G.device("support", cloud.device if torch.is_tensor(cloud) and cloud.is_cuda else None)
     arrs = [np.asarray(l, dtype=np.float64).reshape(-1, 3) for l in lines]
     first = next((a[0] for a in arrs if len(a)), np.zeros(3))
-    org = np.floor(first / 1000.0) * 1000.0 if origin is None else np.asarray(origin, dtype=np.float64).reshape(3)
+    org = F.floor_km(first) if origin is None else np.asarray(origin, dtype=np.float64).reshape(3)
     shifted, cums = F._lines(arrs, org)
-    counts = np.array([int(np.floor(c[-1] / step)) + 1 if len(c) else 0 for c in cums], dtype=np.int64)
-    node_off = np.zeros(len(arrs) + 1, dtype=np.int64)
-    node_off[1:] = np.cumsum(counts)
+    node_off = F.node_offsets(cums, step)
     n_nodes = int(node_off[-1])
     pts = _cloud(cloud, dev, "node_support")
     acc = torch.zeros((n_nodes, COLS), dtype=torch.int64, device=dev)

@@ -544,15 +544,14 @@ def render_drive3d(drive_dir, gt_json, out_dir=None, name=None, max_slices=None,
     slice, 'points', 'offsets': slice_cloud's}.  With out_dir: NAME_merged.png, NAME_slice_POSE.png
     and NAME.json.  ValueError for a drive without poses or points."""
     from . import drive as D
-    from .io import load_pcd_data
     _need_gpu("render_drive3d")
     dev = G.device("view3d")
     poses = D.load_poses(os.path.join(drive_dir, "pose"))
-    pcd_path = os.path.join(drive_dir, "merged.pcd")
-    cloud = np.atleast_2d(load_pcd_data(pcd_path)) if poses and os.path.exists(pcd_path) else np.zeros((0, 4))
+    have = poses and os.path.exists(os.path.join(drive_dir, "merged.pcd"))
+    cloud = D.load_merged_cloud(drive_dir) if have else np.zeros((0, 4))
     if cloud.shape[0] == 0 or cloud.shape[1] < 4:
         raise ValueError(f"render_drive3d: {drive_dir} has no poses or no points")
-    cloud_t = torch.from_numpy(np.ascontiguousarray(cloud[:, :4], dtype=np.float32)).to(dev)
+    cloud_t = torch.from_numpy(np.ascontiguousarray(cloud, dtype=np.float32)).to(dev)
     gt_items = D.load_gt_items(gt_json) if gt_json and os.path.exists(gt_json) else []
     chosen = D.plan_slices(poses)
     chosen = chosen if max_slices is None else chosen[:int(max_slices)]

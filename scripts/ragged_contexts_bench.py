@@ -73,14 +73,14 @@ def model_side(model, pts, oh, cands, seed=0):
         return n
 
     def batched(which_cands):
-        return fuse.refine_slices_batched(model, pts, oh, which_cands, 32, 1024, 0.3, 2.0, seed, None, fuse.MIN_TUBE_POINTS)
+        return fuse.refine_slices(model, pts, oh, which_cands, 32, 1024, 0.3, 2.0, seed, None, fuse.MIN_TUBE_POINTS, batched=True)
 
     loop(used[:4])
     batched([c if si in used[:4] else [] for si, c in enumerate(cands)])
     loop_ms, n_lines = wall_ms(lambda: loop(used))
     batched_ms, res = wall_ms(lambda: batched(cands))
 
-    # ---- the ragged build in phases, on the same inputs refine_slices_batched builds
+    # ---- the ragged build in phases, on the same inputs refine_slices(batched=True) builds
     dev = pts.device
     lib = L.lib()
     points = pts.to(torch.float32)
