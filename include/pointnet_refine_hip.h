@@ -142,7 +142,41 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
  * forward keeps - and `fused`, and the gradient buffers of the backward - STORED in bf16
  * (uint16_t = raw bf16 bits).  Accumulation, BatchNorm statistics (taken from the rounded
  * values), parameters and parameter gradients are fp32.  Channel widths must be multiples of 8
- * (the context rows are padded to 8 channels internally). */
+ * (the context rows are padded to 8 channels internally).
+ *
+ * The rounding contract: bf16() is round to nearest even (v_cvt_pk_bf16_f32) and is applied exactly
+ * here; everything else is fp32 arithmetic.  tests/_encoder_ref.py states the same with store=bf16
+ * and tests/test_encoder16_abi_gpu.py holds the two entry points to it.
+ *   forward
+ *     conv1, in_channel <= 8   z1 = bf16(b + W x): fp32 operands, fmaf chain in channel order
+ *     conv1, in_channel > 8    x and W rounded to bf16, rows zero-padded to a multiple of 8 channels;
+ *                              z1 = bf16(acc + b)
+ *     conv2..5, fusion         A = bf16(relu(fmaf(z_prev, scale, shift))), W = bf16(W), z = bf16(acc + b)
+ *     BatchNorm statistics     of the ROUNDED z; rstd, scale, shift and the running statistics as in
+ *                              the fp32 contract
+ *     gate                     u = bf16(relu(fmaf(intensity, w1, b1))), W2 = bf16(W2),
+ *                              m = 0.5 + 0.5*sigmoid(acc + b2) in fp32; saved.gate = bf16(m);
+ *                              fused = bf16(relu(fmaf(zf, s, t)) * m) with the UNROUNDED m
+ *     pooling                  max and first arg-max over the bf16 `fused`; mean = fp32 sum / N
+ *   backward
+ *     combine step             d = d_fused (bf16) + d_gfeat's mean term / N + its max term at the arg-max;
+ *                              dy_f = bf16(pre > 0 ? d*m : 0) with m = saved.gate as stored, sig = 2m - 1,
+ *                              dG = bf16(d * relu(pre) * 0.5*sig*(1 - sig)) written over saved.gate;
+ *                              the BatchNorm sums are taken from the rounded dy_f
+ *     BatchNorm apply          dz = bf16(fmaf(ka, dy, fmaf(kb, z, kc))) in place; db comes from the two
+ *                              sums (the sum of the UNROUNDED dz: analytically zero in training)
+ *     wgrads                   operands: the bf16 dz and the bf16 prologue activations A of the forward;
+ *                              fp32 slabs summed in fp64
+ *     fusion dgrad             its block of dy_cat = bf16(mask(dz_f . bf16(W)))
+ *     conv dgrads              accumulate, new = bf16(mask(old_bf16 + dz . bf16(W))); the sums for the
+ *                              layer below are taken from the rounded result
+ *     conv1                    dW from the fp32 ctx rows (in_channel <= 8) or the bf16 padded rows with
+ *                              the pad columns dropped; d_ctx = dz_1 . bf16(W1), fp32
+ *     gate part                the bf16 dG is the operand of both GEMMs (dW2 against the bf16 u);
+ *                              dU = mask(dG . bf16(W2)) and what follows it are fp32
+ * Shapes: d_ctx needs in_channel % 4 == 0, and out_dim <= 3008 (the fusion conv's K = 960 + out_dim
+ * must fit the LDS image of its prologue coefficients).  Every shape either entry point cannot serve
+ * is refused with PRH_ERR_ARG before the device is touched: nothing is written, saved.gate included. */
 typedef struct {
   uint16_t* z_cat;   /* [P, cat]      bf16 pre-BN outputs of conv1..5 */
   uint16_t* z_fus;   /* [P, out_dim]  bf16 pre-BN output of the fusion conv */

@@ -319,6 +319,11 @@ static_assert(8 * 32 * EPI_LDW * 4 <= S3_LDS, "epilogue scratch must fit in the 
 // ------------------------------------------------------------------ bf16 mode launchers (prh_b16.hpp)
 // C[M,N] = pro(A) W^T on the bf16 NT core.  A bf16 (A16) or fp32, C / C2 / matrix E1 bf16 (C16)
 // or fp32.  p.wprep must hold b16_weight_bytes(N, K).  Leading dimensions in elements.
+// dynamic LDS of the bf16 NT core: two stages + (with a prologue) the two coefficient vectors
+inline size_t nt_b16_lds(int K, int pro) {
+  return (size_t)H2_LDS + (pro == PRO_NONE ? 0 : 2 * (size_t)(cdiv(K, B16_BK) + 2) * B16_BK * 4);
+}
+inline bool nt_b16_depth_ok(int K, int pro) { return nt_b16_lds(K, pro) <= 160 * 1024; }
 template <int PRO, int EPI, bool A16, bool C16>
 int launch_nt_b16(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {
   if (p.M <= 0 || p.N <= 0) return PRH_OK;
@@ -329,8 +334,8 @@ int launch_nt_b16(NTParams& p, hipStream_t st, StatInfo* si = nullptr) {
                 p.K, p.N, p.lda, p.ldc);
   if (rowvec && C16) return fail(PRH_ERR_ARG, "gemm_nt_b16: a row-vector E1 comes with fp32 outputs");
   const int KT = cdiv(p.K, B16_BK), NTl = cdiv(p.N, 256);
-  const size_t lds = (size_t)H2_LDS + (PRO == PRO_NONE ? 0 : 2 * (size_t)(KT + 2) * B16_BK * 4);
-  if (lds > 160 * 1024) return fail(PRH_ERR_ARG, "gemm_nt_b16: K=%d too deep for the prologue coefficient image", p.K);
+  const size_t lds = nt_b16_lds(p.K, PRO);
+  if (!nt_b16_depth_ok(p.K, PRO)) return fail(PRH_ERR_ARG, "gemm_nt_b16: K=%d too deep for the prologue coefficient image", p.K);
   const long th = (long)NTl * 256 * KT * 8;
   hipLaunchKernelGGL(prep_weights_b16_kernel, dim3((unsigned)cdiv(th, 256)), dim3(256), 0, st, p.W, p.N, p.K, p.ldw,
                      p.wprep + S3_WHDR);
@@ -1941,6 +1946,23 @@ int prh_encoder_backward(const prh_encoder_params* prm, const float* ctx, int B,
 // Encoder with bf16 activation storage on the bf16 cores (prh_b16.hpp); same arithmetic and
 // the same order of operations as prh_encoder_forward / prh_encoder_backward.
 
+// Every shape rule of the launches inside the two entry points (launch_nt_b16, launch_tn_b16, bn_bwd_apply16, the
+// combine kernels), so that a shape is refused before the device is touched and before anything is written:
+// 8-element vectors of bf16 on every width, the fusion conv's K = cat within the LDS image of its BN+ReLU prologue
+// (cat <= 3968, i.e. out_dim <= 3008), and - backward, when d_ctx is asked for - in_channel % 4 == 0 for the fp32
+// vector stores of the conv1 dgrad.
+static int check_encoder_bf16(const prh_encoder_params* prm, long P, bool want_dctx, const char* who) {
+  if (P > 1000000000L) return fail(PRH_ERR_ARG, "%s: B*N too large", who);
+  for (int l = 0; l < 5; ++l)
+    if (prm->conv[l].cout % 8) return fail(PRH_ERR_ARG, "%s: channel widths must be multiples of 8", who);
+  if (prm->out_dim % 8) return fail(PRH_ERR_ARG, "%s: out_dim must be a multiple of 8", who);
+  if (!nt_b16_depth_ok(enc_cat(prm), PRO_BNRELU))
+    return fail(PRH_ERR_ARG, "%s: out_dim=%d puts the fusion conv's K=%d beyond the prologue coefficient image (K <= 3968)",
+                who, prm->out_dim, enc_cat(prm));
+  if (want_dctx && prm->in_channel % 4) return fail(PRH_ERR_ARG, "%s: d_ctx needs in_channel %% 4 == 0", who);
+  return PRH_OK;
+}
+
 size_t prh_encoder_bf16_workspace_bytes(int B, int N, int in_channel, int out_dim, int backward) {
   const int ch[6] = {in_channel, 64, 128, 256, 512, out_dim};
   Arena a; Enc16WS e;
@@ -1956,12 +1978,9 @@ int prh_encoder_forward_bf16(const prh_encoder_params* prm, const float* ctx, in
   if (!ctx || !fused || !sv || !sv->z_cat || !sv->z_fus || !sv->bn_scale || !sv->bn_shift || !sv->bn_mean ||
       !sv->bn_rstd || B <= 0 || N <= 0)
     return fail(PRH_ERR_ARG, "encoder_forward_bf16: bad argument");
-  if ((long)B * N > 1000000000L) return fail(PRH_ERR_ARG, "encoder_forward_bf16: B*N too large");
+  TRY(check_encoder_bf16(prm, (long)B * N, false, "encoder_forward_bf16"));
   const int P = B * N;
   if (training && P < 2) return fail(PRH_ERR_ARG, "Expected more than 1 value per channel when training");
-  for (int l = 0; l < 5; ++l)
-    if (prm->conv[l].cout % 8) return fail(PRH_ERR_ARG, "encoder_forward_bf16: channel widths must be multiples of 8");
-  if (prm->out_dim % 8) return fail(PRH_ERR_ARG, "encoder_forward_bf16: out_dim must be a multiple of 8");
   const int cat = enc_cat(prm), od = prm->out_dim, C = prm->in_channel, c0p = cin_pad8(C);
   const int ch[6] = {C, prm->conv[0].cout, prm->conv[1].cout, prm->conv[2].cout, prm->conv[3].cout, od};
   Arena a(workspace, workspace_bytes);
@@ -2050,6 +2069,8 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
   if (!ctx || !sv || !gr || !sv->z_cat || !sv->z_fus || !sv->gate || (!d_fused && !d_gfeat) || B <= 0 || N <= 0)
     return fail(PRH_ERR_ARG, "encoder_backward_bf16: bad argument (a gradient and saved.gate are required)");
   if (d_gfeat && !sv->argmax) return fail(PRH_ERR_ARG, "encoder_backward_bf16: d_gfeat needs saved.argmax");
+  // every shape refusal of the launches below, before the device is touched: saved.gate is overwritten by step (1)
+  TRY(check_encoder_bf16(prm, (long)B * N, d_ctx != nullptr, "encoder_backward_bf16"));
   const int P = B * N;
   const int cat = enc_cat(prm), od = prm->out_dim, C = prm->in_channel, c0p = cin_pad8(C);
   const int ch[6] = {C, prm->conv[0].cout, prm->conv[1].cout, prm->conv[2].cout, prm->conv[3].cout, od};
@@ -2147,7 +2168,6 @@ int prh_encoder_backward_bf16(const prh_encoder_params* prm, const float* ctx, i
       NTParams p; memset(&p, 0, sizeof(p));
       p.A = f16p(w.dy_cat + o); p.lda = cat; p.W = w.wT; p.ldw = co; p.M = P; p.N = C; p.K = co;
       p.C = d_ctx; p.ldc = C; p.wprep = w.wprep; p.flags = 0;
-      if (C % 4) return fail(PRH_ERR_ARG, "encoder_backward_bf16: d_ctx needs in_channel %% 4 == 0");
       TRY((launch_nt_b16<PRO_NONE, EPI_DGRAD, true, false>(p, st)));
     }
   }

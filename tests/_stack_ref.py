@@ -5,6 +5,16 @@ taken to fp64 on entry.  Layer l is followed by a ReLU when l < L - 1 or relu_la
 where(mask, y, 0) so that masks taken elsewhere - from the device's own z, scale and shift (device_masks) - can stand
 in for the layer's own y > 0: with the masks fixed the stack is Linear + BatchNorm only, and two evaluations differ by
 arithmetic error alone.  No torch, no GPU.
+
+`store` is the one storage hook of both passes.  None is the fp32 contract: nothing is rounded and every statement
+below is the plain fp64 one.  A Store (BF16, BF16_VIA_F32) is the bf16-storage contract of the *_bf16 entry points: it
+is applied wherever that contract stores or feeds a 16-bit value, and to nothing else -
+    forward   A = store(relu(z_prev * scale + shift)) and W = store(W) feed every GEMM (the first layer's x and W too
+              unless store_first = 0: the VALU first layer on fp32 operands), z = store(A W^T + b), and the BatchNorm
+              statistics are those of the stored z;
+    backward  dz = store(ca*dy + cb*z + cc) (db stays the sum of the unrounded expression: bn_bwd_finalize_kernel
+              forms it from the partial sums), dw = dz^T A with the stored dz and the stored A of the forward,
+              dx = dz store(W), and a masked dx that a buffer holds (l > 0) is stored.
 """
 import numpy as np
 
@@ -15,40 +25,83 @@ def _f64(a):
     return np.asarray(a, dtype=np.float64)
 
 
+def bf16(a):
+    """Round to nearest even to 8 significant bits (v_cvt_pk_bf16_f32; the exponent range is fp32's and is not
+    modelled: no value here comes near it)."""
+    m, e = np.frexp(_f64(a))
+    return np.ldexp(np.rint(m * 256.0), e - 8)
+
+
+class Store:
+    """store(a): the value a 16-bit buffer or operand holds for the result a.  `via`: a type every result passes
+    through first (np.float32: one fp32 evaluation of the contract, as a kernel's fp32 registers; None: fp64)."""
+
+    def __init__(self, rounding=bf16, via=None):
+        self.rounding, self.via = rounding, via
+
+    def result(self, a):
+        return _f64(a) if self.via is None else _f64(_f64(a).astype(self.via))
+
+    def __call__(self, a):
+        return self.rounding(self.result(a))
+
+
+BF16, BF16_VIA_F32 = Store(), Store(via=np.float32)
+
+
+def stored(store, a):
+    """What a 16-bit buffer or operand holds (a itself in the fp32 contract)."""
+    return a if store is None else store(a)
+
+
+def result(store, a):
+    """A result that stays in fp32 (accumulators, statistics, parameter gradients)."""
+    return a if store is None else store.result(a)
+
+
 def has_relu(l, L, relu_last):
     return l < L - 1 or bool(relu_last)
 
 
-def forward(x, layers, training, momentum, eps, relu_last, running, masks=None, mutation=None):
+def batchnorm(z, ly, rn, training, momentum, eps, mutation=None, store=None):
+    """mean, rstd, scale, shift and the running statistics after the call, of the z given (with a store: the stored z)."""
+    gamma, beta = _f64(ly["gamma"]), _f64(ly["beta"])
+    rm, rv = _f64(rn[0]), _f64(rn[1])
+    P = z.shape[0]
+    if training:
+        mean = result(store, z.mean(axis=0))
+        m2 = ((z - mean) ** 2).sum(axis=0)
+        rstd = result(store, 1.0 / np.sqrt(m2 / P + eps))
+        new_rm = (1.0 - momentum) * rm + momentum * mean
+        new_rv = (1.0 - momentum) * rv + momentum * (m2 / (P if mutation == "biased_running_var" else P - 1))
+    else:
+        mean, rstd, new_rm, new_rv = rm, 1.0 / np.sqrt(rv + eps), rm, rv
+    scale = result(store, gamma * rstd)
+    shift = result(store, beta - mean * scale)
+    return dict(mean=mean, rstd=rstd, scale=scale, shift=shift, running_mean=new_rm, running_var=new_rv)
+
+
+def forward(x, layers, training, momentum, eps, relu_last, running, masks=None, mutation=None, store=None,
+            store_first=1):
     """Per layer: z, mean, rstd (biased variance), scale, shift, y (post-BN), running_mean / running_var after the call
     (unbiased variance, as nn.BatchNorm1d; unchanged in eval), mask (the layer's own y > 0) and out.
     mutation: one of MUTATIONS, a deliberate mistake (tests/test_stack_ref_cpu.py shows the inputs detect each)."""
     L = len(layers)
     h = _f64(x)
-    P = h.shape[0]
     recs = []
     for l, ly in enumerate(layers):
-        w, b, gamma, beta = (_f64(ly[k]) for k in ("w", "b", "gamma", "beta"))
-        rm, rv = _f64(running[l][0]), _f64(running[l][1])
-        z = h @ w.T + b
-        if training:
-            mean = z.mean(axis=0)
-            m2 = ((z - mean) ** 2).sum(axis=0)
-            rstd = 1.0 / np.sqrt(m2 / P + eps)
-            new_rm = (1.0 - momentum) * rm + momentum * mean
-            new_rv = (1.0 - momentum) * rv + momentum * (m2 / (P if mutation == "biased_running_var" else P - 1))
-        else:
-            mean, rstd, new_rm, new_rv = rm, 1.0 / np.sqrt(rv + eps), rm, rv
-        scale = gamma * rstd
-        shift = beta - mean * scale
-        y = z * scale + shift
+        w, b = _f64(ly["w"]), _f64(ly["b"])
+        if l > 0 or store_first:
+            h, w = stored(store, h), stored(store, w)
+        z = stored(store, h @ w.T + b)
+        bn = batchnorm(z, ly, running[l], training, momentum, eps, mutation, store)
+        y = z * bn["scale"] + bn["shift"]
         own = y > 0
         if has_relu(l, L, relu_last):
             out = np.where(own if masks is None else masks[l], y, 0.0)
         else:
             out = y
-        recs.append(dict(z=z, mean=mean, rstd=rstd, scale=scale, shift=shift, y=y, running_mean=new_rm,
-                         running_var=new_rv, mask=own, out=out))
+        recs.append(dict(z=z, y=y, mask=own, out=out, **bn))
         h = out
     return recs
 
@@ -68,11 +121,14 @@ def records_from_saved(z_cat, scale, shift, mean, rstd, widths, relu_last, masks
     return recs
 
 
-def backward(dy, x, layers, recs, training, relu_last, masks, mutation=None, coeff_dtype=None):
+def backward(dy, x, layers, recs, training, relu_last, masks, mutation=None, coeff_dtype=None, store=None,
+             store_first=1, dy_stats=None):
     """dx and, per layer, dw, db, dgamma, dbeta (and dz, for the tests' scales) from the records of a forward.
     Training: the full BatchNorm backward.  Eval: dz = scale * dy.
     coeff_dtype: round the three BatchNorm-backward coefficient vectors to this type and nothing else - what storing
-    them in fp32 alone costs (at P = 2 the terms of dz cancel to eps / (var + eps) of themselves)."""
+    them in fp32 alone costs (at P = 2 the terms of dz cancel to eps / (var + eps) of themselves).
+    store, store_first: the storage hook (module docstring).  dy_stats: what the last layer's two BatchNorm sums are
+    taken from when not from dy itself (a deliberate mistake of tests/_encoder_ref.py)."""
     L = len(layers)
     P = recs[0]["z"].shape[0]
     g = _f64(dy)
@@ -83,8 +139,9 @@ def backward(dy, x, layers, recs, training, relu_last, masks, mutation=None, coe
         r = recs[l]
         w, gamma = _f64(layers[l]["w"]), _f64(layers[l]["gamma"])
         xhat = (r["z"] - r["mean"]) * r["rstd"]
-        dbeta = g.sum(axis=0)
-        dgamma = (g * xhat).sum(axis=0)
+        gs = g if dy_stats is None or l < L - 1 else _f64(dy_stats)
+        dbeta = result(store, gs.sum(axis=0))
+        dgamma = result(store, (gs * xhat).sum(axis=0))
         if training:
             dz = gamma * r["rstd"] * (g - dbeta / P - xhat * (dgamma / P))
             if coeff_dtype is not None:
@@ -99,11 +156,17 @@ def backward(dy, x, layers, recs, training, relu_last, masks, mutation=None, coe
                 dz = dz - gamma * r["rstd"] * (m2 * r["mean"] * r["rstd"] - dbeta / P)
         else:
             dz = r["scale"] * g
+        db = dz.sum(axis=0)
+        dz = stored(store, dz)
         h = recs[l - 1]["out"] if l > 0 else _f64(x)
-        grads[l] = dict(dw=dz.T @ h, db=dz.sum(axis=0), dgamma=dgamma, dbeta=dbeta, dz=dz)
-        g = dz @ w
+        if l > 0 or store_first:
+            h = stored(store, h)
+        grads[l] = dict(dw=result(store, dz.T @ h), db=result(store, db), dgamma=dgamma, dbeta=dbeta, dz=dz)
+        g = result(store, dz @ stored(store, w))
         if l > 0 and mutation != "dgrad_unmasked":
             g = np.where(masks[l - 1], g, 0.0)
+        if l > 0:
+            g = stored(store, g)
     return g, grads
 
 

@@ -4,7 +4,9 @@ operands AND bf16 activation storage in the encoder (csrc/prh_b16.hpp).
 Two kinds of checks:
   * the kernels compute what they say - against fp64 arithmetic on the SAME bf16-rounded
     operands the errors are at fp32-accumulation level (1e-5), which pins indexing, swizzles,
-    prologues, epilogues and tails independently of the precision question;
+    prologues, epilogues and tails independently of the precision question.  Here that is done
+    for the bf16 Linear kernels; for the encoder pair (prh_encoder_forward_bf16 /
+    prh_encoder_backward_bf16) this check lives in tests/test_encoder16_abi_gpu.py;
   * the mode as a whole against the reference's fp32 results (oracle, golden vectors G1-G3):
     the looser gate SURVEY 8(d) states for reduced precision - max-abs on `out` <= 5e-2 - and
     the gradient error the mode really has, stated below per test.

@@ -501,7 +501,8 @@ def test_a_missing_or_short_workspace_is_refused(lib_mode, mode):
 
 def test_the_bf16_pair_refuses_a_missing_or_short_workspace(lib_mode):
     """The same defect and the same rule on prh_encoder_forward_bf16 / prh_encoder_backward_bf16; their numerics are
-    pinned elsewhere (tests/test_bf16_gpu.py)."""
+    pinned in tests/test_encoder16_abi_gpu.py (fp64 with the storage roundings of the bf16 contract), and
+    tests/test_bf16_gpu.py asks whether bf16 is precise enough."""
     from pointnet_refine_amd import _lib as L, ops
     lib = lib_mode(4)
     en = Encoder(lib, SMALL.inputs)
