@@ -76,51 +76,11 @@ def attribute(fused, gt):
     return owner
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("drive_dir")
-    ap.add_argument("results_json")
-    ap.add_argument("--checkpoint", default=None)
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--gt", default=None)
-    ap.add_argument("--png", default=None)
-    ap.add_argument("--step", type=float, default=0.5)
-    ap.add_argument("--gate", type=float, default=1.0)
-    ap.add_argument("--min-pieces", type=int, default=2)
-    ap.add_argument("--batched", action="store_true", help="contexts of all frames in one ragged GPU pass")
-    ap.add_argument("--device-sync", action="store_true", help="piece linking steps 5-6 on the GPU (the same map)")
-    ap.add_argument("--support", action="store_true", help="score the map against the cloud (no GT needed)")
-    ap.add_argument("--intensity-floor", type=float, default=0.0)
-    ap.add_argument("--lift", action="store_true", help="put the detector's lines on the road read from the cloud")
-    ap.add_argument("--lift-radius", type=float, default=0.5)
-    ap.add_argument("--align", action="store_true", help="move the detector's lines in x y onto the paint of the cloud")
-    ap.add_argument("--align-max-shift", type=float, default=1.0)
-    ap.add_argument("--align-scope", choices=("frame", "drive"), default="frame")
-    ap.add_argument("--align-max-yaw", type=float, default=0.0, metavar="RAD",
-                    help="with --align: also sweep a yaw of up to RAD radians about each frame's ego origin")
-    args = ap.parse_args()
-
-    from pointnet_refine_amd import drive, fuse, link
-    res = link.refine_predictions(load_model(args.checkpoint), args.drive_dir, args.results_json, seed=args.seed,
-                                  step=args.step, gate=args.gate, min_pieces=args.min_pieces, batched=args.batched,
-                                  support=args.support, intensity_floor=args.intensity_floor,
-                                  device_sync=args.device_sync, lift=args.lift, lift_radius=args.lift_radius,
-                                  align=args.align, align_max_shift=args.align_max_shift, align_scope=args.align_scope,
-                                  align_max_yaw=args.align_max_yaw)
+def report_map(res, args):
+    """The map, support and map_error lines, MAP.json and the --png picture: what this tool and
+    examples/refine_cloud.py print once the drive is refined.  args: out, drive_dir, support, gt, png."""
+    from pointnet_refine_amd import drive, fuse
     rep = res["report"]
-    if args.lift:
-        print(f"GROUND LIFT  {rep['lift_lines_lifted']} of {rep['lift_lines']} lines lifted "
-              f"({rep['lift_lines_unlifted']} left at the detector's z)   {rep['lift_stations_without_ground']} of "
-              f"{rep['lift_stations']} stations without ground")
-    if args.align:
-        norm = np.hypot(rep["align_shifts"][:, 0], rep["align_shifts"][:, 1]) if rep["align_frames"] else np.zeros(1)
-        yaw = ""
-        if args.align_max_yaw > 0.0:
-            a = np.abs(rep["align_yaws"]) if rep["align_frames"] else np.zeros(1)
-            yaw = f"   |yaw| median {float(np.median(a)) * 1e3:.1f} mrad   max {float(a.max()) * 1e3:.1f} mrad"
-        print(f"PAINT ALIGN  {rep['align_frames_aligned']} of {rep['align_frames']} frames aligned   |shift| median "
-              f"{float(np.median(norm)):.3f} m   max {float(norm.max()):.3f} m{yaw}   ({rep['align_candidates']} bright points)")
     print(f"{rep['slices']} frames, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['candidates']} candidate pairs, {rep['edges']} edges, {rep['clusters']} clusters, "
           f"{rep['clusters_kept']} kept ({rep['pieces_unlinked']} pieces unlinked), "
@@ -157,6 +117,54 @@ def main():
         path = os.path.join(args.png, os.path.basename(os.path.normpath(args.drive_dir)) + "_map.png")
         bev.write_png(path, rgba)
         print(f"Saved {path}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("drive_dir")
+    ap.add_argument("results_json")
+    ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--gt", default=None)
+    ap.add_argument("--png", default=None)
+    ap.add_argument("--step", type=float, default=0.5)
+    ap.add_argument("--gate", type=float, default=1.0)
+    ap.add_argument("--min-pieces", type=int, default=2)
+    ap.add_argument("--batched", action="store_true", help="contexts of all frames in one ragged GPU pass")
+    ap.add_argument("--device-sync", action="store_true", help="piece linking steps 5-6 on the GPU (the same map)")
+    ap.add_argument("--support", action="store_true", help="score the map against the cloud (no GT needed)")
+    ap.add_argument("--intensity-floor", type=float, default=0.0)
+    ap.add_argument("--lift", action="store_true", help="put the detector's lines on the road read from the cloud")
+    ap.add_argument("--lift-radius", type=float, default=0.5)
+    ap.add_argument("--align", action="store_true", help="move the detector's lines in x y onto the paint of the cloud")
+    ap.add_argument("--align-max-shift", type=float, default=1.0)
+    ap.add_argument("--align-scope", choices=("frame", "drive"), default="frame")
+    ap.add_argument("--align-max-yaw", type=float, default=0.0, metavar="RAD",
+                    help="with --align: also sweep a yaw of up to RAD radians about each frame's ego origin")
+    args = ap.parse_args()
+
+    from pointnet_refine_amd import link
+    res = link.refine_predictions(load_model(args.checkpoint), args.drive_dir, args.results_json, seed=args.seed,
+                                  step=args.step, gate=args.gate, min_pieces=args.min_pieces, batched=args.batched,
+                                  support=args.support, intensity_floor=args.intensity_floor,
+                                  device_sync=args.device_sync, lift=args.lift, lift_radius=args.lift_radius,
+                                  align=args.align, align_max_shift=args.align_max_shift, align_scope=args.align_scope,
+                                  align_max_yaw=args.align_max_yaw)
+    rep = res["report"]
+    if args.lift:
+        print(f"GROUND LIFT  {rep['lift_lines_lifted']} of {rep['lift_lines']} lines lifted "
+              f"({rep['lift_lines_unlifted']} left at the detector's z)   {rep['lift_stations_without_ground']} of "
+              f"{rep['lift_stations']} stations without ground")
+    if args.align:
+        norm = np.hypot(rep["align_shifts"][:, 0], rep["align_shifts"][:, 1]) if rep["align_frames"] else np.zeros(1)
+        yaw = ""
+        if args.align_max_yaw > 0.0:
+            a = np.abs(rep["align_yaws"]) if rep["align_frames"] else np.zeros(1)
+            yaw = f"   |yaw| median {float(np.median(a)) * 1e3:.1f} mrad   max {float(a.max()) * 1e3:.1f} mrad"
+        print(f"PAINT ALIGN  {rep['align_frames_aligned']} of {rep['align_frames']} frames aligned   |shift| median "
+              f"{float(np.median(norm)):.3f} m   max {float(norm.max()):.3f} m{yaw}   ({rep['align_candidates']} bright points)")
+    report_map(res, args)
 
 
 if __name__ == "__main__":

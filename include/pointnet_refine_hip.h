@@ -1329,6 +1329,84 @@ int prh_align_score_rigid(const void* records, const long long* cand_offsets, lo
                           const long long* items, long long n_items, double r2, long long* acc, int device,
                           void* stream);
 
+/* Paint tracing - the rule.
+ * Lane candidates read from the cloud itself: per slice, polylines along the bright ridges of its
+ * points, with no detector and no GT.  The lines are 3-D and lie on the paint, so they go to the
+ * slice refinement as they are, with no lift and no alignment.  The conventions are those of "Ground
+ * lift - the rule" and "Paint alignment - the rule": fp64 throughout, one rounding per operation, no
+ * contraction, every constant computed once on the host and passed in; the same bits go to the
+ * device and to the oracle (tests/_trace_oracle.py).
+ * Inputs.  points [T,4] = x y z intensity in the ego frame of their slice, float64 (is_double != 0,
+ * what drive.slice_cloud returns) or float32, converted to fp64 first, which is exact.  slice_offsets
+ * [S+1] int64; a slice has fewer than 2^22 points (the host raises ValueError).
+ * Grid.  Columns along ego x: nx = rint(2 * half_length / col) (half_length 25.0, col 0.5: 100);
+ * cells along y: ny = rint(2 * half_width / cell) (half_width 12.8, cell 0.05: 512); both computed
+ * on the host, 1 <= nx, ny <= 4096, 0 < half_length, half_width <= 128.  ix = floor((x + half_length)
+ * / col), iy = floor((y + half_width) / cell), decided on the floor in fp64; a point with ix outside
+ * 0 .. nx - 1 or iy outside 0 .. ny - 1 is dropped (a non-finite x or y is).
+ * Point weight.  Step 1 of the alignment rule: wI = min(max((double)I - intensity_floor, 0), 4096), qi
+ * = (long long)rint(wI * 256), a non-finite I gives 0.  A point with a non-finite z, with |z| > 512
+ * or with qi == 0 is dropped.  qx = (long long)rint(x * 1024), qy and qz likewise (half to even).
+ * Tables.  Per (slice, ix, iy): n (int32, the points kept), w = sum qi, wx = sum qi * qx, wy = sum
+ * qi * qy, wz = sum qi * qz (int64).  |x| < 3 * 128 and |z| <= 512 give |q| <= 2^19, qi <= 2^20, an
+ * addend below 2^39, and with fewer than 2^22 points per slice three cells stay below 2^63.
+ * Box.  b[iy] = w[iy-1] + w[iy] + w[iy+1] within the column, a cell outside 0 .. ny - 1 counting 0;
+ * n3, bx, by, bz likewise from n, wx, wy, wz.  b of a cell outside the grid is 0.
+ * Peak.  Cell (ix, iy) is a peak iff n3 >= min_points (default 3, >= 1), b >= min_weight (default
+ * 1, >= 1) and for every k = 1 .. nms (default 4, 0 <= nms <= prh_trace_max_nms() = 31): b > b[iy-k]
+ * and b >= b[iy+k].  The strict lower side makes the lower cell of a plateau the peak.  Its position
+ * is x = ((double)bx / (double)b) / 1024.0, y and z likewise: the weighted centroid of the box.  The
+ * peaks are ordered by (slice, ix, iy): peak_offsets [S*nx+1] is the CSR over all columns.
+ * Links.  tol(dc) = link_cells + gap_slope * (dc - 1) in integers (defaults 3 and 1).  succ(p), p at
+ * (ix, iy): the smallest dc in 1 .. max_gap_cols + 1 (default 24: 12 m, the gap of a dashed line)
+ * for which column ix + dc of the same slice holds a peak with |iy' - iy| <= tol(dc); within that
+ * column the peak with the smallest |iy' - iy|, of two the one with the smaller iy'; -1 where there
+ * is none.  pred(q) is the mirror image towards lower columns.  The link p -> q exists iff succ(p)
+ * == q and pred(q) == p; the outputs succ and pred hold mutual links only, -1 elsewhere.
+ * Lines (host, trace.chain_lines).  The maximal chains of links; a chain is kept iff it has at least
+ * min_peaks (3) peaks and x_last - x_first >= min_length (5.0 m) in fp64; the lines of a slice are
+ * ordered by their head's (ix, iy); their vertices are the peaks' x y z.
+ * Scope.  The rule follows ridges that run within about atan(link_cells * cell / col) of the ego x
+ * axis (17 degrees at the defaults); stop lines and crosswalks are not traced.  Without an
+ * intensity_floor that separates paint from asphalt it traces asphalt texture.
+ * All sums are integers, so the result does not depend on the order of the points, on their dtype,
+ * on the chunking of the slices or on the launch shape: it is bitwise reproducible by construction.
+ *   prh_trace_workspace_bytes  the tables of n_slices slices: n [C] int32 first, then w, wx, wy, wz
+ *                         [C] int64, each on a 256-byte boundary, C = n_slices * nx * ny, cell (s,
+ *                         ix, iy) at (s * nx + ix) * ny + iy; 0 for a shape outside the limits.  The
+ *                         caller may cut its slices into chunks that fit its memory: the tables of
+ *                         one chunk are filled, read by the two peak passes and dropped.
+ *   prh_trace_hist        zeroes the workspace, then one thread per point of rows first_row ..
+ *                         first_row + n_rows: slice_offsets [n_slices+1] holds the absolute rows of
+ *                         the chunk's slices (slice_offsets[0] <= first_row, first_row + n_rows <=
+ *                         slice_offsets[n_slices]).  x y in one load, z and I only inside the grid,
+ *                         one 32-bit and four 64-bit integer atomics per kept point.
+ *   prh_trace_peaks_count col_counts [n_slices*nx] int32: the peaks of every column.  One wave per
+ *                         column; w goes through LDS 256 cells at a time with a halo of 32.
+ *   prh_trace_peaks_write with col_offsets [n_slices*nx+1] int64 the exclusive prefix of col_counts
+ *                         (the caller scans): rows col_offsets[c] .. col_offsets[c+1] of iy (int32),
+ *                         weight = b (int64), count = n3 (int32), xyz [.,3] fp64 and col (int32:
+ *                         col_base + c, the column's number among all chunks' columns) are column c's
+ *                         peaks in ascending iy (ballot / popcount: no sort, no atomic).
+ *   prh_trace_link        one thread per peak over all chunks: col_offsets [n_cols+1] with n_cols a
+ *                         multiple of nx, iy and col as written above; succ and pred [n_peaks] int32.
+ * points must be aligned to two coordinates (16 bytes for fp64, 8 for float32), the workspace to 256
+ * bytes.  PRH_ERR_ARG for a parameter outside the limits above, PRH_ERR_WORKSPACE below
+ * prh_trace_workspace_bytes; both before the device is touched.  No float atomics. */
+int prh_trace_max_nms(void);
+size_t prh_trace_workspace_bytes(int n_slices, int nx, int ny);
+int prh_trace_hist(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long first_row,
+                   long long n_rows, double half_length, double col, int nx, double half_width, double cell, int ny,
+                   double intensity_floor, void* workspace, size_t workspace_bytes, int device, void* stream);
+int prh_trace_peaks_count(void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny, int nms, int min_points,
+                          long long min_weight, int* col_counts, int device, void* stream);
+int prh_trace_peaks_write(void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny, int nms, int min_points,
+                          long long min_weight, const long long* col_offsets, long long capacity, int col_base, int* iy,
+                          long long* weight, int* count, double* xyz, int* col, int device, void* stream);
+int prh_trace_link(const long long* col_offsets, long long n_cols, int nx, const int* iy, const int* col,
+                   long long n_peaks, int link_cells, int gap_slope, int max_gap_cols, int* succ, int* pred, int device,
+                   void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

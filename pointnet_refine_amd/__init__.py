@@ -10,6 +10,7 @@ from .metrics import (calibrate_alignment, calibrate_alignments, evaluate_scene,
 from .support import map_support, marking_attributes, node_support  # noqa: F401
 from .ground import ground_heights, lift_lines, line_stations  # noqa: F401
 from .align import align_lines, paint_scores, pick_shift, shift_grid  # noqa: F401
+from .trace import paint_peaks, refine_cloud, trace_lines  # noqa: F401
 
 __all__ = ["LineRefineNet", "MultiScalePointNetEncoder", "PositionalEncoding",
            "DetrTransformerDecoderLayer",
@@ -17,4 +18,5 @@ __all__ = ["LineRefineNet", "MultiScalePointNetEncoder", "PositionalEncoding",
            "shift_sweep_ragged", "calibrate_alignments", "evaluate_scenes",
            "node_support", "map_support", "marking_attributes",
            "ground_heights", "line_stations", "lift_lines",
-           "paint_scores", "align_lines", "pick_shift", "shift_grid"]
+           "paint_scores", "align_lines", "pick_shift", "shift_grid",
+           "paint_peaks", "trace_lines", "refine_cloud"]

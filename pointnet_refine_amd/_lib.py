@@ -109,6 +109,8 @@ EXPORTS = [
     "prh_align_select_write", "prh_align_score",
     "prh_align_max_poses", "prh_align_select_cells_workspace_bytes", "prh_align_select_cells_count",
     "prh_align_select_cells_write", "prh_align_score_rigid",
+    "prh_trace_max_nms", "prh_trace_workspace_bytes", "prh_trace_hist", "prh_trace_peaks_count", "prh_trace_peaks_write",
+    "prh_trace_link",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -514,6 +516,20 @@ def _bind(lib):
     lib.prh_align_select_cells_write.argtypes = [vp, i, vp, i, ll, vp, vp, vp, vp, ll, dbl, dbl, vp, vp, ll, vp, sz, i, vp]
     lib.prh_align_score_rigid.restype = i
     lib.prh_align_score_rigid.argtypes = [vp, vp, ll, vp, ll, vp, i, vp, vp, vp, ll, vp, vp, i, vp, ll, dbl, vp, i, vp]
+    if not hasattr(lib, "prh_trace_link"):
+        return lib      # an older build under PRH_LIB_PATH (A/B runs): it has no paint tracing
+    lib.prh_trace_max_nms.restype = i
+    lib.prh_trace_max_nms.argtypes = []
+    lib.prh_trace_workspace_bytes.restype = sz
+    lib.prh_trace_workspace_bytes.argtypes = [i, i, i]
+    lib.prh_trace_hist.restype = i
+    lib.prh_trace_hist.argtypes = [vp, i, vp, i, ll, ll, dbl, dbl, i, dbl, dbl, i, dbl, vp, sz, i, vp]
+    lib.prh_trace_peaks_count.restype = i
+    lib.prh_trace_peaks_count.argtypes = [vp, sz, i, i, i, i, i, ll, vp, i, vp]
+    lib.prh_trace_peaks_write.restype = i
+    lib.prh_trace_peaks_write.argtypes = [vp, sz, i, i, i, i, i, ll, vp, ll, i, vp, vp, vp, vp, vp, i, vp]
+    lib.prh_trace_link.restype = i
+    lib.prh_trace_link.argtypes = [vp, ll, i, vp, vp, ll, i, i, i, vp, vp, i, vp]
     return lib
 
 

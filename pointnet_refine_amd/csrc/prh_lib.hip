@@ -35,6 +35,7 @@
 #include "prh_support.hpp"
 #include "prh_ground.hpp"
 #include "prh_align.hpp"
+#include "prh_trace.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
@@ -3942,6 +3943,118 @@ int prh_align_score_rigid(const void* records, const long long* cand_offsets, lo
   return align_score(true, records, cand_offsets, n_candidates, line_vertices, n_vertices, line_offsets, n_lines,
                      slice_line_offsets, poses, pose_offsets, n_poses, pivots, reach, n_slices, items, n_items, r2, acc,
                      device, stream);
+}
+
+// ------------------------------------------------------------------ paint tracing
+int prh_trace_max_nms(void) { return TRACE_MAX_NMS; }
+static bool trace_shape_ok(int n_slices, int nx, int ny) {
+  return n_slices >= 0 && nx >= 1 && nx <= TRACE_MAX_CELLS && ny >= 1 && ny <= TRACE_MAX_CELLS &&
+         (long long)n_slices * nx <= 0x7fffffffll;
+}
+// n [C] int32 first, then w, wx, wy, wz [C] int64, each on a 256-byte boundary; C = n_slices * nx * ny
+size_t prh_trace_workspace_bytes(int n_slices, int nx, int ny) {
+  if (!trace_shape_ok(n_slices, nx, ny)) return 0;
+  const size_t cells = (size_t)n_slices * (size_t)nx * (size_t)ny;
+  return align_up(cells * sizeof(int), 256) + 4 * align_up(cells * sizeof(long long), 256);
+}
+static int trace_tables(const char* what, void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny,
+                        TraceTables& t) {
+  if (!trace_shape_ok(n_slices, nx, ny))
+    return fail(PRH_ERR_ARG, "%s: 1 <= nx, ny <= %d and fewer than 2^31 columns", what, TRACE_MAX_CELLS);
+  if (n_slices == 0) return PRH_OK;
+  if (!workspace || ((uintptr_t)workspace & 255) != 0 || workspace_bytes < prh_trace_workspace_bytes(n_slices, nx, ny))
+    return fail(PRH_ERR_WORKSPACE, "%s: workspace missing, not 256-byte aligned or too small (%zu bytes)", what,
+                workspace_bytes);
+  const size_t cells = (size_t)n_slices * (size_t)nx * (size_t)ny;
+  char* p = (char*)workspace;
+  t.n = (int*)p;
+  p += align_up(cells * sizeof(int), 256);
+  unsigned long long** tabs[4] = {&t.w, &t.wx, &t.wy, &t.wz};
+  for (auto tab : tabs) {
+    *tab = (unsigned long long*)p;
+    p += align_up(cells * sizeof(long long), 256);
+  }
+  return PRH_OK;
+}
+int prh_trace_hist(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long first_row,
+                   long long n_rows, double half_length, double col, int nx, double half_width, double cell, int ny,
+                   double intensity_floor, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  TraceTables t{};
+  TRY_RC(trace_tables("trace_hist", workspace, workspace_bytes, n_slices, nx, ny, t));
+  if (first_row < 0 || n_rows < 0 || n_rows >= 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "trace_hist: bad argument");
+  if (!(half_length > 0.0) || !(half_length <= 128.0) || !(half_width > 0.0) || !(half_width <= 128.0) || !(col > 0.0) ||
+      !(cell > 0.0) || !(col < 1e300) || !(cell < 1e300))
+    return fail(PRH_ERR_ARG, "trace_hist: 0 < half_length, half_width <= 128 and col, cell positive and finite");
+  if (!(intensity_floor == intensity_floor) || !(fabs(intensity_floor) < 1e300))
+    return fail(PRH_ERR_ARG, "trace_hist: intensity_floor must be finite");
+  if (n_rows > 0 && (!points || !slice_offsets || n_slices == 0)) return fail(PRH_ERR_ARG, "trace_hist: points without a slice");
+  if (((uintptr_t)points & (is_double ? 15 : 7)) != 0)
+    return fail(PRH_ERR_ARG, "trace_hist: points must be aligned to two coordinates (%d bytes)", is_double ? 16 : 8);
+  if (n_slices == 0) return PRH_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(workspace, 0, prh_trace_workspace_bytes(n_slices, nx, ny), st));
+  if (n_rows == 0) return PRH_OK;
+  const TraceGrid g{half_length, col, half_width, cell, intensity_floor, nx, ny};
+  const unsigned nblk = (unsigned)((n_rows + TRACE_THREADS - 1) / TRACE_THREADS);
+  for_points(is_double, [&](auto v) {
+    using T = decltype(v);
+    hipLaunchKernelGGL(trace_hist_kernel<T>, dim3(nblk), dim3(TRACE_THREADS), 0, st, (const T*)points, slice_offsets,
+                       n_slices, first_row, n_rows, g, t);
+  });
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+static int trace_peaks(bool write, void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny, int nms,
+                       int min_points, long long min_weight, int* col_counts, const long long* col_offsets,
+                       long long capacity, int col_base, int* iy, long long* weight, int* count, double* xyz, int* col,
+                       int device, void* stream) {
+  const char* what = write ? "trace_peaks_write" : "trace_peaks_count";
+  TraceTables t{};
+  TRY_RC(trace_tables(what, workspace, workspace_bytes, n_slices, nx, ny, t));
+  if (nms < 0 || nms > TRACE_MAX_NMS || min_points < 1 || min_weight < 1)
+    return fail(PRH_ERR_ARG, "%s: 0 <= nms <= %d, min_points >= 1 and min_weight >= 1", what, TRACE_MAX_NMS);
+  if (col_base < 0 || capacity < 0 || capacity > 0x7fffffffll) return fail(PRH_ERR_ARG, "%s: bad argument", what);
+  if (n_slices == 0 || (write && capacity == 0)) return PRH_OK;
+  if (write ? (!col_offsets || !iy || !weight || !count || !xyz || !col) : !col_counts)
+    return fail(PRH_ERR_ARG, "%s: null pointer", what);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  auto kernel = write ? trace_peaks_kernel<true> : trace_peaks_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(n_slices * nx)), dim3(64), 0, st, t, ny, nms, min_points, min_weight,
+                     col_counts, col_offsets, capacity, col_base, iy, weight, count, xyz, col);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_trace_peaks_count(void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny, int nms, int min_points,
+                          long long min_weight, int* col_counts, int device, void* stream) {
+  return trace_peaks(false, workspace, workspace_bytes, n_slices, nx, ny, nms, min_points, min_weight, col_counts, nullptr,
+                     0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, device, stream);
+}
+int prh_trace_peaks_write(void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny, int nms, int min_points,
+                          long long min_weight, const long long* col_offsets, long long capacity, int col_base, int* iy,
+                          long long* weight, int* count, double* xyz, int* col, int device, void* stream) {
+  return trace_peaks(true, workspace, workspace_bytes, n_slices, nx, ny, nms, min_points, min_weight, nullptr, col_offsets,
+                     capacity, col_base, iy, weight, count, xyz, col, device, stream);
+}
+int prh_trace_link(const long long* col_offsets, long long n_cols, int nx, const int* iy, const int* col,
+                   long long n_peaks, int link_cells, int gap_slope, int max_gap_cols, int* succ, int* pred, int device,
+                   void* stream) {
+  if (nx < 1 || nx > TRACE_MAX_CELLS || n_cols < 0 || n_cols > 0x7fffffffll || n_cols % nx != 0 || n_peaks < 0 ||
+      n_peaks > 0x7fffffffll)
+    return fail(PRH_ERR_ARG, "trace_link: bad argument (whole slices of nx columns, fewer than 2^31 peaks)");
+  if (link_cells < 0 || link_cells > TRACE_MAX_CELLS || gap_slope < 0 || gap_slope > TRACE_MAX_CELLS || max_gap_cols < 0 ||
+      max_gap_cols >= TRACE_MAX_CELLS)
+    return fail(PRH_ERR_ARG, "trace_link: 0 <= link_cells, gap_slope <= %d and 0 <= max_gap_cols < %d", TRACE_MAX_CELLS,
+                TRACE_MAX_CELLS);
+  if (n_peaks == 0) return PRH_OK;
+  if (!col_offsets || !iy || !col || !succ || !pred || n_cols == 0) return fail(PRH_ERR_ARG, "trace_link: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  const unsigned nblk = (unsigned)((n_peaks + TRACE_THREADS - 1) / TRACE_THREADS);
+  hipLaunchKernelGGL(trace_link_kernel, dim3(nblk), dim3(TRACE_THREADS), 0, (hipStream_t)stream, col_offsets, n_cols, nx,
+                     iy, col, n_peaks, link_cells, gap_slope, max_gap_cols, succ, pred);
+  LAUNCH_CHECK();
+  return PRH_OK;
 }
 
 // ------------------------------------------------------------------ fused cross-attention
