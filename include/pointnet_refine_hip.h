@@ -224,7 +224,10 @@ int prh_cast_perm_bf16(const float* src, long ld, uint16_t* dst, long rows, int 
 /* ... or both images in one pass from their sources: x16 = bf16(memory + pos), y16 = bf16(memory) with
  * pos = PositionalEncoding(xyz) = relu(xyz W0^T + b0) W2^T + b2 (src/model.py:64-75; W0 [256,3], W2 [256,256]).
  * The hidden layer and memory + pos never exist in fp32: 2 KB per point instead of 7 (pos_hidden, Linear
- * with residual, two casts).  xyz rows read in place (ld >= 3), memory [rows, 256] (ld >= 256). */
+ * with residual, two casts).  xyz rows read in place (ld >= 3), memory [rows, 256] (ld >= 256 and a multiple of 4,
+ * as for prh_cast_perm_bf16: the rows are read with 16-byte loads; anything else is refused with PRH_ERR_ARG).  A NULL
+ * b0 or b2 is read as zero.  Every rounding, in order: h = bf16(relu(fma(z, w0z, fma(y, w0y, fma(x, w0x, b0))))) in fp32,
+ * pos = bf16(W2) h accumulated in fp32, x16 = bf16((memory + pos) + b2), y16 = bf16(memory). */
 int prh_posmem_images(const float* xyz, long ldx, const float* w0, const float* b0, const float* w2, const float* b2,
                       const float* memory, long ldm, long rows, uint16_t* x16, uint16_t* y16, int device, void* stream);
 int prh_attn_fold_forward(const float* q, long ldq, const uint16_t* x16, const uint16_t* y16, const float* wk, long ldwk,

@@ -4180,10 +4180,11 @@ int prh_cast_perm_bf16(const float* src, long ld, uint16_t* dst, long rows, int 
 }
 /* Both row images of the folded attention from their sources in one pass (csrc/prh_attnfold.hpp):
  * x16 = bf16(memory + pos_emb(xyz)), y16 = bf16(memory) with pos_emb = Linear(3,256) + ReLU + Linear(256,256)
- * (src/model.py:64-75).  xyz rows are read in place (ld >= 3), memory [rows, 256] (ld >= 256). */
+ * (src/model.py:64-75).  xyz rows are read in place (ld >= 3), memory [rows, 256] (ld >= 256, a multiple of 4:
+ * the rows are read with 16-byte loads). */
 int prh_posmem_images(const float* xyz, long ldx, const float* w0, const float* b0, const float* w2, const float* b2,
                       const float* memory, long ldm, long rows, uint16_t* x16, uint16_t* y16, int device, void* stream) {
-  if (!xyz || !w0 || !w2 || !memory || !x16 || !y16 || rows < 0 || ldx < 3 || ldm < 256)
+  if (!xyz || !w0 || !w2 || !memory || !x16 || !y16 || rows < 0 || ldx < 3 || ldm < 256 || (ldm & 3))
     return fail(PRH_ERR_ARG, "posmem_images: bad argument");
   HIP_TRY(hipSetDevice(device));
   if (rows == 0) return PRH_OK;
