@@ -3,13 +3,15 @@ traced from every slice of the cloud (pointnet_refine_amd/trace.py), the traced 
 their ego frame, the refined pieces are linked across slices into lanes and fused into one polyline
 per lane in the drive frame (pointnet_refine_amd/link.py).
 
-    python examples/refine_cloud.py DRIVE_DIR --checkpoint CKPT --out MAP.json --intensity-floor F
+    python examples/refine_cloud.py DRIVE_DIR --checkpoint CKPT --out MAP.json --intensity-floor F|auto
                                     [--half-width W] [--support] [--gt GT_JSON] [--png DIR]
                                     [--batched] [--device-sync]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; MAP.json gets the fused map in the drive file layout.
 --intensity-floor F separates paint from asphalt: F is subtracted from every point's intensity and
 only what stays above 0 counts; without a floor that does, the tracer follows asphalt texture.
+--intensity-floor auto reads F from the road surface of the slices (pointnet_refine_amd/paintfloor.py)
+and prints one PAINT FLOOR line: the floor, the surface points it was read from, the share above it.
 --half-width W is the half width, in metres, of the strip beside the ego x axis that is traced.
 One PAINT TRACE line says how many slices, bright points, peaks and lines the tracer found; the map,
 --support, --gt, --png, --batched and --device-sync lines are those of examples/refine_predictions.py.
@@ -29,12 +31,13 @@ from refine_predictions import load_model, report_map  # noqa: E402
 
 
 def main():
+    from pointnet_refine_amd import paintfloor
     ap = argparse.ArgumentParser()
     ap.add_argument("drive_dir")
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--out", required=True)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--intensity-floor", type=float, required=True)
+    ap.add_argument("--intensity-floor", type=paintfloor.floor_argument, required=True, help="a number, or auto")
     ap.add_argument("--half-width", type=float, default=12.8)
     ap.add_argument("--gt", default=None)
     ap.add_argument("--png", default=None)
@@ -52,6 +55,8 @@ def main():
                              device_sync=args.device_sync, intensity_floor=args.intensity_floor,
                              half_width=args.half_width)
     rep = res["report"]
+    if args.intensity_floor == "auto":
+        print(paintfloor.floor_line(rep))
     print(f"PAINT TRACE  {rep['trace_slices']} slices   {rep['trace_bright_points']} bright points   "
           f"{rep['trace_peaks']} peaks   {rep['trace_lines']} lines ({rep['trace_lines_dropped_short']} short chains left out)")
     report_map(res, args)

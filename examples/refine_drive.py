@@ -4,7 +4,7 @@ input line in the drive frame (pointnet_refine_amd/fuse.py).
 
     python examples/refine_drive.py DRIVE_DIR LINES_JSON --checkpoint CKPT --out MAP.json
                                     [--noise S] [--seed N] [--gt GT_JSON] [--png DIR] [--batched]
-                                    [--support [--intensity-floor F]]
+                                    [--support [--intensity-floor F|auto]]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; LINES_JSON the lines to refine in the drive file layout
 (items[].category / attributes / position); MAP.json gets the fused map in the same layout.
@@ -61,6 +61,7 @@ def show_support(fused, before, attributes):
 
 
 def main():
+    from pointnet_refine_amd import paintfloor
     ap = argparse.ArgumentParser()
     ap.add_argument("drive_dir")
     ap.add_argument("lines_json")
@@ -73,7 +74,8 @@ def main():
     ap.add_argument("--step", type=float, default=0.5)
     ap.add_argument("--batched", action="store_true", help="contexts of all slices in one ragged GPU pass")
     ap.add_argument("--support", action="store_true", help="score the map against the cloud (no GT needed)")
-    ap.add_argument("--intensity-floor", type=float, default=0.0)
+    ap.add_argument("--intensity-floor", type=paintfloor.floor_argument, default=0.0,
+                    help="a number, or auto: read from the road surface of the slices (one PAINT FLOOR line)")
     args = ap.parse_args()
 
     from pointnet_refine_amd import drive, fuse
@@ -86,6 +88,8 @@ def main():
     res = fuse.refine_drive(load_model(args.checkpoint), args.drive_dir, None, lines, seed=args.seed, step=args.step,
                             batched=args.batched, support=args.support, intensity_floor=args.intensity_floor)
     rep = res["report"]
+    if args.intensity_floor == "auto":
+        print(paintfloor.floor_line(rep))
     print(f"{rep['slices']} slices, {rep['pieces']} pieces ({rep['pieces_sparse']} left out: sparse tube), "
           f"{rep['nodes_used']} of {rep['nodes']} nodes used, {rep['fused_polylines']} polylines")
     attributes = [dict(it["attributes"]) for it in items]

@@ -5,7 +5,7 @@ frames into lanes and fused into one polyline per lane in the drive frame
 
     python examples/refine_predictions.py DRIVE_DIR RESULTS_JSON --checkpoint CKPT --out MAP.json
                                           [--gt GT_JSON] [--png DIR] [--batched] [--device-sync]
-                                          [--support [--intensity-floor F]] [--lift [--lift-radius R]]
+                                          [--support [--intensity-floor F|auto]] [--lift [--lift-radius R]]
                                           [--align [--align-max-shift M] [--align-scope frame|drive] [--align-max-yaw RAD]]
 
 DRIVE_DIR holds pose/*.json and merged.pcd; RESULTS_JSON is the detector's output
@@ -120,6 +120,7 @@ def report_map(res, args):
 
 
 def main():
+    from pointnet_refine_amd import paintfloor
     ap = argparse.ArgumentParser()
     ap.add_argument("drive_dir")
     ap.add_argument("results_json")
@@ -134,7 +135,8 @@ def main():
     ap.add_argument("--batched", action="store_true", help="contexts of all frames in one ragged GPU pass")
     ap.add_argument("--device-sync", action="store_true", help="piece linking steps 5-6 on the GPU (the same map)")
     ap.add_argument("--support", action="store_true", help="score the map against the cloud (no GT needed)")
-    ap.add_argument("--intensity-floor", type=float, default=0.0)
+    ap.add_argument("--intensity-floor", type=paintfloor.floor_argument, default=0.0,
+                    help="a number, or auto: read from the road surface of the frames' slices (one PAINT FLOOR line)")
     ap.add_argument("--lift", action="store_true", help="put the detector's lines on the road read from the cloud")
     ap.add_argument("--lift-radius", type=float, default=0.5)
     ap.add_argument("--align", action="store_true", help="move the detector's lines in x y onto the paint of the cloud")
@@ -152,6 +154,8 @@ def main():
                                   align=args.align, align_max_shift=args.align_max_shift, align_scope=args.align_scope,
                                   align_max_yaw=args.align_max_yaw)
     rep = res["report"]
+    if args.intensity_floor == "auto":
+        print(paintfloor.floor_line(rep))
     if args.lift:
         print(f"GROUND LIFT  {rep['lift_lines_lifted']} of {rep['lift_lines']} lines lifted "
               f"({rep['lift_lines_unlifted']} left at the detector's z)   {rep['lift_stations_without_ground']} of "

@@ -1410,6 +1410,75 @@ int prh_trace_link(const long long* col_offsets, long long n_cols, int nx, const
                    long long n_peaks, int link_cells, int gap_slope, int max_gap_cols, int* succ, int* pred, int device,
                    void* stream);
 
+/* Paint floor - the rule.
+ * The intensity threshold between asphalt and paint, read from the cloud: what trace.paint_peaks,
+ * align.paint_scores and support.node_support take as intensity_floor.  The conventions are those of
+ * "Ground lift - the rule" and "Paint tracing - the rule": fp64 for geometry, one rounding per
+ * operation, no contraction, every constant computed once on the host and passed in; all
+ * accumulated quantities are integers, so nothing depends on point order, dtype, chunking or launch
+ * shape.  tests/_floor_oracle.py restates the rule in plain Python.
+ * Inputs.  points [T,4] = x y z intensity in the ego frame of their slice, float64 (is_double != 0)
+ * or float32, converted to fp64 first, which is exact.  slice_offsets [S+1] int64, what
+ * drive.slice_cloud returns; a slice holds fewer than 2^31 points.
+ * Surface grid.  The window is |x| < half_length (25.0), |y| < half_width (12.8), in cells ground_cell
+ * (1.0 m) wide: gx = ceil(2 * half_length / ground_cell), gy likewise, both on the host, 1 <= gx, gy
+ * <= 1024.  ix = floor((x + half_length) / ground_cell), iy = floor((y + half_width) / ground_cell),
+ * decided on the floor in fp64; a point with ix outside 0 .. gx - 1 or iy outside 0 .. gy - 1 is
+ * dropped (a non-finite x or y is).  ground [S,gx,gy] fp64 is the road height of every cell, NaN where
+ * there is none; the host fills it with one call of "Ground lift - the rule" (ground.ground_heights)
+ * whose queries are the cell centres (-half_length + (ix + 0.5) * ground_cell, -half_width + (iy +
+ * 0.5) * ground_cell), with radius = ground_radius (0.75, which covers the cell's corners) and
+ * ground's own defaults otherwise.
+ * Surface point.  A point is a surface point iff its cell's ground g is not NaN, z is finite and
+ * fabs(z - g) <= band (0.15), and I is finite and I >= 0 (-0.0 is).
+ * Histogram.  fb = floor(I / bin_width); the bin is n_bins - 1 if fb >= n_bins, else (int)fb - the
+ * comparison is made in fp64 before the conversion, so 1e30 clamps.  n_bins 256, 2 <= n_bins <=
+ * prh_floor_max_bins() = 1024; bin_width 1.0, positive and finite.  hist[s][b] (int64) counts the
+ * surface points of slice s.
+ * Threshold of one histogram row h[0 .. n-1] (a count below 0 counts as 0).  r[b] = isqrt(h[b]), the
+ * exact integer floor square root: Otsu's rule over the raw counts cuts the asphalt in half once the
+ * paint is below about 2 % of the surface points, over the square roots it stays between the two
+ * populations.  Wr = sum r, Mr = sum b * r, W = sum h.  For t = 1 .. n - 1: w0 = sum_{b<t}
+ * r, m0 = sum_{b<t} b * r, w1 = Wr - w0, m1 = Mr - m0, and over the raw counts c0 = sum_{b<t} h, c1 =
+ * W - c0.  t is a candidate iff c0 >= min_points and c1 >= min_points (16, >= 1) and w0 > 0 and w1 >
+ * 0.  Its score, in fp64 in exactly this order: d = (double)m1 / (double)w1 - (double)m0 /
+ * (double)w0; p = (double)w0 * (double)w1; score = p * (d * d).  t_lo is the smallest candidate with
+ * the largest score, provided that score is > 0.  t_hi is the largest t >= t_lo such that every u
+ * in t_lo .. t is a candidate with a score equal to score(t_lo): the plateau - between two separated
+ * populations the sums do not change, so the bits are equal.  t* = (t_lo + t_hi) >> 1 and floor =
+ * (double)t* * bin_width.  A row with no candidate, or with a largest score of 0, has no floor: t_lo
+ * = t_hi = t* = -1, and above, w0, m0 and score are 0.
+ * Drive floor.  The row that is the integer sum of all slice rows goes through the same kernel as
+ * one more row; paintfloor.paint_floor returns that row's floor, the slices' own go into its report.
+ * Scope.  The rule always splits: a road with no paint still gets a floor.  paint_share = c1 / W and
+ * contrast = mu1 - mu0 (the means, in intensity units, of the raw counts at and above t* and below
+ * it, computed on the host) are reported so the caller can judge; nothing is gated on them.
+ * Intensity is taken as it is: there is no range or incidence correction.
+ *   prh_floor_hist   zeroes hist [n_slices][n_bins], then reads rows 0 .. n_rows (n_rows <=
+ *                    slice_offsets[n_slices]) once: blocks of 256 threads walk 2048 rows each, x y in
+ *                    one load, z and I only inside the window, one fp64 gather from ground, one LDS
+ *                    atomic on the block's private histogram of its first slice (a point of another
+ *                    slice in a block that straddles a boundary goes to hist itself), and the
+ *                    non-zero bins are flushed with 64-bit integer atomics.
+ *   prh_test_floor_hist   the same with 1, 2, 4 or 8 lane-interleaved LDS copies of the block's
+ *                    histogram: the same bits, for the measurement that chose prh_floor_hist's count.
+ *   prh_floor_otsu   one wave per row of hist [n_rows][n_bins] (any int64 rows, slice or drive):
+ *                    t_lo, t_hi, t (int32), total = W, above = c1 at t*, w0, m0 at t_lo, wr, mr
+ *                    (int64) and score (fp64), each [n_rows].  No atomics.
+ * points must be aligned to two coordinates (16 bytes for fp64, 8 for float32).  PRH_ERR_ARG for a
+ * parameter outside the limits above, before the device is touched.  No float atomics. */
+int prh_floor_max_bins(void);
+int prh_floor_hist(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long n_rows,
+                   double half_length, double half_width, double ground_cell, int gx, int gy, const double* ground,
+                   double band, double bin_width, int n_bins, long long* hist, int device, void* stream);
+int prh_test_floor_hist(int copies, const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                        long long n_rows, double half_length, double half_width, double ground_cell, int gx, int gy,
+                        const double* ground, double band, double bin_width, int n_bins, long long* hist, int device,
+                        void* stream);
+int prh_floor_otsu(const long long* hist, int n_rows, int n_bins, long long min_points, int* t_lo, int* t_hi, int* t,
+                   long long* total, long long* above, long long* w0, long long* m0, long long* wr, long long* mr,
+                   double* score, int device, void* stream);
+
 /* Row f1, query side of DetrTransformerDecoderLayer (src/model.py:117,128,133):
  *   y = LayerNorm(x + dropout(r)), nn.LayerNorm(256) semantics (eps, biased variance, affine),
  * rows x 256 fp32, one pass forward and one backward.  The dropout decision is a counter hash of

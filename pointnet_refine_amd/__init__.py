@@ -11,6 +11,7 @@ from .support import map_support, marking_attributes, node_support  # noqa: F401
 from .ground import ground_heights, lift_lines, line_stations  # noqa: F401
 from .align import align_lines, paint_scores, pick_shift, shift_grid  # noqa: F401
 from .trace import paint_peaks, refine_cloud, trace_lines  # noqa: F401
+from .paintfloor import otsu_floors, paint_floor, surface_ground, surface_histograms  # noqa: F401
 
 __all__ = ["LineRefineNet", "MultiScalePointNetEncoder", "PositionalEncoding",
            "DetrTransformerDecoderLayer",
@@ -19,4 +20,5 @@ __all__ = ["LineRefineNet", "MultiScalePointNetEncoder", "PositionalEncoding",
            "node_support", "map_support", "marking_attributes",
            "ground_heights", "line_stations", "lift_lines",
            "paint_scores", "align_lines", "pick_shift", "shift_grid",
-           "paint_peaks", "trace_lines", "refine_cloud"]
+           "paint_peaks", "trace_lines", "refine_cloud",
+           "paint_floor", "surface_ground", "surface_histograms", "otsu_floors"]

@@ -111,6 +111,7 @@ EXPORTS = [
     "prh_align_select_cells_write", "prh_align_score_rigid",
     "prh_trace_max_nms", "prh_trace_workspace_bytes", "prh_trace_hist", "prh_trace_peaks_count", "prh_trace_peaks_write",
     "prh_trace_link",
+    "prh_floor_max_bins", "prh_floor_hist", "prh_test_floor_hist", "prh_floor_otsu",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
     "prh_pcd_parse", "prh_pcd_unpack14",
@@ -530,6 +531,16 @@ def _bind(lib):
     lib.prh_trace_peaks_write.argtypes = [vp, sz, i, i, i, i, i, ll, vp, ll, i, vp, vp, vp, vp, vp, i, vp]
     lib.prh_trace_link.restype = i
     lib.prh_trace_link.argtypes = [vp, ll, i, vp, vp, ll, i, i, i, vp, vp, i, vp]
+    if not hasattr(lib, "prh_floor_otsu"):
+        return lib      # an older build under PRH_LIB_PATH (A/B runs): it has no paint floor
+    lib.prh_floor_max_bins.restype = i
+    lib.prh_floor_max_bins.argtypes = []
+    lib.prh_floor_hist.restype = i
+    lib.prh_floor_hist.argtypes = [vp, i, vp, i, ll, dbl, dbl, dbl, i, i, vp, dbl, dbl, i, vp, i, vp]
+    lib.prh_test_floor_hist.restype = i
+    lib.prh_test_floor_hist.argtypes = [i] + lib.prh_floor_hist.argtypes
+    lib.prh_floor_otsu.restype = i
+    lib.prh_floor_otsu.argtypes = [vp, i, i, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     return lib
 
 

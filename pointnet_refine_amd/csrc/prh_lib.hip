@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include <stdlib.h>
@@ -36,6 +37,7 @@
 #include "prh_ground.hpp"
 #include "prh_align.hpp"
 #include "prh_trace.hpp"
+#include "prh_floor.hpp"
 #include "prh_pcd.hpp"
 #include "prh_kernels.hpp"
 
@@ -4053,6 +4055,79 @@ int prh_trace_link(const long long* col_offsets, long long n_cols, int nx, const
   const unsigned nblk = (unsigned)((n_peaks + TRACE_THREADS - 1) / TRACE_THREADS);
   hipLaunchKernelGGL(trace_link_kernel, dim3(nblk), dim3(TRACE_THREADS), 0, (hipStream_t)stream, col_offsets, n_cols, nx,
                      iy, col, n_peaks, link_cells, gap_slope, max_gap_cols, succ, pred);
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+
+// ------------------------------------------------------------------ paint floor
+int prh_floor_max_bins(void) { return FLOOR_MAX_BINS; }
+static int floor_hist(int copies, const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                      long long n_rows, double half_length, double half_width, double ground_cell, int gx, int gy,
+                      const double* ground, double band, double bin_width, int n_bins, long long* hist, int device,
+                      void* stream) {
+  if (n_slices < 0 || n_rows < 0 || n_rows >= (long long)FLOOR_RUN * 0x7fffffff)
+    return fail(PRH_ERR_ARG, "floor_hist: bad argument");
+  if (gx < 1 || gx > FLOOR_MAX_CELLS || gy < 1 || gy > FLOOR_MAX_CELLS)
+    return fail(PRH_ERR_ARG, "floor_hist: 1 <= gx, gy <= %d", FLOOR_MAX_CELLS);
+  if (n_bins < 2 || n_bins > FLOOR_MAX_BINS) return fail(PRH_ERR_ARG, "floor_hist: 2 <= n_bins <= %d", FLOOR_MAX_BINS);
+  if (!(half_length > 0.0) || !(half_length < 1e300) || !(half_width > 0.0) || !(half_width < 1e300) ||
+      !(ground_cell > 0.0) || !(ground_cell < 1e300) || !(bin_width > 0.0) || !(bin_width < 1e300) || !(band >= 0.0) ||
+      !(band < 1e300))
+    return fail(PRH_ERR_ARG, "floor_hist: half_length, half_width, ground_cell, bin_width positive, band >= 0, all finite");
+  if (copies != 1 && copies != 2 && copies != 4 && copies != 8) return fail(PRH_ERR_ARG, "floor_hist: 1, 2, 4 or 8 copies");
+  if (n_slices > 0 && !hist) return fail(PRH_ERR_ARG, "floor_hist: null pointer");
+  if (n_rows > 0 && (!points || !slice_offsets || !ground || n_slices == 0))
+    return fail(PRH_ERR_ARG, "floor_hist: points without a slice or a ground table");
+  if (((uintptr_t)points & (is_double ? 15 : 7)) != 0)
+    return fail(PRH_ERR_ARG, "floor_hist: points must be aligned to two coordinates (%d bytes)", is_double ? 16 : 8);
+  if (n_slices == 0) return PRH_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(hist, 0, (size_t)n_slices * (size_t)n_bins * sizeof(long long), st));
+  if (n_rows == 0) return PRH_OK;
+  const FloorGrid g{half_length, half_width, ground_cell, band, bin_width, gx, gy, n_bins};
+  const unsigned nblk = (unsigned)((n_rows + FLOOR_RUN - 1) / FLOOR_RUN);
+  auto launch = [&](auto copies_c) {                          // extern "C" holds no template: a generic lambda does
+    for_points(is_double, [&](auto v) {
+      using T = decltype(v);
+      hipLaunchKernelGGL((floor_hist_kernel<T, decltype(copies_c)::value>), dim3(nblk), dim3(FLOOR_THREADS), 0, st,
+                         (const T*)points, slice_offsets, n_slices, n_rows, g, ground, (unsigned long long*)hist);
+    });
+  };
+  switch (copies) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 4: launch(std::integral_constant<int, 4>{}); break;
+    default: launch(std::integral_constant<int, 8>{}); break;
+  }
+  LAUNCH_CHECK();
+  return PRH_OK;
+}
+int prh_floor_hist(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long n_rows,
+                   double half_length, double half_width, double ground_cell, int gx, int gy, const double* ground,
+                   double band, double bin_width, int n_bins, long long* hist, int device, void* stream) {
+  return floor_hist(FLOOR_COPIES, points, is_double, slice_offsets, n_slices, n_rows, half_length, half_width, ground_cell,
+                    gx, gy, ground, band, bin_width, n_bins, hist, device, stream);
+}
+int prh_test_floor_hist(int copies, const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                        long long n_rows, double half_length, double half_width, double ground_cell, int gx, int gy,
+                        const double* ground, double band, double bin_width, int n_bins, long long* hist, int device,
+                        void* stream) {
+  return floor_hist(copies, points, is_double, slice_offsets, n_slices, n_rows, half_length, half_width, ground_cell, gx, gy,
+                    ground, band, bin_width, n_bins, hist, device, stream);
+}
+int prh_floor_otsu(const long long* hist, int n_rows, int n_bins, long long min_points, int* t_lo, int* t_hi, int* t,
+                   long long* total, long long* above, long long* w0, long long* m0, long long* wr, long long* mr,
+                   double* score, int device, void* stream) {
+  if (n_rows < 0) return fail(PRH_ERR_ARG, "floor_otsu: bad argument");
+  if (n_bins < 2 || n_bins > FLOOR_MAX_BINS) return fail(PRH_ERR_ARG, "floor_otsu: 2 <= n_bins <= %d", FLOOR_MAX_BINS);
+  if (min_points < 1) return fail(PRH_ERR_ARG, "floor_otsu: min_points >= 1");
+  if (n_rows == 0) return PRH_OK;
+  if (!hist || !t_lo || !t_hi || !t || !total || !above || !w0 || !m0 || !wr || !mr || !score)
+    return fail(PRH_ERR_ARG, "floor_otsu: null pointer");
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(floor_otsu_kernel, dim3((unsigned)n_rows), dim3(64), 0, (hipStream_t)stream, hist, n_bins, min_points,
+                     t_lo, t_hi, t, total, above, w0, m0, wr, mr, score);
   LAUNCH_CHECK();
   return PRH_OK;
 }

@@ -397,7 +397,9 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     byte for byte, the same pieces in the same order up to which rows share a forward call.
     support=True scores the input lines and the fused map against the cloud (support.map_support
     with tube radius support_radius, default crop_radius, and intensity_floor): the lateral offset
-    of the paint before and after refinement, with no GT.
+    of the paint before and after refinement, with no GT.  intensity_floor may be "auto":
+    paintfloor.paint_floor reads it from the slices, once, as soon as they are cut, and the report
+    gains 'floor', 'floor_surface_points', 'floor_paint_share' and 'floor_contrast'.
 
     Returns {'fused', 'pieces' (P,M,3) float64 ego frame, 'piece_line', 'piece_slice' (P,),
     'pose_index' (plan_slices), 'poses' (S,7) of the slices, 'nodes' (fuse_pieces' node dict),
@@ -405,6 +407,7 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
     and, with support=True, 'support': {'input', 'fused' (map_support's dicts), 'attributes'
     (support.marking_attributes of the fused map, per line)}."""
     from . import drive as D
+    from . import paintfloor as PF
     G.device("fuse")
     if not 2 <= int(num_line_points) <= MAX_POINTS:
         raise ValueError(f"refine_drive: 2..{MAX_POINTS} points per line, got {num_line_points}")
@@ -429,6 +432,7 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
         points, offsets, _ = D.slice_cloud(cloud, pq, segment_len, D.RADIUS if radius is None else radius)
         clipped = D.clip_lines(lines, pq, segment_len)
         off = offsets.cpu().numpy()
+    intensity_floor, floor_report = PF.resolve(intensity_floor, points, off, "refine_drive")      # "auto" without a slice raises
     pieces, piece_slice, row, sparse = refine_slices(
         model, points, off, [[v for _, v in kept] for kept in clipped], num_line_points,
         num_context_points, crop_radius, decay_scale, seed, precision, min_tube_points, batched)
@@ -438,6 +442,8 @@ def refine_drive(model, drive_dir_or_cloud, poses, lines, num_line_points=32, nu
                                return_nodes=True)
     res = {"fused": fused, "pieces": pieces, "piece_line": piece_line, "piece_slice": piece_slice, "pose_index": chosen,
            "poses": pq, "nodes": nodes, "report": refine_report(len(chosen), pieces, sparse, nodes, fused, min_count)}
+    if floor_report is not None:
+        res["report"].update(PF.report_keys(floor_report))
     if support:
         res["support"] = cloud_support(cloud, fused, lines, step, crop_radius if support_radius is None else support_radius,
                                        intensity_floor, nodes["origin"])

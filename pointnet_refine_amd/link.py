@@ -468,6 +468,9 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     one align.align_lines_rigid call: a yaw of up to align_max_yaw radians about each frame's ego
     origin is swept with the shift, for the heading error a shift cannot take out, and the report
     gains 'align_yaws' (S,); at 0.0 the shift-only path runs untouched.
+    intensity_floor (the floor of support=True's scores) may be "auto": paintfloor.paint_floor reads it
+    from the frames' slices, once, as soon as they are cut, and the report gains 'floor',
+    'floor_surface_points', 'floor_paint_share' and 'floor_contrast'.
 
     Returns {'fused' [per kept cluster], 'pieces' (P,M,3) float64 ego frame, 'piece_frame' (P,) the
     row of 'poses' each piece was seen from, 'piece_slice' (the same), 'pose_index' (per used frame
@@ -475,6 +478,7 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
     'pieces', 'pieces_sparse', 'nodes', 'nodes_used', 'fused_polylines', 'candidates', 'edges',
     'clusters', 'clusters_kept', 'pieces_unlinked'}}."""
     from . import drive as D
+    from . import paintfloor as PF
     from . import predictions as PR
     G.device("link")
     m = int(num_line_points)
@@ -496,6 +500,7 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
         cloud = np.ascontiguousarray(D.load_merged_cloud(drive_dir), dtype=np.float32).reshape(-1, 4)
         points, offsets, _ = D.slice_cloud(cloud, pq, segment_len, PR.RADIUS if radius is None else radius)
         off = offsets.cpu().numpy()
+        intensity_floor, floor_report = PF.resolve(intensity_floor, points, off, "refine_predictions")
         cands_all = [[PR.pixel_to_ego(px) for px in frames[n]["pixels"]] for n in with_pose]
         if lift:
             from . import ground as GR
@@ -506,6 +511,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
                                                radius=align_radius, scope=align_scope)
         pieces, piece_frame, _, sparse = F.refine_slices(model, points, off, cands_all, m, num_context_points, crop_radius,
                                                          decay_scale, seed, precision, min_tube_points, batched)
+    else:
+        intensity_floor, floor_report = PF.resolve(intensity_floor, None, None, "refine_predictions")   # "auto" without a slice raises
     fused, nodes = fuse_unmatched(pieces, piece_frame, pq, gate, min_in, out_ratio, min_pieces, step, min_count, max_gap,
                                   origin, return_nodes=True, device_sync=device_sync, return_links=return_links)
     all_clusters = nodes["clusters_all"]
@@ -519,6 +526,8 @@ def refine_predictions(model, drive_dir, results_json, num_line_points=32, num_c
         if float(align_max_yaw) > 0.0:
             align_report.setdefault("yaws", np.zeros(0))
         report.update({"align_" + k: v for k, v in align_report.items()})
+    if floor_report is not None:
+        report.update(PF.report_keys(floor_report))
     res = {"fused": fused, "pieces": pieces, "piece_frame": piece_frame, "piece_slice": piece_frame.copy(),
            "pose_index": [int(c) for c in chosen[with_pose]], "poses": pq, "nodes": nodes, "report": report}
     if support:

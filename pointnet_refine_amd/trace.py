@@ -33,6 +33,7 @@ from . import _lib as L
 from . import drive as D
 from . import fuse as F
 from . import link as K
+from . import paintfloor as PF
 
 HALF_LENGTH, COL = 25.0, 0.5
 HALF_WIDTH, CELL = 12.8, 0.05
@@ -240,7 +241,10 @@ def refine_cloud(model, drive_dir_or_cloud, poses=None, num_line_points=32, num_
     candidates; link.fuse_unmatched links and fuses the pieces (gate, min_in, out_ratio, min_pieces,
     step, min_count, max_gap, origin, device_sync, return_links: link.refine_predictions' arguments
     with its defaults); support=True scores the map against the cloud (fuse.cloud_support with
-    support_radius, default crop_radius, and intensity_floor).
+    support_radius, default crop_radius, and intensity_floor).  intensity_floor="auto" reads the floor
+    from the slices themselves (paintfloor.paint_floor, once, before tracing; tracing and support use
+    it alike) and the report gains 'floor', 'floor_surface_points', 'floor_paint_share' and
+    'floor_contrast'.
 
     Returns link.refine_predictions' dict - 'fused', 'pieces', 'piece_frame', 'piece_slice',
     'pose_index' (plan_slices' indices), 'poses', 'nodes', 'report', with support=True 'support' -
@@ -268,7 +272,8 @@ def refine_cloud(model, drive_dir_or_cloud, poses=None, num_line_points=32, num_
     trace_kw = dict(half_length=float(segment_len) / 2.0, col=col, half_width=half_width, cell=cell,
                     intensity_floor=intensity_floor, nms=nms, min_points=min_points, min_weight=min_weight,
                     link_cells=link_cells, gap_slope=gap_slope, max_gap_cols=max_gap_cols)
-    _params("refine_cloud", **trace_kw)                          # a bad parameter raises before the cloud is cut
+    # a bad parameter raises before the cloud is cut; "auto" is read from the slices below
+    _params("refine_cloud", **dict(trace_kw, intensity_floor=0.0 if intensity_floor == "auto" else intensity_floor))
     _chain_params("refine_cloud", min_peaks, min_length)
     pieces, piece_slice, sparse = np.zeros((0, m, 3)), np.zeros(0, dtype=np.int64), 0
     traced = []
@@ -276,9 +281,14 @@ def refine_cloud(model, drive_dir_or_cloud, poses=None, num_line_points=32, num_
     if len(chosen):
         points, offsets, _ = D.slice_cloud(cloud, pq, segment_len, D.RADIUS if radius is None else radius)
         off = offsets.cpu().numpy()
+        # "auto": read from the slices, once, for tracing and support alike
+        intensity_floor, floor_report = PF.resolve(intensity_floor, points, off, "refine_cloud")
+        trace_kw["intensity_floor"] = intensity_floor
         traced, trace_report = trace_lines(points, off, min_peaks, min_length, **trace_kw)
         pieces, piece_slice, _, sparse = F.refine_slices(model, points, off, traced, m, num_context_points, crop_radius,
                                                          decay_scale, seed, precision, min_tube_points, batched)
+    else:
+        intensity_floor, floor_report = PF.resolve(intensity_floor, None, None, "refine_cloud")      # "auto" without a slice raises
     fused, nodes = K.fuse_unmatched(pieces, piece_slice, pq, gate, min_in, out_ratio, min_pieces, step, min_count, max_gap,
                                     origin, return_nodes=True, device_sync=device_sync, return_links=return_links)
     all_clusters = nodes["clusters_all"]
@@ -287,6 +297,8 @@ def refine_cloud(model, drive_dir_or_cloud, poses=None, num_line_points=32, num_
                    "clusters": int(all_clusters.max()) + 1 if len(all_clusters) else 0, "clusters_kept": len(fused),
                    "pieces_unlinked": int((nodes["cluster"] < 0).sum())})
     report.update({"trace_" + k: v for k, v in trace_report.items()})
+    if floor_report is not None:
+        report.update(PF.report_keys(floor_report))
     res = {"fused": fused, "pieces": pieces, "piece_frame": piece_slice, "piece_slice": piece_slice.copy(),
            "pose_index": [int(c) for c in chosen], "poses": pq, "nodes": nodes, "report": report, "traced": traced}
     if support:
