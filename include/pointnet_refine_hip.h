@@ -1371,7 +1371,9 @@ int prh_align_score_rigid(const void* records, const long long* cand_offsets, lo
  * ordered by their head's (ix, iy); their vertices are the peaks' x y z.
  * Scope.  The rule follows ridges that run within about atan(link_cells * cell / col) of the ego x
  * axis (17 degrees at the defaults); stop lines and crosswalks are not traced.  Without an
- * intensity_floor that separates paint from asphalt it traces asphalt texture.
+ * intensity_floor that separates paint from asphalt it traces asphalt texture.  A point is taken
+ * whatever its height, so bright things above the road are traced with the paint unless the surface
+ * gate is on ("Paint tracing - the rule: surface gate", below).
  * All sums are integers, so the result does not depend on the order of the points, on their dtype,
  * on the chunking of the slices or on the launch shape: it is bitwise reproducible by construction.
  *   prh_trace_workspace_bytes  the tables of n_slices slices: n [C] int32 first, then w, wx, wy, wz
@@ -1401,6 +1403,47 @@ size_t prh_trace_workspace_bytes(int n_slices, int nx, int ny);
 int prh_trace_hist(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long first_row,
                    long long n_rows, double half_length, double col, int nx, double half_width, double cell, int ny,
                    double intensity_floor, void* workspace, size_t workspace_bytes, int device, void* stream);
+/* Paint tracing - the rule: surface gate.
+ * A merged cloud holds bright things that are not paint - the plate and reflectors of a followed
+ * vehicle smeared into a trail half a metre above the lane, guard-rail reflectors, signs and gantries
+ * over the carriageway - and the weight min(I - floor, 4096) favours them.  With the gate the tables
+ * see the points on the road surface only.  It is off unless asked for (trace.paint_peaks with a
+ * ground table, trace.refine_cloud with surface=True); without it every bit is as above.  The
+ * conventions are those of "Paint tracing - the rule" and "Paint floor - the rule": fp64, one
+ * rounding per operation, no contraction, every constant computed once on the host and passed in;
+ * tests/_trace_surface_oracle.py restates the gate.
+ * Gate.  A point that passes every test of "Grid" and "Point weight" above (inside the trace grid, z
+ * finite, |z| <= 512, qi > 0) is tested further.  gix = floor((x + g_half_length) / ground_cell), giy
+ * = floor((y + g_half_width) / ground_cell): the expressions of "Paint floor - the rule: Surface
+ * grid", decided on the floor in fp64, over ground [S,gx,gy] fp64, the road height of every cell, NaN
+ * where there is none (paintfloor.surface_ground; 1 <= gx, gy <= 1024, g_half_length, g_half_width and
+ * ground_cell positive and finite; trace.paint_peaks passes its own half_length and half_width and
+ * ground_cell 1.0).  The point is off the surface iff gix lies outside 0 .. gx - 1, or giy outside 0
+ * .. gy - 1, or g = ground[s][gix][giy] is NaN, or !(fabs(z - g) <= band); band 0.15
+ * (paintfloor.BAND), finite and >= 0.  A point off the surface adds nothing to the tables and 1 to
+ * off_surface[s] (int64).  The intensity clauses of the floor rule's "Surface point" do not apply:
+ * qi > 0 has decided them already, and with a negative intensity_floor the two would disagree.
+ * A point that fails an earlier test (outside the trace grid, a bad z, qi == 0) is dropped as
+ * before and is not counted in off_surface.  Box, peak, links and lines are unchanged; all sums stay
+ * integers, so the bits do not depend on point order, dtype, chunking or launch shape.
+ * Scope.  The ground table has constant cells of ground_cell (1 m): the gate is as good as "Ground
+ * lift - the rule" is on that cell.  A point outside the ground window is off the surface.  Paint on
+ * a structure the ground rule does not call road - a bridge deck above the lowest mode of its cell -
+ * is gated out with the structure.
+ *   prh_trace_hist_surface  prh_trace_hist with the gate: its arguments up to workspace_bytes, then
+ *                         the ground window and ground [n_slices][gx][gy], the rows of the chunk's
+ *                         slices, band, and off_surface [n_slices], zeroed here.  The same point
+ *                         function as prh_trace_hist, the gate compiled in: x y in one load, the
+ *                         grid test, z and I, qi, and only then the ground cell and one fp64 gather
+ *                         (bright points only), the band test, the five atomics.  off_surface is
+ *                         reduced within the wave by ballot / popcount: one 64-bit integer atomic per
+ *                         wave and slice touched.  PRH_ERR_ARG as prh_trace_hist and prh_floor_hist
+ *                         give it, before the device is touched.  No float atomics. */
+int prh_trace_hist_surface(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                           long long first_row, long long n_rows, double half_length, double col, int nx,
+                           double half_width, double cell, int ny, double intensity_floor, void* workspace,
+                           size_t workspace_bytes, double g_half_length, double g_half_width, double ground_cell, int gx,
+                           int gy, const double* ground, double band, long long* off_surface, int device, void* stream);
 int prh_trace_peaks_count(void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny, int nms, int min_points,
                           long long min_weight, int* col_counts, int device, void* stream);
 int prh_trace_peaks_write(void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny, int nms, int min_points,

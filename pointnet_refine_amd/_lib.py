@@ -109,8 +109,8 @@ EXPORTS = [
     "prh_align_select_write", "prh_align_score",
     "prh_align_max_poses", "prh_align_select_cells_workspace_bytes", "prh_align_select_cells_count",
     "prh_align_select_cells_write", "prh_align_score_rigid",
-    "prh_trace_max_nms", "prh_trace_workspace_bytes", "prh_trace_hist", "prh_trace_peaks_count", "prh_trace_peaks_write",
-    "prh_trace_link",
+    "prh_trace_max_nms", "prh_trace_workspace_bytes", "prh_trace_hist", "prh_trace_hist_surface", "prh_trace_peaks_count",
+    "prh_trace_peaks_write", "prh_trace_link",
     "prh_floor_max_bins", "prh_floor_hist", "prh_test_floor_hist", "prh_floor_otsu",
     "prh_pcd_group_rows", "prh_pcd_format_workspace_bytes", "prh_pcd_format_count", "prh_pcd_format_write",
     "prh_pcd_index_blocks", "prh_pcd_index_count", "prh_pcd_index_write", "prh_pcd_parse_workspace_bytes",
@@ -541,6 +541,10 @@ def _bind(lib):
     lib.prh_test_floor_hist.argtypes = [i] + lib.prh_floor_hist.argtypes
     lib.prh_floor_otsu.restype = i
     lib.prh_floor_otsu.argtypes = [vp, i, i, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
+    if not hasattr(lib, "prh_trace_hist_surface"):
+        return lib      # an older build under PRH_LIB_PATH (A/B runs): it has no surface gate
+    lib.prh_trace_hist_surface.restype = i
+    lib.prh_trace_hist_surface.argtypes = lib.prh_trace_hist.argtypes[:-2] + [dbl, dbl, dbl, i, i, vp, dbl, vp, i, vp]
     return lib
 
 

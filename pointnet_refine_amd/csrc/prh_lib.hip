@@ -3978,34 +3978,67 @@ static int trace_tables(const char* what, void* workspace, size_t workspace_byte
   }
   return PRH_OK;
 }
-int prh_trace_hist(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long first_row,
-                   long long n_rows, double half_length, double col, int nx, double half_width, double cell, int ny,
-                   double intensity_floor, void* workspace, size_t workspace_bytes, int device, void* stream) {
+// sg == nullptr: the ungated pass.  Else the surface gate with ground [n_slices][gx][gy] and off_surface [n_slices].
+static int trace_hist(const char* what, const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                      long long first_row, long long n_rows, double half_length, double col, int nx, double half_width,
+                      double cell, int ny, double intensity_floor, void* workspace, size_t workspace_bytes,
+                      const TraceSurface* sg, const double* ground, long long* off_surface, int device, void* stream) {
   TraceTables t{};
-  TRY_RC(trace_tables("trace_hist", workspace, workspace_bytes, n_slices, nx, ny, t));
-  if (first_row < 0 || n_rows < 0 || n_rows >= 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "trace_hist: bad argument");
+  TRY_RC(trace_tables(what, workspace, workspace_bytes, n_slices, nx, ny, t));
+  if (first_row < 0 || n_rows < 0 || n_rows >= 256ll * 0x7fffffff) return fail(PRH_ERR_ARG, "%s: bad argument", what);
   if (!(half_length > 0.0) || !(half_length <= 128.0) || !(half_width > 0.0) || !(half_width <= 128.0) || !(col > 0.0) ||
       !(cell > 0.0) || !(col < 1e300) || !(cell < 1e300))
-    return fail(PRH_ERR_ARG, "trace_hist: 0 < half_length, half_width <= 128 and col, cell positive and finite");
+    return fail(PRH_ERR_ARG, "%s: 0 < half_length, half_width <= 128 and col, cell positive and finite", what);
   if (!(intensity_floor == intensity_floor) || !(fabs(intensity_floor) < 1e300))
-    return fail(PRH_ERR_ARG, "trace_hist: intensity_floor must be finite");
-  if (n_rows > 0 && (!points || !slice_offsets || n_slices == 0)) return fail(PRH_ERR_ARG, "trace_hist: points without a slice");
+    return fail(PRH_ERR_ARG, "%s: intensity_floor must be finite", what);
+  if (sg) {
+    if (sg->gx < 1 || sg->gx > FLOOR_MAX_CELLS || sg->gy < 1 || sg->gy > FLOOR_MAX_CELLS)
+      return fail(PRH_ERR_ARG, "%s: 1 <= gx, gy <= %d", what, FLOOR_MAX_CELLS);
+    if (!(sg->half_length > 0.0) || !(sg->half_length < 1e300) || !(sg->half_width > 0.0) || !(sg->half_width < 1e300) ||
+        !(sg->cell > 0.0) || !(sg->cell < 1e300) || !(sg->band >= 0.0) || !(sg->band < 1e300))
+      return fail(PRH_ERR_ARG, "%s: g_half_length, g_half_width, ground_cell positive, band >= 0, all finite", what);
+    if (n_slices > 0 && !off_surface) return fail(PRH_ERR_ARG, "%s: null pointer", what);
+    if (n_rows > 0 && !ground) return fail(PRH_ERR_ARG, "%s: points without a ground table", what);
+  }
+  if (n_rows > 0 && (!points || !slice_offsets || n_slices == 0)) return fail(PRH_ERR_ARG, "%s: points without a slice", what);
   if (((uintptr_t)points & (is_double ? 15 : 7)) != 0)
-    return fail(PRH_ERR_ARG, "trace_hist: points must be aligned to two coordinates (%d bytes)", is_double ? 16 : 8);
+    return fail(PRH_ERR_ARG, "%s: points must be aligned to two coordinates (%d bytes)", what, is_double ? 16 : 8);
   if (n_slices == 0) return PRH_OK;
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(workspace, 0, prh_trace_workspace_bytes(n_slices, nx, ny), st));
+  if (sg) HIP_TRY(hipMemsetAsync(off_surface, 0, (size_t)n_slices * sizeof(long long), st));
   if (n_rows == 0) return PRH_OK;
   const TraceGrid g{half_length, col, half_width, cell, intensity_floor, nx, ny};
   const unsigned nblk = (unsigned)((n_rows + TRACE_THREADS - 1) / TRACE_THREADS);
   for_points(is_double, [&](auto v) {
     using T = decltype(v);
-    hipLaunchKernelGGL(trace_hist_kernel<T>, dim3(nblk), dim3(TRACE_THREADS), 0, st, (const T*)points, slice_offsets,
-                       n_slices, first_row, n_rows, g, t);
+    if (sg)
+      hipLaunchKernelGGL(trace_hist_surface_kernel<T>, dim3(nblk), dim3(TRACE_THREADS), 0, st, (const T*)points,
+                         slice_offsets, n_slices, first_row, n_rows, g, t, *sg, ground, (unsigned long long*)off_surface);
+    else
+      hipLaunchKernelGGL(trace_hist_kernel<T>, dim3(nblk), dim3(TRACE_THREADS), 0, st, (const T*)points, slice_offsets,
+                         n_slices, first_row, n_rows, g, t);
   });
   LAUNCH_CHECK();
   return PRH_OK;
+}
+int prh_trace_hist(const void* points, int is_double, const long long* slice_offsets, int n_slices, long long first_row,
+                   long long n_rows, double half_length, double col, int nx, double half_width, double cell, int ny,
+                   double intensity_floor, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  return trace_hist("trace_hist", points, is_double, slice_offsets, n_slices, first_row, n_rows, half_length, col, nx,
+                    half_width, cell, ny, intensity_floor, workspace, workspace_bytes, nullptr, nullptr, nullptr, device,
+                    stream);
+}
+int prh_trace_hist_surface(const void* points, int is_double, const long long* slice_offsets, int n_slices,
+                           long long first_row, long long n_rows, double half_length, double col, int nx,
+                           double half_width, double cell, int ny, double intensity_floor, void* workspace,
+                           size_t workspace_bytes, double g_half_length, double g_half_width, double ground_cell, int gx,
+                           int gy, const double* ground, double band, long long* off_surface, int device, void* stream) {
+  const TraceSurface sg{g_half_length, g_half_width, ground_cell, band, gx, gy};
+  return trace_hist("trace_hist_surface", points, is_double, slice_offsets, n_slices, first_row, n_rows, half_length, col,
+                    nx, half_width, cell, ny, intensity_floor, workspace, workspace_bytes, &sg, ground, off_surface, device,
+                    stream);
 }
 static int trace_peaks(bool write, void* workspace, size_t workspace_bytes, int n_slices, int nx, int ny, int nms,
                        int min_points, long long min_weight, int* col_counts, const long long* col_offsets,

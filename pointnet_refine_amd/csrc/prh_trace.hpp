@@ -6,6 +6,10 @@
 //                    search (once per block where the block lies in one slice), then one 32-bit and
 //                    four 64-bit integer atomics on the cell's sums.
 //                    The hot pass: it reads every point once.
+//   trace_hist_surface_kernel   the same point function with the surface gate compiled in ("Paint
+//                    tracing - the rule: surface gate"): after qi > 0, the ground cell of the point and
+//                    one fp64 gather from the road-height table; a point off the surface touches no
+//                    table and is counted per slice, one 64-bit integer atomic per wave and slice.
 //   trace_peaks_kernel<WRITE=false>   one wave per (slice, column).  The column's w goes through LDS
 //                    TRACE_TILE cells at a time with a halo of TRACE_HALO cells on both sides; the box
 //                    sums b are formed in LDS; a lane tests one cell against its 2 * nms neighbours;
@@ -49,16 +53,26 @@ template <typename T> struct TracePair;
 template <> struct TracePair<double> { typedef double2 type; };
 template <> struct TracePair<float> { typedef float2 type; };
 
+// the surface gate ("Paint tracing - the rule: surface gate"): the ground window and its table's shape
+struct TraceSurface {
+  double half_length, half_width, cell, band;
+  int gx, gy;
+};
+
+// One point of the hist pass, for both kernels below.  SURFACE = false is trace_hist_kernel as it was:
+// the gate's arguments are not read.  SURFACE = true: a point that passed every test up to qi > 0 is
+// tested against ground [S][gx][gy] (the rows of the same slices as slice_off); the function returns
+// true for a point off the surface, with its slice in s_out, and such a point touches no table.
 // rows row0 .. row0 + n of pts; slice_off [S+1] holds absolute rows with slice_off[0] <= row0 and
 // row0 + n <= slice_off[S]
-template <typename T>
-__global__ __launch_bounds__(TRACE_THREADS) void trace_hist_kernel(
-    const T* __restrict__ pts, const long long* __restrict__ slice_off, int S, long long row0, long long n, TraceGrid g,
-    TraceTables t) {
+template <typename T, bool SURFACE>
+__device__ __forceinline__ bool trace_hist_point(
+    const T* __restrict__ pts, const long long* __restrict__ slice_off, int S, long long row0, long long n,
+    const TraceGrid& g, const TraceTables& t, const TraceSurface& sg, const double* __restrict__ ground, int& s_out) {
 #pragma clang fp contract(off)
   typedef typename TracePair<T>::type pair_t;
   const long long k = (long long)blockIdx.x * TRACE_THREADS + threadIdx.x;
-  if (k >= n) return;
+  if (k >= n) return false;
   const long long i = row0 + k;
   // the rows of a block lie in one slice far more often than not: one search per block, on uniform
   // addresses and in flight with the point's own loads, instead of one at the end of every wave's chain
@@ -68,13 +82,26 @@ __global__ __launch_bounds__(TRACE_THREADS) void trace_hist_kernel(
   const pair_t xy = reinterpret_cast<const pair_t*>(pts + 4 * i)[0];
   const double x = (double)xy.x, y = (double)xy.y;
   const double fx = floor((x + g.half_length) / g.col), fy = floor((y + g.half_width) / g.cell);
-  if (!(fx >= 0.0 && fx < (double)g.nx && fy >= 0.0 && fy < (double)g.ny)) return;      // NaN and inf leave here
+  if (!(fx >= 0.0 && fx < (double)g.nx && fy >= 0.0 && fy < (double)g.ny)) return false;      // NaN and inf leave here
   const pair_t zi = reinterpret_cast<const pair_t*>(pts + 4 * i)[1];
   const double z = (double)zi.x;
-  if (!(isfinite(z) && fabs(z) <= 512.0)) return;
+  if (!(isfinite(z) && fabs(z) <= 512.0)) return false;
   const long long qi = align_qi((double)zi.y, g.intensity_floor);
-  if (qi <= 0) return;
+  if (qi <= 0) return false;
   const int s = one_slice ? s_block : bev_slice_of(slice_off, S, i);
+  if constexpr (SURFACE) {
+    // only a bright point comes here: the gather is paid by the paint and what is as bright
+    const double gfx = floor((x + sg.half_length) / sg.cell), gfy = floor((y + sg.half_width) / sg.cell);
+    bool on = gfx >= 0.0 && gfx < (double)sg.gx && gfy >= 0.0 && gfy < (double)sg.gy;
+    if (on) {
+      const double gz = ground[((long long)s * sg.gx + (long long)gfx) * sg.gy + (long long)gfy];
+      on = gz == gz && fabs(z - gz) <= sg.band;
+    }
+    if (!on) {
+      s_out = s;
+      return true;
+    }
+  }
   const long long c = ((long long)s * g.nx + (long long)fx) * g.ny + (long long)fy;
   const long long qx = (long long)rint(x * 1024.0), qy = (long long)rint(y * 1024.0), qz = (long long)rint(z * 1024.0);
   atomicAdd(t.n + c, 1);
@@ -82,6 +109,35 @@ __global__ __launch_bounds__(TRACE_THREADS) void trace_hist_kernel(
   atomicAdd(t.wx + c, (unsigned long long)(qi * qx));
   atomicAdd(t.wy + c, (unsigned long long)(qi * qy));
   atomicAdd(t.wz + c, (unsigned long long)(qi * qz));
+  return false;
+}
+
+template <typename T>
+__global__ __launch_bounds__(TRACE_THREADS) void trace_hist_kernel(
+    const T* __restrict__ pts, const long long* __restrict__ slice_off, int S, long long row0, long long n, TraceGrid g,
+    TraceTables t) {
+  int s = 0;
+  trace_hist_point<T, false>(pts, slice_off, S, row0, n, g, t, TraceSurface{}, nullptr, s);
+}
+
+// off_surface [S], zeroed by the caller.  Every lane of the wave is back here after its point: the
+// lanes off the surface are counted per slice with ballot / popcount and their first lane adds the
+// count, so a wave that straddles slice boundaries counts each side into its own slice.
+template <typename T>
+__global__ __launch_bounds__(TRACE_THREADS) void trace_hist_surface_kernel(
+    const T* __restrict__ pts, const long long* __restrict__ slice_off, int S, long long row0, long long n, TraceGrid g,
+    TraceTables t, TraceSurface sg, const double* __restrict__ ground, unsigned long long* __restrict__ off_surface) {
+  int s = -1;
+  const bool off = trace_hist_point<T, true>(pts, slice_off, S, row0, n, g, t, sg, ground, s);
+  const int lane = threadIdx.x & 63;
+  unsigned long long left = __ballot(off);
+  while (left) {                           // uniform over the wave: one round per slice touched
+    const int first = __ffsll((long long)left) - 1;
+    const int s_first = __shfl(s, first, 64);
+    const unsigned long long same = __ballot(off && s == s_first);
+    if (lane == first) atomicAdd(off_surface + s_first, (unsigned long long)__popcll(same));
+    left &= ~same;
+  }
 }
 
 // the sum of tab over cells iy - 1, iy, iy + 1 of the column that starts at base

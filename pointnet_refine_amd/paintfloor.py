@@ -99,6 +99,22 @@ def surface_ground(points, slice_offsets, half_length=HALF_LENGTH, half_width=HA
     return _surface_ground(pts, off, p)
 
 
+def ground_shape(ground, n_slices, p, what):
+    """ValueError unless a caller's prebuilt ground table is (n_slices, gx, gy) of p = _params(...)."""
+    shape = tuple(ground.shape) if torch.is_tensor(ground) else np.shape(ground)
+    if shape != (n_slices, p["gx"], p["gy"]):
+        raise ValueError(f"{what}: ground must be {(n_slices, p['gx'], p['gy'])}, got {shape}")
+
+
+def _ground_table(ground, pts, off, p, dev, what):
+    """The (S,gx,gy) float64 CUDA table: surface_ground's (None), or the caller's own, checked."""
+    if ground is None:
+        return _surface_ground(pts, off, p)
+    ground = G.as_cuda(ground, dev, what, torch.float64)
+    ground_shape(ground, len(off) - 1, p, what)
+    return ground
+
+
 def _histograms(pts, off, ground, p, dev, copies=None):
     n_s, n_bins = len(off) - 1, p["n_bins"]
     hist = torch.empty((n_s, n_bins), dtype=torch.int64, device=dev)
@@ -129,13 +145,7 @@ def surface_histograms(points, slice_offsets, ground=None, copies=None, **params
     dev, pts, off = _sliced(points, slice_offsets, what)
     if copies is not None and copies not in (1, 2, 4, 8):
         raise ValueError(f"{what}: copies must be 1, 2, 4 or 8")
-    if ground is None:
-        ground = _surface_ground(pts, off, p)
-    else:
-        ground = G.as_cuda(ground, dev, what, torch.float64)
-        if tuple(ground.shape) != (len(off) - 1, p["gx"], p["gy"]):
-            raise ValueError(f"{what}: ground must be {(len(off) - 1, p['gx'], p['gy'])}, got {tuple(ground.shape)}")
-    return _histograms(pts, off, ground, p, dev, copies)
+    return _histograms(pts, off, _ground_table(ground, pts, off, p, dev, what), p, dev, copies)
 
 
 def otsu_floors(hist, min_points=MIN_POINTS, bin_width=BIN_WIDTH):
@@ -167,11 +177,12 @@ def otsu_floors(hist, min_points=MIN_POINTS, bin_width=BIN_WIDTH):
     return out
 
 
-def paint_floor(points, slice_offsets, **params):
+def paint_floor(points, slice_offsets, ground=None, **params):
     """The drive's intensity floor, read from its own road ("Paint floor - the rule").
 
-    points, slice_offsets: as surface_histograms takes them; params: its parameters and min_points.
-    One surface_ground call, one pass over the points, then one otsu_floors call over the slices'
+    points, slice_offsets, ground: as surface_histograms takes them (ground: a table surface_ground
+    has already built for these slices and parameters, which is then not built again); params: its
+    parameters and min_points.  One surface_ground call, one pass over the points, then one otsu_floors call over the slices'
     rows and their integer sum, the drive's row.  Returns (floor: float, report {'floor', 'bin' (t*),
     'plateau' (t_lo, t_hi), 'surface_points', 'paint_share' (c1 / W), 'contrast' (mu1 - mu0 of the raw
     counts, in intensity units), 'floor_per_slice' (S,) float64 (NaN: none), 'slices_without_floor'});
@@ -179,7 +190,7 @@ def paint_floor(points, slice_offsets, **params):
     what = "paint_floor"
     p = _params(what, **params)
     dev, pts, off = _sliced(points, slice_offsets, what)
-    hist = _histograms(pts, off, _surface_ground(pts, off, p), p, dev)
+    hist = _histograms(pts, off, _ground_table(ground, pts, off, p, dev, what), p, dev)
     rows = torch.cat([hist, hist.sum(0, keepdim=True)])
     res = {k: v.cpu().numpy() for k, v in otsu_floors(rows, p["min_points"], p["bin_width"]).items()}
     t = int(res["t"][-1])
@@ -198,15 +209,16 @@ def paint_floor(points, slice_offsets, **params):
     return report["floor"], report
 
 
-def resolve(intensity_floor, points, slice_offsets, what):
+def resolve(intensity_floor, points, slice_offsets, what, ground=None, **params):
     """What a caller's intensity_floor means: a number passes through unchanged, with the report
-    None; the string "auto" gives paint_floor(points, slice_offsets); anything else raises ValueError."""
+    None; the string "auto" gives paint_floor(points, slice_offsets, ground, **params); anything else
+    raises ValueError."""
     if isinstance(intensity_floor, str):
         if intensity_floor != "auto":
             raise ValueError(f"{what}: intensity_floor must be a number or 'auto', got {intensity_floor!r}")
         if points is None:
             raise ValueError(f"{what}: intensity_floor='auto' needs a sliced cloud, and there is no slice")
-        return paint_floor(points, slice_offsets)
+        return paint_floor(points, slice_offsets, ground, **params)
     try:
         ok = not isinstance(intensity_floor, (bool, np.bool_)) and float(intensity_floor) is not None
     except (TypeError, ValueError):
